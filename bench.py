@@ -3,6 +3,7 @@
 bench.py -- predicted-params/sec of the GHN-3 hot path (GHN fwd+bwd) on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--model ghn3xlm16] [--nodes 256] [--compute f32]
+                    [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch of synthetic graphs per GPU:
     GHN3 forward (Graphormer + decoders + tile/normalise -> all target-network weights)
@@ -14,10 +15,23 @@ Inputs (graph tensors, index tables, GHN weights) are resident in HBM before the
 `--gpus N` with N > 1 and no RANK in the environment starts N ranks itself (fresh child processes, one per GPU, created
 before this process touches the GPU); under `python -m torch.distributed.run` the ranks are the launcher's.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline` objects, plus (N = 1)
-`forward` (forward-only time and its fraction of the 16-bit MFMA peak on algorithmic FLOPs: the north star's >= 30 %
-target), `fresh_graph_ms_per_step` (a NEW architecture compiled every step on a host thread, what train_ghn_ddp.py does)
-and `f32_mode` (the exact-fp32 configuration of the same workload).
+Prints ONE JSON line on rank 0: `metric`, `value` (predicted parameters per second over the K timed steps), `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` (milliseconds of one timed step) and the workload's `config`.  A plain run does
+nothing else: set-up, W warm-up steps, the K timed steps, the line.
+
+`--full` adds everything measured beside the headline, each in runs of its own behind the timed region: the `roofline`
+object (per-kernel times of extra instrumented and serialised steps), `cpu_baseline` (the CPU restatement on the same
+inputs), for N = 1 `forward` (forward-only time and its fraction of the 16-bit MFMA peak on algorithmic FLOPs: the north
+star's >= 30 % target), `fresh_graph_ms_per_step` (a NEW architecture compiled every step in loader worker processes, what
+train_ghn_ddp.py does), `train_step`, the 2- and 4-graph batches and `f32_mode` (the exact-fp32 configuration of the same
+workload), and for N > 1 the cost of the gradient exchange.
+
+`--dump-outputs DIR` writes what the last timed step handed its caller as DIR/<name>.npy (float32 / float64, 64 MB at most,
+fixed seeded samples of the large flat buffers): `loss`, `loss_terms` (the per-tensor norms the fused loss summed),
+`predicted_sample` / `predicted_norms` (the flat buffer of predicted parameters: a sample, every tensor's norm in float64)
+and `grad_sample` / `grad_norms` (the flat gradient of all GHN parameters: a sample, every parameter's norm in float64).
+Inference lines (`--config` on a graph fixture) write the two `predicted_*` arrays.  Inputs are seeded: the same arguments
+give the same inputs in every run.
 """
 
 import argparse
@@ -243,6 +257,55 @@ def link_bound_estimate(grad_bytes, world, compute_ms):
             'note': 'arithmetic only: RCCL picks its own channels; `exchange_ms.exposed` is the measurement'}
 
 
+DUMP_SAMPLE = 1 << 22            # --dump-outputs: positions sampled from a large flat buffer (16 MB of float32)
+DUMP_LIMIT = 64 << 20            # bytes of all dumped arrays together
+
+
+def sample_positions(n, seed):
+    """Fixed, seeded, sorted positions into a flat buffer of n elements (all of them when n is small)."""
+    if n <= DUMP_SAMPLE:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.RandomState(seed).randint(0, n, size=DUMP_SAMPLE, dtype=np.int64))
+
+
+def gather_sample(t, seed):
+    """The seeded sample of a flat device buffer, on the host in float32."""
+    idx = torch.from_numpy(sample_positions(t.numel(), seed)).to(t.device)
+    return t.reshape(-1)[idx].float().cpu().numpy()
+
+
+def forward_outputs(prog, out):
+    """A forward's result, the flat buffer of predicted tensors: a seeded sample of it and every tensor's norm (float64)."""
+    norms = torch.stack([out[p['offset']:p['offset'] + p['numel']].double().norm() for p in prog.predicted])
+    return {'predicted_sample': gather_sample(out, 1), 'predicted_norms': norms.cpu().numpy()}
+
+
+def train_step_outputs(ghn, plan):
+    """What the last step of the timed path left its caller: the forward's result, the loss and its per-tensor norms (the
+    plan's scalar buffer: loss at byte 0, norms from byte 256, Program.norm_fin_ops) and the flat gradient of all GHN
+    parameters (a seeded sample, every parameter's norm in float64)."""
+    prog = plan.program
+    d = forward_outputs(prog, plan.out)
+    scal = plan.scal.view(torch.float32)
+    d['loss'] = scal[0:1].double().cpu().numpy()
+    d['loss_terms'] = scal[64:64 + len(prog.predicted)].cpu().numpy()
+    pieces = plan.gflat.split_with_sizes(ghn._split_sizes)        # (parameter, alignment gap) pairs
+    d['grad_norms'] = torch.stack([pieces[k].double().norm() for k in range(0, len(pieces), 2)]).cpu().numpy()
+    d['grad_sample'] = gather_sample(plan.gflat, 2)
+    return d
+
+
+def write_outputs(out_dir, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit('bench.py: %d bytes of outputs exceed the %d-byte limit of --dump-outputs' % (total, DUMP_LIMIT))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(a))
+
+
 CONFIGS = {   # BASELINE.json `configs` 1-4 (config 5 = the headline workload with --graphs-per-gpu 2)
     'resnet18-tm8': dict(model='ghn3tm8', fixture='resnet18', baseline_config=1),
     'tm8-128': dict(model='ghn3tm8', nodes=128, baseline_config=2),
@@ -307,9 +370,9 @@ def bench_fixture(args, cfg):
     """BASELINE configs 1 / 4: INFERENCE forward of a released GHN-3 size on a committed graph fixture (tests/golden/recipe.py:
     the torchvision-shaped ResNet-18 / ResNet-50 / ViT-B/16 graphs the reference-golden parity tests use), one GPU.
     `value` = predicted parameters / time of the forward program with graph, index tables and weights resident (the metric's
-    definition); beside it the end-to-end `ghn(model, graph)` call (host compile + upload + program + assignment into the
-    modules), `Graph(model)` on the host, the HBM roofline of SURVEY 8(d) (M = 196 / 229 / ~450 decoder rows: the decoder
-    weight stream bounds these, not the matrix cores) and the CPU restatement on the same inputs."""
+    definition); beside it the HBM roofline of SURVEY 8(d) (M = 196 / 229 / ~450 decoder rows: the decoder weight stream
+    bounds these, not the matrix cores) and, with --full, the end-to-end `ghn(model, graph)` call (host compile + upload +
+    program + assignment into the modules), `Graph(model)` on the host and the CPU restatement on the same inputs."""
     sys.path.insert(0, os.path.join(ROOT, 'tests', 'golden'))
     import recipe
     torch.set_num_threads(int(os.environ.get('GHN3_HOST_THREADS', '1')))
@@ -349,19 +412,22 @@ def bench_fixture(args, cfg):
         fwd_ms = ea.elapsed_ms(eb) / args.steps
         tags = ctx.profile_read_tags(reset=True)
         ctx.profile(0)
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, forward_outputs(prog, plan.out))
         # end to end, as a user calls it (eval_ghn.py:148 with a pre-built graph): host compile + uploads + program + assign
-        n_e2e = max(3, min(20, args.steps))
-        for _ in range(2):
-            ghn(net, batch(), bn_track_running_stats=True)
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        for _ in range(n_e2e):
-            ghn(net, batch(), bn_track_running_stats=True)
-        torch.cuda.synchronize()
-        e2e_ms = 1e3 * (time.perf_counter() - t1) / n_e2e
+        if args.full:
+            n_e2e = max(3, min(20, args.steps))
+            for _ in range(2):
+                ghn(net, batch(), bn_track_running_stats=True)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            for _ in range(n_e2e):
+                ghn(net, batch(), bn_track_running_stats=True)
+            torch.cuda.synchronize()
+            e2e_ms = 1e3 * (time.perf_counter() - t1) / n_e2e
     # Graph(model) on the host (the step in front of the prediction when no graph is given)
     graph_ms = None
-    if fixture.startswith('resnet'):
+    if args.full and fixture.startswith('resnet'):
         model = TorchvisionShapedResNet(int(fixture[6:]))
         Graph(model)
         tg = time.perf_counter()
@@ -402,12 +468,13 @@ def bench_fixture(args, cfg):
                                                   'equivalents) + 4 B x predicted params + tiles written and read' % w2_b,
                      'algorithmic_gflop': (g_fl + d_fl) / 1e9,
                      'mfma_frac_of_16bit_peak': (g_fl + d_fl) / (fwd_ms * 1e-3) / 1e12 / 2500.0, 'kernels': detail},
-        'end_to_end_ms': {'ghn(model, graph)': e2e_ms, 'Graph(model) host': graph_ms,
-                          'note': 'ghn(model, graph) = host compile of the op program + uploads + the forward program + '
-                                  'assignment of the predicted tensors into the modules (eval: clones into .data), per call'},
         'wall_ms_per_step': 1e3 * wall / args.steps,
     }
-    if not args.no_cpu_baseline:
+    if args.full:
+        out['end_to_end_ms'] = {'ghn(model, graph)': e2e_ms, 'Graph(model) host': graph_ms,
+                                'note': 'ghn(model, graph) = host compile of the op program + uploads + the forward program + '
+                                        'assignment of the predicted tensors into the modules (eval: clones into .data), per call'}
+    if args.full and not args.no_cpu_baseline:
         try:
             from oracle import ghn3_ref as R
             cores = max(1, min(usable_cores(), int(os.environ.get('GHN3_CPU_THREADS', '16'))))
@@ -447,9 +514,15 @@ def main():
     ap.add_argument('--compute', default=os.environ.get('GHN3_COMPUTE', 'f16'), choices=['f32', 'f16', 'bf16'])
     ap.add_argument('--cpu-sample-nodes', type=int, default=0,
                     help='nodes of the CPU-baseline graph (0 = the same graph(s) the GPU ran)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beside the headline figure: roofline (extra instrumented and serialised '
+                         'steps), CPU baseline, forward-only / fresh-graph / training-step / 2- and 4-graph / f32-mode lines '
+                         '(N = 1), gradient-exchange costs (N > 1), end-to-end calls (--config fixtures)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed to DIR/<name>.npy (see the module docstring)')
     ap.add_argument('--no-extras', action='store_true',
-                    help='skip the forward-only / fresh-graph / f32-mode measurements (profiling runs)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+                    help='with --full: skip the forward-only / fresh-graph / f32-mode measurements (profiling runs)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--profile-ops', action='store_true', help='print per-op-kind time of one extra step')
     ap.add_argument('--grad-allreduce', default=os.environ.get('GHN3_GRAD_ALLREDUCE', 'f32'),
                     choices=['f32', 'bf16', 'f32-serial'],
@@ -464,6 +537,8 @@ def main():
                          'reference publishes a number for) or the per-GPU workload of config 2 / 3 (tm8-128, lm8-200: the default '
                          'measurement on that model / graph size)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
     if args.config is not None:
         cfg_ = CONFIGS[args.config]
         if 'fixture' in cfg_:
@@ -485,7 +560,8 @@ def main():
     # whole process throttled).  cpu_baseline() sets its own count.
     torch.set_num_threads(int(os.environ.get('GHN3_HOST_THREADS', '1')))     # (4 threads measured 9.2 vs 7.4 ms per fresh step)
     pool = None
-    if world == 1 and not args.no_extras and not args.force_ddp:
+    extras_on = args.full and world == 1 and not args.no_extras and not args.force_ddp
+    if extras_on:
         import multiprocessing as mp                     # loader workers: started before ANY torch.cuda call of this process
         for var in ('OMP_NUM_THREADS', 'MKL_NUM_THREADS', 'OPENBLAS_NUM_THREADS'):
             os.environ.setdefault(var, '1')              # (inherited by the workers: the host half of the compile is
@@ -599,33 +675,40 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    beat('instrumented passes')
-    n_inst = args.steps
-    if not tags_in_timed:
-        n_inst = max(3, min(10, args.steps))
-        ctx.profile(2)
+    # (read back before anything else runs a step: the --full measurements below overwrite the plan's buffers, and the
+    # training-step line updates the weights)
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, train_step_outputs(ghn, plan))
+    if args.full:
+        beat('instrumented passes')
+        n_inst = args.steps
+        if not tags_in_timed:
+            n_inst = max(3, min(10, args.steps))
+            ctx.profile(2)
+            ctx.profile_read_tags(reset=True)
+            for _ in range(n_inst):
+                step()
+            torch.cuda.synchronize()
+            if world > 1:
+                dist.barrier()
+        tags = ctx.profile_read_tags(reset=True)
+        ctx.profile(0)
+        # The kernels' OWN durations, for `roofline`: a few untimed steps with the side stream serialised into the chain
+        # (profile mode 3: nothing co-runs with a timed kernel, side-stream grid caps dropped).  The timed region above runs the
+        # fastest schedule -- there the W2 weight gradient shares the chip with the Graphormer backward and its in-step duration
+        # (`roofline.kernels_in_step`) says how the two streams interleave, not what the kernel can do.
+        n_ser = max(3, min(10, args.steps))
+        ex_on, exchange['on'] = exchange['on'], False
+        ctx.profile(3)
         ctx.profile_read_tags(reset=True)
-        for _ in range(n_inst):
+        for _ in range(n_ser):
             step()
         torch.cuda.synchronize()
-        if world > 1:
-            dist.barrier()
-    tags = ctx.profile_read_tags(reset=True)
-    ctx.profile(0)
-    # The kernels' OWN durations, for `roofline`: a few untimed steps with the side stream serialised into the chain (profile
-    # mode 3: nothing co-runs with a timed kernel, side-stream grid caps dropped).  The timed region above runs the fastest
-    # schedule -- there the W2 weight gradient shares the chip with the Graphormer backward and its in-step duration
-    # (`roofline.kernels_in_step`) says how the two streams interleave, not what the kernel can do.
-    n_ser = max(3, min(10, args.steps))
-    ex_on, exchange['on'] = exchange['on'], False
-    ctx.profile(3)
-    ctx.profile_read_tags(reset=True)
-    for _ in range(n_ser):
-        step()
-    torch.cuda.synchronize()
-    tags_ser = ctx.profile_read_tags(reset=True)
-    ctx.profile(0)
-    exchange['on'] = ex_on
+        tags_ser = ctx.profile_read_tags(reset=True)
+        ctx.profile(0)
+        exchange['on'] = ex_on
+    else:
+        ctx.profile(0)
     t_all = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     n_all = torch.tensor([float(n_pred)], dtype=torch.float64, device=dev)
     if world > 1:
@@ -635,7 +718,7 @@ def main():
     total_pred = float(n_all.item())
 
     extras = {}
-    if ddp:
+    if ddp and args.full:
         # What the N > 1 line needs to be judged: proof that RCCL spans all ranks (an all-reduce of ones), the EXPOSED cost
         # of the gradient exchange (step with it - the same step without any collective), the exchange alone (serial, not
         # overlapped) and -- for the default fp32 wire -- the bf16-wire variant as an extra figure.
@@ -731,7 +814,7 @@ def main():
             del plan_r
             torch.cuda.empty_cache()
         beat('tail')
-    if world == 1 and not args.no_extras and not args.force_ddp:
+    if extras_on:
         # (a) forward only: the north star's target is stated on the Graphormer + decoder FORWARD
         ev0, ev1 = L.Event(), L.Event()
         n_f = max(5, args.steps)
@@ -971,52 +1054,6 @@ def main():
 
     if rank == 0:
         ms_per_step = 1e3 * elapsed / args.steps
-        # roofline of the dominant kernel family: the decoder W2 GEMM (forward, dgrad, wgrad).  Algorithmic
-        # FLOPs = 2*rows*8C*(o*i) per parameter group (only the W2 rows a group consumes), DESIGN.md 4.
-        dom = [prog.TAG_D3_FWD, prog.TAG_D3_DGRAD, prog.TAG_D3_WGRAD]
-        fl = sum(prog.tag_flops.get(t, 0.0) for t in dom)                   # per step
-        ms = sum(tags_ser.get(t, (0.0, 0))[0] for t in dom) / n_ser          # per step, kernels alone (serialised pass)
-        ms_in_step = sum(tags.get(t, (0.0, 0))[0] for t in dom) / n_inst       # per step, in the step's own schedule (instrumented steps)
-        achieved = fl / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
-        peak = PEAK_TFLOPS[args.compute]
-
-        def per_kernel(tg, n):
-            d = {}
-            for t, (tms, cnt) in sorted(tg.items()):
-                name = prog.TAG_NAMES.get(t, str(t))
-                d[name] = {'ms_per_step': round(tms / n, 4), 'launch_groups_per_step': cnt // n}
-                if t in prog.tag_flops and tms > 0:
-                    d[name]['tflops'] = round(prog.tag_flops[t] / (tms / n * 1e-3) / 1e12, 2)
-            return d
-        detail, detail_in_step = per_kernel(tags_ser, n_ser), per_kernel(tags, n_inst)
-        # whole path: algorithmic FLOPs of forward + backward (3 x the forward's: Graphormer 24 N C^2 + 4 N^2 C per layer,
-        # decoders on consumed rows / positions only) over the step time
-        rows_ = prog.B * prog.N
-        g_fl_ = prog.Lyr * (24.0 * rows_ * prog.C ** 2 + 4.0 * prog.B * prog.N ** 2 * prog.C)
-        d_fl_ = sum(prog.tag_flops.get(t, 0.0) for t in (prog.TAG_D3_FWD, prog.TAG_D2_FWD, prog.TAG_D1_FWD))
-        step_fl = 3.0 * (g_fl_ + d_fl_)
-        # HBM bytes per step of the same kernels from the PMC counters: they cannot be collected inside this process, so
-        # the number comes from the committed rocprofv3 --pmc passes over this exact workload (tools/pmc_profile.sh,
-        # FETCH_SIZE doubled as MI355X_MICROARCH.md prescribes for gfx950, WRITE_SIZE calibrated) -- and only from a file
-        # that was measured on THIS code (`code_hash` = ghn3_amd.build.source_hash() of the kernels + host compiler); null
-        # otherwise.
-        traffic, traffic_src = None, None
-        if (args.model, args.nodes, args.graphs_per_gpu, args.compute) == ('ghn3xlm16', 256, 1, 'f16'):
-            import glob
-            from ghn3_amd.build import source_hash
-            cur = source_hash()
-            for cand in sorted(glob.glob(os.path.join(ROOT, 'profiles', '*_pmc_traffic_xl_f16.json')), reverse=True):
-                try:
-                    with open(cand) as fh:
-                        rec = json.load(fh)
-                    if rec.get('code_hash') == cur:
-                        traffic = float(rec['hbm_bytes_per_step'])
-                        traffic_src = 'profiles/' + os.path.basename(cand)
-                        break
-                except Exception:
-                    continue
-            if traffic is None:
-                traffic_src = 'no PMC pass of the current code (source hash %s) is committed: tools/gpu_round.sh' % cur
         out = {
             'metric': 'predicted-params/sec (GHN fwd+bwd), %s, %d-node graphs' % (args.model, args.nodes),
             'value': total_pred * args.steps / elapsed,
@@ -1040,23 +1077,71 @@ def main():
                        'parallelism': 'dp%d' % world, 'index_mode': ghn.index_mode,
                        'loss': 'fused into the tile kernels' if fused_loss else 'streaming norm passes',
                        'grad_allreduce': (args.grad_allreduce if ddp else None)},
-            'roofline': {'bound': 'mfma', 'achieved': achieved, 'peak': peak, 'unit': 'TFLOP/s',
-                         'frac': achieved / peak, 'traffic': traffic, 'traffic_unit': 'bytes per step',
-                         'traffic_source': traffic_src,
-                         'kernel': 'decoder W2 grouped GEMM (fwd + dgrad + wgrad), %s MFMA operands' % args.compute,
-                         'measured': 'HIP events around each launch in %d extra steps with the side stream serialised into the '
-                                     'chain (nothing co-runs, side-stream grid caps dropped): the kernels\' own durations; '
-                                     '`kernels_in_step` = the same events in %d steps of the timed schedule itself (the weight '
-                                     'gradient shares the chip with the Graphormer backward), run right behind the timed '
-                                     'region, which carries no events' % (n_ser, n_inst),
-                         'algorithmic_gflop_per_step': fl / 1e9, 'kernel_ms_per_step': ms, 'kernels': detail,
-                         'kernel_ms_per_step_in_step': ms_in_step, 'kernels_in_step': detail_in_step,
-                         'frac_in_step': (fl / (ms_in_step * 1e-3) / 1e12 / peak) if ms_in_step > 0 else None,
-                         # the whole path against the same peak: algorithmic forward + backward FLOPs / step time
-                         'frac_step': step_fl / (ms_per_step * 1e-3) / 1e12 / peak,
-                         'algorithmic_gflop_fwd_bwd': step_fl / 1e9,
-                         'wgrad_side_workgroups': int(getattr(prog, 'wgrad_cap', 0))},
         }
+        if args.full:
+            # roofline of the dominant kernel family: the decoder W2 GEMM (forward, dgrad, wgrad).  Algorithmic
+            # FLOPs = 2*rows*8C*(o*i) per parameter group (only the W2 rows a group consumes), DESIGN.md 4.
+            dom = [prog.TAG_D3_FWD, prog.TAG_D3_DGRAD, prog.TAG_D3_WGRAD]
+            fl = sum(prog.tag_flops.get(t, 0.0) for t in dom)                   # per step
+            ms = sum(tags_ser.get(t, (0.0, 0))[0] for t in dom) / n_ser          # per step, kernels alone (serialised pass)
+            # (per step, in the step's own schedule: the instrumented steps)
+            ms_in_step = sum(tags.get(t, (0.0, 0))[0] for t in dom) / n_inst
+            achieved = fl / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
+            peak = PEAK_TFLOPS[args.compute]
+
+            def per_kernel(tg, n):
+                d = {}
+                for t, (tms, cnt) in sorted(tg.items()):
+                    name = prog.TAG_NAMES.get(t, str(t))
+                    d[name] = {'ms_per_step': round(tms / n, 4), 'launch_groups_per_step': cnt // n}
+                    if t in prog.tag_flops and tms > 0:
+                        d[name]['tflops'] = round(prog.tag_flops[t] / (tms / n * 1e-3) / 1e12, 2)
+                return d
+            detail, detail_in_step = per_kernel(tags_ser, n_ser), per_kernel(tags, n_inst)
+            # whole path: algorithmic FLOPs of forward + backward (3 x the forward's: Graphormer 24 N C^2 + 4 N^2 C per layer,
+            # decoders on consumed rows / positions only) over the step time
+            rows_ = prog.B * prog.N
+            g_fl_ = prog.Lyr * (24.0 * rows_ * prog.C ** 2 + 4.0 * prog.B * prog.N ** 2 * prog.C)
+            d_fl_ = sum(prog.tag_flops.get(t, 0.0) for t in (prog.TAG_D3_FWD, prog.TAG_D2_FWD, prog.TAG_D1_FWD))
+            step_fl = 3.0 * (g_fl_ + d_fl_)
+            # HBM bytes per step of the same kernels from the PMC counters: they cannot be collected inside this process, so
+            # the number comes from the committed rocprofv3 --pmc passes over this exact workload (tools/pmc_profile.sh,
+            # FETCH_SIZE doubled as MI355X_MICROARCH.md prescribes for gfx950, WRITE_SIZE calibrated) -- and only from a file
+            # that was measured on THIS code (`code_hash` = ghn3_amd.build.source_hash() of the kernels + host compiler); null
+            # otherwise.
+            traffic, traffic_src = None, None
+            if (args.model, args.nodes, args.graphs_per_gpu, args.compute) == ('ghn3xlm16', 256, 1, 'f16'):
+                import glob
+                from ghn3_amd.build import source_hash
+                cur = source_hash()
+                for cand in sorted(glob.glob(os.path.join(ROOT, 'profiles', '*_pmc_traffic_xl_f16.json')), reverse=True):
+                    try:
+                        with open(cand) as fh:
+                            rec = json.load(fh)
+                        if rec.get('code_hash') == cur:
+                            traffic = float(rec['hbm_bytes_per_step'])
+                            traffic_src = 'profiles/' + os.path.basename(cand)
+                            break
+                    except Exception:
+                        continue
+                if traffic is None:
+                    traffic_src = 'no PMC pass of the current code (source hash %s) is committed: tools/gpu_round.sh' % cur
+            out['roofline'] = {'bound': 'mfma', 'achieved': achieved, 'peak': peak, 'unit': 'TFLOP/s',
+                               'frac': achieved / peak, 'traffic': traffic, 'traffic_unit': 'bytes per step',
+                               'traffic_source': traffic_src,
+                               'kernel': 'decoder W2 grouped GEMM (fwd + dgrad + wgrad), %s MFMA operands' % args.compute,
+                               'measured': 'HIP events around each launch in %d extra steps with the side stream serialised into the '
+                                           'chain (nothing co-runs, side-stream grid caps dropped): the kernels\' own durations; '
+                                           '`kernels_in_step` = the same events in %d steps of the timed schedule itself (the weight '
+                                           'gradient shares the chip with the Graphormer backward), run right behind the timed '
+                                           'region, which carries no events' % (n_ser, n_inst),
+                               'algorithmic_gflop_per_step': fl / 1e9, 'kernel_ms_per_step': ms, 'kernels': detail,
+                               'kernel_ms_per_step_in_step': ms_in_step, 'kernels_in_step': detail_in_step,
+                               'frac_in_step': (fl / (ms_in_step * 1e-3) / 1e12 / peak) if ms_in_step > 0 else None,
+                               # the whole path against the same peak: algorithmic forward + backward FLOPs / step time
+                               'frac_step': step_fl / (ms_per_step * 1e-3) / 1e12 / peak,
+                               'algorithmic_gflop_fwd_bwd': step_fl / 1e9,
+                               'wgrad_side_workgroups': int(getattr(prog, 'wgrad_cap', 0))}
         # the number the north star is written on: Graphormer + decoder FORWARD, algorithmic FLOPs / forward time / 2.5 PF
         # (N = 1 with extras; also for the per-GPU batch of BASELINE config 5, 2 graphs per GPU)
         if 'forward' in extras:
@@ -1068,7 +1153,7 @@ def main():
         if op_breakdown is not None:
             out['op_breakdown_ms'] = {k: round(v[0], 3) for k, v in op_breakdown.items()}
             out['phase_ms'] = phases
-        if not args.no_cpu_baseline and world == 1:      # (rank 0 at N = 1 only: the other ranks would idle)
+        if args.full and not args.no_cpu_baseline and world == 1:    # (rank 0 at N = 1 only: the other ranks would idle)
             try:
                 if args.cpu_sample_nodes:
                     out['cpu_baseline'] = cpu_baseline(args.model, args.cpu_sample_nodes, args.cpu_sample_nodes * 1000)

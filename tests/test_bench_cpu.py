@@ -1,4 +1,5 @@
-"""Host-side pieces of bench.py that the N > 1 line depends on (no GPU): the stall watchdog and the a-priori link arithmetic."""
+"""Host-side pieces of bench.py (no GPU): the stall watchdog and the a-priori link arithmetic of the N > 1 line, the options
+and the output dump."""
 import os
 import subprocess
 import sys
@@ -34,3 +35,35 @@ def test_watchdog_ends_a_stalled_rank_with_code_3():
     r = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, timeout=120)
     assert r.returncode == 3, (r.returncode, r.stderr[-500:])
     assert 'alive' in r.stdout and 'no progress' in r.stderr and 'loop' in r.stderr
+
+
+def test_dump_sample_positions_are_fixed_and_in_range():
+    """--dump-outputs samples large flat buffers at seeded positions: the same in every run, sorted, inside the buffer."""
+    import numpy as np
+    import bench
+    a = bench.sample_positions(10 ** 8, 1)
+    assert np.array_equal(a, bench.sample_positions(10 ** 8, 1))
+    assert len(a) == bench.DUMP_SAMPLE and a.min() >= 0 and a.max() < 10 ** 8 and (np.diff(a) >= 0).all()
+    assert not np.array_equal(a, bench.sample_positions(10 ** 8, 2))
+    assert np.array_equal(bench.sample_positions(1000, 1), np.arange(1000))       # small buffers: every element
+
+
+def test_write_outputs_writes_float_arrays_within_the_limit(tmp_path):
+    import numpy as np
+    import bench
+    bench.write_outputs(str(tmp_path / 'o'), {'a': np.arange(5, dtype=np.float32), 'b': np.ones(3)})
+    assert np.array_equal(np.load(tmp_path / 'o' / 'a.npy'), np.arange(5, dtype=np.float32))
+    assert np.load(tmp_path / 'o' / 'b.npy').dtype == np.float64
+    with pytest.raises(SystemExit):
+        bench.write_outputs(str(tmp_path / 'p'), {'big': np.zeros(bench.DUMP_LIMIT // 8 + 1)})
+    assert not (tmp_path / 'p').exists()
+
+
+def test_bench_options():
+    """--full and --dump-outputs exist; --steps sets the number of timed steps and must be at least one."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--help'], capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 0 and '--full' in r.stdout and '--dump-outputs' in r.stdout
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '0'], capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 2 and '--steps' in r.stderr

@@ -930,6 +930,37 @@ def test_two_rank_rccl_bench_line():
     assert line['n_gpus'] == 2 and line['value'] > 0 and line['config']['parallelism'] == 'dp2'
 
 
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """A plain `python bench.py` run prints the headline line alone (nothing behind --full) and, with --dump-outputs, writes
+    what its last timed step computed: finite float arrays within 64 MB, the loss equal to the sum of the per-tensor norms it
+    was formed from, those norms equal to the predicted tensors' own, and the same values again in a second run."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def run(d):
+        out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '4', '--warmup', '1',
+                              '--model', 'ghn3tm8', '--nodes', '64', '--dump-outputs', str(d)],
+                             stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        return json.loads(out.stdout.strip().splitlines()[-1]), {p.stem: np.load(p) for p in d.glob('*.npy')}
+    line, a = run(tmp_path / 'a')
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert k in line, k
+    assert line['steps'] == 4 and line['warmup'] == 1 and line['ms_per_step'] > 0 and line['value'] > 0
+    assert not {'roofline', 'cpu_baseline', 'forward', 'train_step', 'f32_mode'} & set(line)
+    assert set(a) == {'loss', 'loss_terms', 'predicted_sample', 'predicted_norms', 'grad_sample', 'grad_norms'}
+    assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert abs(float(a['loss'][0]) - float(a['loss_terms'].astype(np.float64).sum())) <= 1e-5 * abs(float(a['loss'][0]))
+    np.testing.assert_allclose(a['loss_terms'], a['predicted_norms'], rtol=1e-4)
+    assert float(np.abs(a['grad_norms']).max()) > 0
+    _, b = run(tmp_path / 'b')
+    for k, v in a.items():
+        np.testing.assert_allclose(b[k], v, rtol=1e-5, atol=1e-6 * float(np.abs(v).max()), err_msg=k)
+
+
 def test_graft_entry_smoke():
     """The driver's smoke(): tiny forward + backward through the public API, checked against the oracle."""
     import __graft_entry__ as g
