@@ -658,3 +658,153 @@ def run_block(layers, x, keep_layout=False):
     out, stats = dwpw_bn(x, w_dw, w_pw, gamma, beta, dw.stride[0], dw.padding[0], dw.dilation[0], bn.eps)
     _update_running_stats(bn, stats, out, has_run)
     return out if (keep_layout or lazy_layout(dw, pw, bn)) else out.contiguous(memory_format=torch.contiguous_format)
+
+
+class _MsaDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ('B', 'H', 'W', 'C', 'heads', 'hidden', 'stride', 'Ho', 'Wo', 'layout')] + \
+        [('eps', ctypes.c_float), ('has_qkv_bias', ctypes.c_int32)]
+
+
+MSA_PARAM_NAMES = ('ln1_w', 'ln1_b', 'w_qkv', 'b_qkv', 'w_o', 'b_o', 'ln2_w', 'ln2_b', 'w1', 'b1', 'w2', 'b2')
+
+
+class _MsaPtrs(ctypes.Structure):
+    """ghn3_msa_params and ghn3_msa_grads (include/ghn3_hip.h): twelve pointers in MSA_PARAM_NAMES order."""
+    _fields_ = [(n, ctypes.c_void_p) for n in MSA_PARAM_NAMES]
+
+
+def _msa_ptrs(tensors):
+    return _MsaPtrs(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def _aligned(t):
+    """t itself when its storage starts on 16 bytes (the kernels read it as float4), else a copy in the same memory format (a
+    weight view of the GHN's flat buffer may start anywhere)."""
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+_MSA_SCRATCH = {}
+
+
+def _msa_scratch_floats(lib, d, backward):
+    key = tuple(getattr(d, f[0]) for f in d._fields_) + (backward,)
+    n = _MSA_SCRATCH.get(key)
+    if n is None:
+        n = int(lib.ghn3_msa_scratch_floats(ctypes.byref(d), backward))
+        if n < 0:
+            raise L.Ghn3Error('ghn3_msa_scratch_floats: %s' % lib.ghn3_last_error().decode())
+        _MSA_SCRATCH[key] = n
+    return n
+
+
+def _no_dropout(m):
+    if _is_kind(m, 'Identity'):
+        return True
+    return _is_kind(m, 'Dropout') and (float(getattr(m, 'p', 1.0)) == 0.0 or not getattr(m, 'training', True))
+
+
+def _msa_modules(layer):
+    """(ln1, to_qkv, to_out linear, ln2, ff1, ff2, the four dropout slots, activation) of a `_TransformerLayer`, or None when the
+    layer is not built the way the `msa` op builds it."""
+    attn, ff = getattr(layer, 'attn', None), getattr(layer, 'ff', None)
+    try:
+        to_out, net = list(attn.to_out), list(ff.net)
+    except (AttributeError, TypeError):
+        return None
+    if len(to_out) != 2 or len(net) != 5:
+        return None
+    return (layer.ln1, attn.to_qkv, to_out[0], layer.ln2, net[0], net[3], (attn.attn_drop, to_out[1], net[2], net[4]), net[1])
+
+
+class MsaLayer(torch.autograd.Function):
+    """The pre-LN transformer layer of the ViT-style target networks -- the `msa` op, ops._TransformerLayer with edge_dim = 0
+    (graphormer.py:144-248) -- as ONE autograd node on ghn3_msa_fwd / _bwd (ghn3_amd/csrc/tnet_msa.hip): x (B, C, H, W) in NCHW or
+    channels_last storage, read as it is; the output (B, C, Ho, Wo) in channels_last storage.  The twelve tensors (MSA_PARAM_NAMES;
+    b_qkv may be None) are read in place; their gradients leave as tensors of their own."""
+
+    @staticmethod
+    def applicable(layer, x):
+        if not (enabled() and os.environ.get('GHN3_NATIVE_MSA', '1') != '0' and torch.is_tensor(x) and x.is_cuda and
+                x.dtype == torch.float32 and x.dim() == 4 and not _autocast_excludes() and x.numel() < 2 ** 31):
+            return False
+        mods = _msa_modules(layer)
+        if mods is None or getattr(layer, 'edge_dim', 0) != 0:
+            return False
+        ln1, qkv, out, ln2, ff1, ff2, drops, act = mods
+        B, C, H, W = x.shape
+        heads = int(getattr(layer.attn, 'num_heads', 0))
+        stride = getattr(layer, 'stride', 1)
+        if not (isinstance(stride, int) and stride >= 1 and heads > 0 and C % heads == 0 and C // heads <= 32 and C % 4 == 0 and
+                C <= 256 and H * W <= 4096):
+            return False
+        if not (all(_no_dropout(m) for m in drops) and _is_kind(act, 'GELU') and getattr(act, 'approximate', 'none') == 'none'):
+            return False
+        if not (tuple(getattr(ln1, 'normalized_shape', ())) == (C,) and tuple(getattr(ln2, 'normalized_shape', ())) == (C,) and
+                getattr(ln1, 'eps', None) == getattr(ln2, 'eps', None)):
+            return False
+        w = [getattr(m, a, None) for m in (ln1, qkv, out, ln2, ff1, ff2) for a in ('weight', 'bias')]
+        if w[3] is None:                                   # (to_qkv without a bias, the search space's default)
+            w = w[:3] + w[4:]
+        if not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in w):
+            return False
+        hidden = int(ff1.weight.shape[0])
+        want = [(ln1.weight, (C,)), (ln1.bias, (C,)), (qkv.weight, (3 * C, C)), (out.weight, (C, C)), (out.bias, (C,)),
+                (ln2.weight, (C,)), (ln2.bias, (C,)), (ff1.weight, (hidden, C)), (ff1.bias, (hidden,)), (ff2.weight, (C, hidden)),
+                (ff2.bias, (C,))] + ([] if qkv.bias is None else [(qkv.bias, (3 * C,))])
+        return all(tuple(t.shape) == s for t, s in want) and hidden % 4 == 0 and hidden <= 1024 and \
+            B * H * W * 3 * C < 2 ** 31 and B * H * W * hidden < 2 ** 31 and B * heads * (H * W) ** 2 < 2 ** 31
+
+    @staticmethod
+    def forward(ctx, x, cfg, *params):
+        heads, stride, eps, train = cfg
+        lib = L.load()
+        layout = 1 if (x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous()) else 0
+        xc = _aligned(x.contiguous(memory_format=torch.channels_last) if layout else x.contiguous())
+        ps = [None if t is None else _aligned(t.contiguous()) for t in params]
+        B, C, H, W = xc.shape
+        Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+        d = _MsaDesc(B, H, W, C, heads, int(ps[8].shape[0]), stride, Ho, Wo, layout, float(eps), int(ps[3] is not None))
+        dev = x.device
+        out = torch.empty((B, C, Ho, Wo), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
+        scratch = torch.empty(_msa_scratch_floats(lib, d, 0), dtype=torch.float32, device=dev)
+        # (P and everything the backward reads only when the layer is differentiated)
+        P = torch.empty(B * heads * H * W * H * W, dtype=torch.float32, device=dev) if train else None
+        L._check(lib.ghn3_msa_fwd(ctypes.byref(d), _ptr(xc), ctypes.byref(_msa_ptrs(ps)), _ptr(out),
+                                  _ptr(P) if P is not None else None, _ptr(scratch), _stream()), 'ghn3_msa_fwd')
+        if train:
+            ctx.save_for_backward(xc, scratch, P, *ps)
+            ctx.desc = d
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = L.load()
+        xc, scratch, P, *ps = ctx.saved_tensors
+        d = ctx.desc
+        do = _aligned(dout.contiguous(memory_format=torch.channels_last))
+        dx = torch.empty_like(xc)
+        grads = [None if t is None else torch.empty_like(t, memory_format=torch.contiguous_format) for t in ps]
+        bscratch = torch.empty(_msa_scratch_floats(lib, d, 1), dtype=torch.float32, device=xc.device)
+        L._check(lib.ghn3_msa_bwd(ctypes.byref(d), _ptr(do), _ptr(xc), ctypes.byref(_msa_ptrs(ps)), _ptr(scratch), _ptr(P),
+                                  _ptr(dx), ctypes.byref(_msa_ptrs(grads)), _ptr(bscratch), _stream()), 'ghn3_msa_bwd')
+        return (dx, None) + tuple(grads)
+
+
+def msa_params(layer):
+    """The twelve tensors of a `_TransformerLayer` in MSA_PARAM_NAMES order (b_qkv None without a QKV bias)."""
+    ln1, qkv, out, ln2, ff1, ff2, _, _ = _msa_modules(layer)
+    return (ln1.weight, ln1.bias, qkv.weight, qkv.bias, out.weight, out.bias, ln2.weight, ln2.bias, ff1.weight, ff1.bias,
+            ff2.weight, ff2.bias)
+
+
+def run_msa_layer(layer, x):
+    """`_TransformerLayer.forward` of a (B, C, H, W) input (tokens, pre-LN attention and feed-forward blocks, stride slicing) on
+    the fused op where it applies; None otherwise (the caller keeps its stock layers).  Under torch.no_grad (or with nothing to
+    differentiate) the op saves nothing for a backward."""
+    if not MsaLayer.applicable(layer, x):
+        return None
+    params = msa_params(layer)
+    train = torch.is_grad_enabled() and (x.requires_grad or any(t is not None and t.requires_grad for t in params))
+    cfg = (int(layer.attn.num_heads), int(layer.stride), float(layer.ln1.eps), bool(train))
+    y = MsaLayer.apply(x, cfg, *params)
+    return y if lazy_layout(layer.ln1, layer.attn.to_qkv) else y.contiguous(memory_format=torch.contiguous_format)

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define GHN3_ABI_VERSION 19
+#define GHN3_ABI_VERSION 20
 
 /* ---- error codes -------------------------------------------------------------------------------- */
 #define GHN3_OK            0
@@ -579,6 +579,37 @@ int ghn3_se_bwd(int N, int HW, int C, int J, const float* dy, const float* x, co
 typedef struct ghn3_pool_desc { int32_t N, H, W, C, k, stride, pad, Ho, Wo, mode; } ghn3_pool_desc;
 int ghn3_pool_fwd(const ghn3_pool_desc* desc, const float* x, float* y, unsigned char* idx, void* stream);
 int ghn3_pool_bwd(const ghn3_pool_desc* desc, const float* dy, const unsigned char* idx, float* dx, void* stream);
+
+
+/* ---- target-network layers, msa (ABI v20): the pre-LN transformer layer of the ViT-style networks ----------------------------
+ * `_TransformerLayer` with edge_dim = 0 (ghn3/graphormer.py:144-248, the `msa` op, ops.py:302), forward and backward:
+ *   t = tokens(x) (B, N = H W, C);  y1 = t + Wo attn(LN1(t) Wqkv^T [+ bqkv]) + bo;  y = y1 + W2 gelu_erf(W1 LN2(y1) + b1) + b2;
+ *   out = y[::stride, ::stride] written as [B][Ho][Wo][C] (NHWC).
+ * x (and dx) [B][C][H][W] when layout == 0, [B][H][W][C] when layout == 1.  Weights in the nn.Linear / nn.LayerNorm layouts
+ * (w_qkv [3C][C], w_o [C][C], w1 [hidden][C], w2 [C][hidden]), read in place; every gradient is written densely in the same
+ * layout.  b_qkv is read (and its gradient written) only when has_qkv_bias != 0.
+ * `scratch` of ghn3_msa_fwd = ghn3_msa_scratch_floats(desc, 0) floats; it holds what the backward reads, so the caller keeps it
+ * until ghn3_msa_bwd, which takes it as `fwd_scratch` next to a scratch of its own (ghn3_msa_scratch_floats(desc, 1) floats).
+ * P [B][heads][N][N]: the attention probabilities, written by the forward for the backward; NULL in inference (the forward then
+ * saves nothing, and a backward is not possible).  x, dout, dx, scratch, P and the four weight matrices 16-byte aligned.
+ * Limits (GHN3_E_LIMIT: the caller keeps its stock path): C % 4 == 0, C <= 256, C % heads == 0, C / heads <= 32, N <= 4096,
+ * hidden % 4 == 0 and <= 1024, element counts < 2^31.  Deterministic: fixed-order partial sums, no float atomics. */
+typedef struct ghn3_msa_desc {
+    int32_t B, H, W, C, heads, hidden, stride, Ho, Wo, layout;
+    float eps;                      /* of both LayerNorms */
+    int32_t has_qkv_bias;
+} ghn3_msa_desc;
+typedef struct ghn3_msa_params {
+    const float *ln1_w, *ln1_b, *w_qkv, *b_qkv, *w_o, *b_o, *ln2_w, *ln2_b, *w1, *b1, *w2, *b2;
+} ghn3_msa_params;
+typedef struct ghn3_msa_grads {
+    float *ln1_w, *ln1_b, *w_qkv, *b_qkv, *w_o, *b_o, *ln2_w, *ln2_b, *w1, *b1, *w2, *b2;
+} ghn3_msa_grads;
+int64_t ghn3_msa_scratch_floats(const ghn3_msa_desc* desc, int backward);      /* host only; < 0: outside the limits (ghn3_last_error) */
+int ghn3_msa_fwd(const ghn3_msa_desc* desc, const float* x, const ghn3_msa_params* params, float* out, float* P, float* scratch,
+                 void* stream);
+int ghn3_msa_bwd(const ghn3_msa_desc* desc, const float* dout, const float* x, const ghn3_msa_params* params,
+                 const float* fwd_scratch, const float* P, float* dx, const ghn3_msa_grads* grads, float* scratch, void* stream);
 
 #ifdef __cplusplus
 }
