@@ -12,7 +12,7 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'lib', 'libghn3_hip.so')
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 # ---- numpy mirrors of the C structs -------------------------------------------------------------
 REF_DT = np.dtype([('buf', '<i4'), ('_pad', '<i4'), ('off', '<i8')])
@@ -72,7 +72,8 @@ EXPORTS = ['ghn3_abi_version', 'ghn3_last_error', 'ghn3_ctx_create', 'ghn3_ctx_d
            'ghn3_event_elapsed_ms', 'ghn3_event_destroy', 'ghn3_profile_enable', 'ghn3_profile_read',
            'ghn3_profile_read_tags', 'ghn3_dwpw_scratch_floats', 'ghn3_dwpw_bn_fwd', 'ghn3_dwpw_bn_bwd',
            'ghn3_conv_scratch_floats', 'ghn3_conv_bn_fwd', 'ghn3_conv_bn_bwd', 'ghn3_se_fwd', 'ghn3_se_bwd', 'ghn3_pool_fwd', 'ghn3_pool_bwd',
-           'ghn3_msa_scratch_floats', 'ghn3_msa_fwd', 'ghn3_msa_bwd']
+           'ghn3_msa_scratch_floats', 'ghn3_msa_fwd', 'ghn3_msa_bwd', 'ghn3_head_scratch_floats', 'ghn3_head_fwd',
+           'ghn3_head_bwd', 'ghn3_xent_fwd', 'ghn3_xent_bwd']
 OPFLAG_TIMED = 0x100
 OPFLAG_SIDE = 0x200
 
@@ -128,6 +129,12 @@ def load():
         lib.ghn3_msa_scratch_floats.restype = ctypes.c_int64
         lib.ghn3_msa_fwd.argtypes = [ctypes.c_void_p] * 7
         lib.ghn3_msa_bwd.argtypes = [ctypes.c_void_p] * 10
+        lib.ghn3_head_scratch_floats.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        lib.ghn3_head_scratch_floats.restype = ctypes.c_int64
+        lib.ghn3_head_fwd.argtypes = [ctypes.c_void_p] * 6
+        lib.ghn3_head_bwd.argtypes = [ctypes.c_void_p] * 9
+        lib.ghn3_xent_fwd.argtypes = [ctypes.c_void_p] * 7
+        lib.ghn3_xent_bwd.argtypes = [ctypes.c_void_p] * 7
         if lib.ghn3_abi_version() != ABI_VERSION:
             raise Ghn3Error('libghn3_hip.so ABI %d != expected %d: rebuild' % (lib.ghn3_abi_version(), ABI_VERSION))
         _lib = lib

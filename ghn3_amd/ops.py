@@ -575,6 +575,10 @@ class _Network:
                 logits_aux = self.auxiliary_head(F.adaptive_avg_pool2d(s1, 8) if small_vit else s1)
         if s1 is None:
             raise ValueError('the network has invalid configuration: the output is None')
+        if torch.is_tensor(s1) and s1.is_cuda:
+            logits = target_ops.run_classifier_head(self.global_pooling if self._glob_avg else None, self.classifier, s1)
+            if logits is not None:                                 # (one fused node: ghn3_amd/csrc/tnet_head.hip)
+                return logits, logits_aux
         out = self.global_pooling(s1) if self._glob_avg else s1
         with torch.autocast(out.device.type, enabled=False):       # the classifier always runs in fp32
             logits = self.classifier(out.float().reshape(out.size(0), -1))

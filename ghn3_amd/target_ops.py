@@ -808,3 +808,268 @@ def run_msa_layer(layer, x):
     cfg = (int(layer.attn.num_heads), int(layer.stride), float(layer.ln1.eps), bool(train))
     y = MsaLayer.apply(x, cfg, *params)
     return y if lazy_layout(layer.ln1, layer.attn.to_qkv) else y.contiguous(memory_format=torch.contiguous_format)
+
+
+# ---- the classifier head and the meta-batch cross-entropy (ghn3_head_* / ghn3_xent_*, ghn3_amd/csrc/tnet_head.hip) ----------
+HEAD_MAX_LINEAR = 4
+HEAD_MAX_B, HEAD_MAX_F, HEAD_MAX_D = 4096, 32768, 4096     # (ghn3_hip.h: the limits of ghn3_head_desc)
+XENT_MAX_B = 4096
+
+
+class _HeadDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ('B', 'C', 'H', 'W', 'layout', 'glob_avg', 'n_lin')] + \
+        [('dims', ctypes.c_int32 * (HEAD_MAX_LINEAR + 1)), ('p', ctypes.c_float * (HEAD_MAX_LINEAR - 1))]
+
+
+class _HeadParams(ctypes.Structure):
+    _fields_ = [('w', ctypes.c_void_p * HEAD_MAX_LINEAR), ('b', ctypes.c_void_p * HEAD_MAX_LINEAR),
+                ('mask', ctypes.c_void_p * (HEAD_MAX_LINEAR - 1))]
+
+
+class _HeadGrads(ctypes.Structure):
+    _fields_ = [('w', ctypes.c_void_p * HEAD_MAX_LINEAR), ('b', ctypes.c_void_p * HEAD_MAX_LINEAR)]
+
+
+class _XentDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ('n_nets', 'B', 'K')] + [('eps', ctypes.c_float)]
+
+
+def _head_desc(B, C, H, W, layout, glob_avg, dims, ps=()):
+    d = _HeadDesc(B, C, H, W, layout, int(glob_avg), len(dims) - 1)
+    for j, v in enumerate(dims[:HEAD_MAX_LINEAR + 1]):        # (more linears than that: refused by the n_lin check)
+        d.dims[j] = int(v)
+    for j, v in enumerate(ps[:HEAD_MAX_LINEAR - 1]):
+        d.p[j] = float(v)
+    return d
+
+
+_HEAD_SCRATCH = {}
+
+
+def _head_scratch_floats(lib, d, backward):
+    key = (d.B, d.C, d.H, d.W, d.layout, d.glob_avg, tuple(d.dims)[:d.n_lin + 1], backward)
+    n = _HEAD_SCRATCH.get(key)
+    if n is None:
+        n = int(lib.ghn3_head_scratch_floats(ctypes.byref(d), backward))
+        if n < 0:
+            raise L.Ghn3Error('ghn3_head_scratch_floats: %s' % lib.ghn3_last_error().decode())
+        _HEAD_SCRATCH[key] = n
+    return n
+
+
+def head_enabled():
+    """GHN3_NATIVE_HEAD=0 (or GHN3_NATIVE_OPS=0) keeps the classifier head and the loss on the stock layers."""
+    return enabled() and os.environ.get('GHN3_NATIVE_HEAD', '1') != '0'
+
+
+def _head_modules(classifier):
+    """(linears, dropouts) of a classifier `Linear (ReLU Dropout Linear)*` (ops.network_plan's head table), or None."""
+    try:
+        mods = list(classifier)
+    except TypeError:
+        return None
+    if len(mods) % 3 != 1:
+        return None
+    lin, drops = [mods[0]], []
+    for j in range(1, len(mods), 3):
+        relu, drop, nxt = mods[j:j + 3]
+        if not (_is_kind(relu, 'ReLU') and _is_kind(drop, 'Dropout')):
+            return None
+        drops.append(drop)
+        lin.append(nxt)
+    if not all(_is_kind(m, 'Linear') for m in lin):
+        return None
+    return lin, drops
+
+
+def _is_global_pool(pool):
+    if pool is None:
+        return False
+    size = getattr(pool, 'output_size', None)
+    return _is_kind(pool, 'AdaptiveAvgPool2d') and (size == 1 or (isinstance(size, (tuple, list)) and tuple(size) == (1, 1)))
+
+
+class ClassifierHead(torch.autograd.Function):
+    """The end of every target network -- AdaptiveAvgPool2d(1) (glob_avg) or the flatten, then the classifier
+    `Linear (ReLU Dropout Linear)*` in fp32 (ops._Network.forward) -- as ONE autograd node on ghn3_head_fwd / _bwd
+    (ghn3_amd/csrc/tnet_head.hip): x (B, C, H, W) in NCHW or channels_last storage, read as it is; logits (B, K) fp32.  The
+    weights and biases are read in place (the kernels make scalar loads: no alignment, no copy); their gradients leave as
+    tensors of their own.  The dropout keep masks are uint8 tensors drawn by torch (one launch each), saved for the
+    backward."""
+
+    @staticmethod
+    def shape_ok(B, C, H, W, glob_avg, dims):
+        """The C limits of ghn3_head_desc (ghn3_head_scratch_floats refuses exactly what this refuses)."""
+        F = C if glob_avg else C * H * W
+        return 1 <= len(dims) - 1 <= HEAD_MAX_LINEAR and dims[0] == F and 0 < B <= HEAD_MAX_B and F <= HEAD_MAX_F and \
+            all(0 < d <= HEAD_MAX_D for d in dims[1:]) and B * C * H * W < 2 ** 31
+
+    @staticmethod
+    def applicable(pool, classifier, x):
+        if not (head_enabled() and torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and
+                not _autocast_excludes()):
+            return False
+        if pool is not None and not _is_global_pool(pool):
+            return False
+        mods = _head_modules(classifier)
+        if mods is None:
+            return False
+        lin, drops = mods
+        if not all(0.0 <= float(getattr(m, 'p', 1.0)) < 1.0 for m in drops):
+            return False
+        B, C, H, W = x.shape
+        dims = [C if pool is not None else C * H * W]
+        for m in lin:
+            w, b = getattr(m, 'weight', None), getattr(m, 'bias', None)
+            if not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in (w, b)):
+                return False
+            if w.dim() != 2 or w.shape[1] != dims[-1] or tuple(b.shape) != (w.shape[0],):
+                return False
+            dims.append(int(w.shape[0]))
+        return ClassifierHead.shape_ok(B, C, H, W, pool is not None, dims)
+
+    @staticmethod
+    def forward(ctx, x, cfg, *tensors):
+        n, glob_avg, ps, train = cfg
+        masks, params = tensors[:n - 1], tensors[n - 1:]
+        lib = L.load()
+        layout = 1 if (x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous()) else 0
+        xc = x.contiguous(memory_format=torch.channels_last) if layout else x.contiguous()
+        ws = [t.contiguous() for t in params]
+        B, C, H, W = xc.shape
+        dims = [C if glob_avg else C * H * W] + [int(w.shape[0]) for w in ws[0::2]]
+        d = _head_desc(B, C, H, W, layout, glob_avg, dims, ps)
+        hp = _HeadParams()
+        for j in range(n):
+            hp.w[j], hp.b[j] = ws[2 * j].data_ptr(), ws[2 * j + 1].data_ptr()
+        for j, m in enumerate(masks):
+            hp.mask[j] = None if m is None else m.data_ptr()
+        logits = torch.empty((B, dims[-1]), dtype=torch.float32, device=x.device)
+        scratch = torch.empty(_head_scratch_floats(lib, d, 0), dtype=torch.float32, device=x.device)
+        L._check(lib.ghn3_head_fwd(ctypes.byref(d), _ptr(xc), ctypes.byref(hp), _ptr(logits), _ptr(scratch), _stream()),
+                 'ghn3_head_fwd')
+        if train:
+            ctx.save_for_backward(xc, scratch, *masks, *ws)
+            ctx.desc, ctx.n = d, n
+        return logits
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        lib = L.load()
+        n, d = ctx.n, ctx.desc
+        xc, scratch, *rest = ctx.saved_tensors
+        masks, ws = rest[:n - 1], rest[n - 1:]
+        do = dlogits.contiguous()
+        dx = torch.empty_like(xc)
+        grads = [torch.empty_like(t, memory_format=torch.contiguous_format) for t in ws]
+        hp, hg = _HeadParams(), _HeadGrads()
+        for j in range(n):
+            hp.w[j], hp.b[j] = ws[2 * j].data_ptr(), ws[2 * j + 1].data_ptr()
+            hg.w[j], hg.b[j] = grads[2 * j].data_ptr(), grads[2 * j + 1].data_ptr()
+        for j, m in enumerate(masks):
+            hp.mask[j] = None if m is None else m.data_ptr()
+        bscratch = torch.empty(_head_scratch_floats(lib, d, 1), dtype=torch.float32, device=xc.device)
+        L._check(lib.ghn3_head_bwd(ctypes.byref(d), _ptr(do), _ptr(xc), ctypes.byref(hp), _ptr(scratch), _ptr(dx),
+                                   ctypes.byref(hg), _ptr(bscratch), _stream()), 'ghn3_head_bwd')
+        return (dx, None) + (None,) * (n - 1) + tuple(grads)
+
+
+def classifier_head(x, weights, biases, masks=(), ps=(), glob_avg=True):
+    """The head on the fused op with explicit tensors: weights[j] (d_j+1, d_j), biases[j]; masks[j] (uint8 (B, d_j+1) or
+    None) the keep mask of the dropout after linear j (rate ps[j])."""
+    if not x.is_cuda:
+        raise L.Ghn3Error('classifier_head runs on an MI355X only (no CPU implementation: use the stock torch layers)')
+    n = len(weights)
+    masks = list(masks) + [None] * (n - 1 - len(masks))
+    ps = [float(p) if m is not None else 0.0 for p, m in zip(list(ps) + [0.0] * (n - 1), masks)]
+    params = [t for wb in zip(weights, biases) for t in wb]
+    train = torch.is_grad_enabled() and any(t.requires_grad for t in [x] + params)
+    return ClassifierHead.apply(x, (n, bool(glob_avg), tuple(ps), bool(train)), *masks, *params)
+
+
+def run_classifier_head(pool, classifier, x):
+    """Global pooling (`pool` = AdaptiveAvgPool2d(1), or None for the flatten of glob_avg = False) + `classifier` on the fused
+    op where it applies; None otherwise (the caller keeps its stock layers).  A Dropout in training mode with p > 0 draws its
+    keep mask with torch's generator on the current stream, as F.dropout would there.  Under torch.no_grad the op saves nothing for a backward."""
+    if not ClassifierHead.applicable(pool, classifier, x):
+        return None
+    lin, drops = _head_modules(classifier)
+    B = x.shape[0]
+    masks, ps = [], []
+    for drop, nxt in zip(drops, lin[1:]):
+        p = float(drop.p)
+        if getattr(drop, 'training', True) and p > 0:
+            # (torch's own dropout kernel on an uninitialised tensor of the activation's shape: one launch, and the draws the
+            # stock F.dropout makes in the same place, so both paths drop the same units)
+            keep = torch.native_dropout(torch.empty((B, nxt.weight.shape[1]), device=x.device), p, True)[1]
+            masks.append(keep.view(torch.uint8))
+            ps.append(p)
+        else:
+            masks.append(None)
+            ps.append(0.0)
+    return classifier_head(x, [m.weight for m in lin], [m.bias for m in lin], masks, ps, glob_avg=pool is not None)
+
+
+class MetaCrossEntropy(torch.autograd.Function):
+    """F.cross_entropy(logits_n, targets, label_smoothing) for every network of a meta-batch at once (ghn3_xent_fwd / _bwd):
+    ce [n] with autograd, and the top-1 / top-5 hit counts (int32 [2], not differentiable).  A hit is "fewer than k logits
+    strictly greater than the target's", topk's rule except on exact ties.  A target outside [0, K) gives a NaN ce[n]."""
+
+    @staticmethod
+    def forward(ctx, targets, eps, *logits):
+        lib = L.load()
+        n, (B, K) = len(logits), logits[0].shape
+        dev = logits[0].device
+        d = _XentDesc(n, B, K, float(eps))
+        ce = torch.empty(n, dtype=torch.float32, device=dev)
+        lse = torch.empty(n * B, dtype=torch.float32, device=dev)
+        hits = torch.zeros(2, dtype=torch.int32, device=dev)
+        ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in logits])
+        L._check(lib.ghn3_xent_fwd(ctypes.byref(d), ptrs, _ptr(targets), _ptr(ce), _ptr(lse), _ptr(hits), _stream()),
+                 'ghn3_xent_fwd')
+        ctx.mark_non_differentiable(hits)
+        ctx.save_for_backward(targets, lse, *logits)
+        ctx.desc = d
+        return ce, hits
+
+    @staticmethod
+    def backward(ctx, dce, _dhits):
+        lib = L.load()
+        targets, lse, *logits = ctx.saved_tensors
+        n = len(logits)
+        g = dce.contiguous()
+        dl = [torch.empty_like(t) for t in logits]
+        ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in logits])
+        dptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in dl])
+        L._check(lib.ghn3_xent_bwd(ctypes.byref(ctx.desc), ptrs, _ptr(targets), _ptr(lse), _ptr(g), dptrs, _stream()),
+                 'ghn3_xent_bwd')
+        return (None, None) + tuple(dl)
+
+
+def _xent_native(logits, targets):
+    if not (head_enabled() and not _autocast_excludes() and len(logits) > 0 and torch.is_tensor(targets) and
+            targets.is_cuda and targets.dtype == torch.int64 and targets.dim() == 1 and targets.is_contiguous()):
+        return False
+    shape, dev = logits[0].shape, logits[0].device
+    if len(shape) != 2 or shape[0] != targets.shape[0] or targets.device != dev or not 0 < shape[0] <= XENT_MAX_B or \
+            shape[1] < 1 or shape[0] * shape[1] >= 2 ** 31:
+        return False
+    return all(torch.is_tensor(y) and y.is_cuda and y.device == dev and y.dtype == torch.float32 and y.shape == shape and
+               y.is_contiguous() for y in logits)
+
+
+def meta_cross_entropy(logits, targets, label_smoothing=0.0):
+    """(ce [n], hits [2]) for the logits of n networks on one batch: ce[n] = F.cross_entropy(logits[n], targets,
+    label_smoothing) with autograd; hits = the top-1 / top-5 hit counts over all (network, sample) pairs, on the device, not
+    differentiable.  One native launch per 32 networks (MetaCrossEntropy) when every logits tensor is an fp32 contiguous CUDA
+    tensor of one shape; else the stock per-network F.cross_entropy and topk."""
+    logits = list(logits)
+    if _xent_native(logits, targets):
+        return MetaCrossEntropy.apply(targets, float(label_smoothing), *logits)
+    ce = torch.stack([F.cross_entropy(y.float(), targets, label_smoothing=label_smoothing) for y in logits])
+    with torch.no_grad():
+        lg = torch.stack([y.detach().float() for y in logits])          # models x batch x classes
+        top = lg.topk(min(5, lg.shape[-1]), dim=-1).indices
+        hit = top == targets.view(1, -1, 1)
+        hits = torch.stack([hit[..., :1].any(-1).sum(), hit.any(-1).sum()])
+    return ce, hits

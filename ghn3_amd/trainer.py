@@ -34,9 +34,9 @@ import math
 import os
 
 import torch
-import torch.nn.functional as F
 
 from .ddp_utils import is_ddp, get_ddp_rank, sync_parameters, FlatGradReducer
+from . import target_ops
 from .optim import FusedAdamW, save_checkpoint
 from .utils import log, Logger
 
@@ -192,24 +192,21 @@ class Trainer:
         if images is not None:
             images = images.to(dev, non_blocking=True)
             targets = targets.to(dev, non_blocking=True)
-            logits = []
+            logits, logits_aux = [], []
             with torch.autocast('cuda', dtype=torch.float16, enabled=self.amp):
                 for m in models:
                     out = m(images)
-                    y = out[0] if isinstance(out, tuple) else out
-                    loss = loss + F.cross_entropy(y.float(), targets, label_smoothing=self.label_smoothing)
+                    logits.append(out[0] if isinstance(out, tuple) else out)
                     if self.auxiliary and isinstance(out, tuple):
-                        loss = loss + self.auxiliary_weight * F.cross_entropy(out[1].float(), targets,
-                                                                              label_smoothing=self.label_smoothing)
-                    logits.append(y.detach().float())
+                        logits_aux.append(out[1])
+            # every network's loss and the top-1 / top-5 hits in one native call (target_ops.meta_cross_entropy)
+            ce, hits = target_ops.meta_cross_entropy(logits, targets, self.label_smoothing)
+            loss = ce.sum()
+            if logits_aux:
+                loss = loss + self.auxiliary_weight * target_ops.meta_cross_entropy(logits_aux, targets, self.label_smoothing)[0].sum()
             loss = loss / len(models)
             with torch.no_grad():
-                lg = torch.stack(logits)                                  # models x batch x classes
-                k = min(5, lg.shape[-1])
-                top = lg.topk(k, dim=-1).indices
-                hit = top == targets.view(1, -1, 1)
-                stats[1] = 100.0 * hit[..., :1].any(-1).float().mean()
-                stats[2] = 100.0 * hit.any(-1).float().mean()
+                stats[1:3] = hits * (100.0 / (len(models) * targets.numel()))
         if self.predparam_wd > 0:
             wd = self.predparam_wd * ghn.predicted_param_norm() / len(models)
             loss = loss + wd

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define GHN3_ABI_VERSION 20
+#define GHN3_ABI_VERSION 21
 
 /* ---- error codes -------------------------------------------------------------------------------- */
 #define GHN3_OK            0
@@ -610,6 +610,54 @@ int ghn3_msa_fwd(const ghn3_msa_desc* desc, const float* x, const ghn3_msa_param
                  void* stream);
 int ghn3_msa_bwd(const ghn3_msa_desc* desc, const float* dout, const float* x, const ghn3_msa_params* params,
                  const float* fwd_scratch, const float* P, float* dx, const ghn3_msa_grads* grads, float* scratch, void* stream);
+
+/* ---- target-network end (ABI v21): the classifier head and the meta-batch cross-entropy ------------------------------------
+ * The head of every network (ghn3/ops.py:565-569; global pooling + `classifier`, built at ops.py:489-494), forward and backward:
+ *   f = mean_{h,w} x (glob_avg = 1) or x flattened in logical NCHW order, feature c H W + h W + w (glob_avg = 0);
+ *   h_1 = f W_1^T + b_1;  h_j = (relu(h_j-1) m_j-1 / (1 - p[j-2])) W_j^T + b_j, j = 2 .. n_lin;  logits = h_n_lin [B][K].
+ * x (and dx) [B][C][H][W] when layout == 0, [B][H][W][C] when layout == 1.  dims[0] = the feature size (C or C H W), dims[j] =
+ * out features of linear j.  Weights [dims[j]][dims[j-1]] and biases (both required), read in place, no alignment needed;
+ * gradients written densely in the same layout.  mask[j] (uint8 [B][dims[j+1]], 0 = dropped) is the keep mask of the dropout
+ * after linear j + 1, scaled by 1 / (1 - p[j]); NULL: no dropout there.  `scratch` of ghn3_head_fwd =
+ * ghn3_head_scratch_floats(desc, 0) floats holds what the backward reads (the caller keeps it until ghn3_head_bwd, which takes it
+ * as `fwd_scratch` next to ghn3_head_scratch_floats(desc, 1) floats of its own; either may be 0 floats).
+ * Launches: forward n_lin + 1 (n_lin for a flattened NCHW x), backward n_lin + 1 (+ 1 when B > 256).
+ * Limits (GHN3_E_LIMIT: the caller keeps its stock path): 1 <= n_lin <= GHN3_HEAD_MAX_LINEAR, B <= 4096, dims[0] <= 32768,
+ * dims[1..] <= 4096, B C H W < 2^31.  Deterministic: fixed-order sums, no float atomics.
+ *
+ * ghn3_xent_fwd: for each of n_nets logits tensors ([B][K] fp32 contiguous; a host array of n_nets device pointers, passed to
+ * the kernels by value, GHN3_XENT_MAX_NETS per launch) ce[n] = F.cross_entropy(logits_n, targets, label_smoothing = eps)
+ * (batch mean), lse[n][B] the row log-sum-exps (for the backward), and hits[0] / hits[1] += the number of (network, sample)
+ * pairs with fewer than 1 / 5 logits strictly greater than the target's (topk's rule except on exact ties; the caller zeroes
+ * hits).  targets int64 [B]; one outside [0, K) makes ce[n] NaN (and its dlogits rows NaN), nothing is read out of bounds.
+ * ghn3_xent_bwd: dlogits_n = dce[n] / B (softmax(logits_n) - (1 - eps) onehot - eps / K), dce read on the device.
+ * Limits: B <= 4096, B K < 2^31. */
+#define GHN3_HEAD_MAX_LINEAR 4
+#define GHN3_XENT_MAX_NETS 32
+typedef struct ghn3_head_desc {
+    int32_t B, C, H, W, layout, glob_avg, n_lin;
+    int32_t dims[GHN3_HEAD_MAX_LINEAR + 1];
+    float p[GHN3_HEAD_MAX_LINEAR - 1];      /* dropout rate of mask[j] */
+} ghn3_head_desc;
+typedef struct ghn3_head_params {
+    const float* w[GHN3_HEAD_MAX_LINEAR];
+    const float* b[GHN3_HEAD_MAX_LINEAR];
+    const unsigned char* mask[GHN3_HEAD_MAX_LINEAR - 1];
+} ghn3_head_params;
+typedef struct ghn3_head_grads {
+    float* w[GHN3_HEAD_MAX_LINEAR];
+    float* b[GHN3_HEAD_MAX_LINEAR];
+} ghn3_head_grads;
+int64_t ghn3_head_scratch_floats(const ghn3_head_desc* desc, int backward);    /* host only; < 0: outside the limits (ghn3_last_error) */
+int ghn3_head_fwd(const ghn3_head_desc* desc, const float* x, const ghn3_head_params* params, float* logits, float* scratch,
+                  void* stream);
+int ghn3_head_bwd(const ghn3_head_desc* desc, const float* dlogits, const float* x, const ghn3_head_params* params,
+                  const float* fwd_scratch, float* dx, const ghn3_head_grads* grads, float* scratch, void* stream);
+typedef struct ghn3_xent_desc { int32_t n_nets, B, K; float eps; } ghn3_xent_desc;
+int ghn3_xent_fwd(const ghn3_xent_desc* desc, const float* const* logits, const int64_t* targets, float* ce, float* lse,
+                  int32_t* hits, void* stream);
+int ghn3_xent_bwd(const ghn3_xent_desc* desc, const float* const* logits, const int64_t* targets, const float* lse,
+                  const float* dce, float* const* dlogits, void* stream);
 
 #ifdef __cplusplus
 }

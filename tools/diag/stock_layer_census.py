@@ -1,6 +1,6 @@
 """Diagnostic: which layers of the training loop's target networks still run on stock ATen / MIOpen kernels?
 Runs Trainer.update on the architecture stream of examples/train_ghn_ddp.py and counts, per step, the stock Conv2d / BatchNorm2d /
-Linear / pooling calls by configuration and by the module class that issued them."""
+Linear / pooling calls and F.cross_entropy calls by configuration and by the module class that issued them."""
 import collections
 import inspect
 import os
@@ -47,6 +47,15 @@ wrap(light_ops.Linear, lambda m, x: 'w%s x%s' % (tuple(m.weight.shape), tuple(x.
 wrap(light_ops.AvgPool2d, lambda m, x: '')
 wrap(light_ops.MaxPool2d, lambda m, x: '')
 wrap(light_ops.AdaptiveAvgPool2d, lambda m, x: '')
+_cross_entropy = torch.nn.functional.cross_entropy
+
+
+def counted_cross_entropy(*args, **kwargs):
+    counts[('cross_entropy', 'F', '')] += 1
+    return _cross_entropy(*args, **kwargs)
+
+
+torch.nn.functional.cross_entropy = counted_cross_entropy
 
 hid, layers, heads = 64, 3, 8
 config = {'max_shape': (hid, hid, 11, 11), 'num_classes': 10, 'weight_norm': True, 've': True, 'layernorm': True, 'hid': hid,
@@ -66,6 +75,8 @@ torch.cuda.synchronize()
 by_kind = collections.Counter()
 for (kind, who, cfg), n in counts.items():
     by_kind[(kind, who)] += n
+print('stock calls per step: Linear %.1f, AdaptiveAvgPool2d %.1f, F.cross_entropy %.1f' % tuple(
+    sum(n for (k, _), n in by_kind.items() if k == kind) / STEPS for kind in ('Linear', 'AdaptiveAvgPool2d', 'cross_entropy')))
 print('stock layer calls per step, by (layer, issuing class):')
 for (kind, who), n in by_kind.most_common():
     t = sum(v for (k2, w2, _), v in host.items() if (k2, w2) == (kind, who))
