@@ -13,7 +13,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, 'csrc')
 OUT_DIR = os.path.join(HERE, 'lib')
 LIB = os.path.join(OUT_DIR, 'libghn3_hip.so')
-SOURCES = ['gemm.hip', 'gemm_p8.hip', 'gemm_small.hip', 'gemm_x3.hip', 'gemm_x3d.hip', 'gemm_wg.hip', 'attention.hip', 'elementwise.hip', 'target_ops.hip', 'tnet_msa.hip', 'tnet_head.hip', 'runtime.hip']
+SOURCES = ['gemm.hip', 'gemm_p8.hip', 'gemm_small.hip', 'gemm_x3.hip', 'gemm_x3d.hip', 'gemm_wg.hip', 'attention.hip', 'elementwise.hip', 'target_ops.hip', 'tnet_msa.hip', 'tnet_head.hip', 'tnet_wgrad.hip', 'runtime.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-I' + os.path.join(ROOT, 'include'),
          '-I' + CSRC, '-Wno-unused-result'] + os.environ.get('GHN3_HIPCC_EXTRA', '').split()
 
@@ -49,7 +49,8 @@ def source_hash():
 def build(force=False, verbose=True):
     os.makedirs(OUT_DIR, exist_ok=True)
     hipcc = _hipcc()
-    headers = [os.path.join(ROOT, 'include', 'ghn3_hip.h'), os.path.join(CSRC, 'ghn3_internal.h')]
+    headers = [os.path.join(ROOT, 'include', 'ghn3_hip.h'), os.path.join(CSRC, 'ghn3_internal.h'),
+               os.path.join(CSRC, 'tnet_common.h')]
     objs, jobs = [], []
     for src in SOURCES:
         s = os.path.join(CSRC, src)

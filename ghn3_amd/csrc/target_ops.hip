@@ -29,9 +29,8 @@
 // the preprocessing layer of every cell and the `conv_1x1` op (ops.py:180-198): the depthwise stage degenerates to the ReLU.
 
 #include <algorithm>
-#include "ghn3_internal.h"
+#include "tnet_common.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
 
@@ -916,23 +915,6 @@ int check_desc(const ghn3_dwpw_desc* g, Desc& d) {
     return GHN3_OK;
 }
 
-template <typename K> int set_lds(K kern, size_t bytes) {
-    // (once per kernel and process; keyed by the function's address -- every instantiation has the same pointer TYPE)
-    static const void* done[32];
-    static int n_done = 0;
-    const void* key = (const void*)kern;
-    bool seen = false;
-    for (int i = 0; i < n_done; ++i) seen |= done[i] == key;
-    if (bytes > 48 * 1024 && !seen) {
-        if (n_done < 32) done[n_done++] = key;
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) { ghn3_set_error("hipFuncSetAttribute(dwpw): %s", hipGetErrorString(e)); return GHN3_E_HIP; }
-    }
-    return GHN3_OK;
-}
-
-#define LAUNCH_CHECK(what) { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) { ghn3_set_error(what ": %s", hipGetErrorString(e_)); return GHN3_E_HIP; } }
-
 }  // namespace
 
 extern "C" int64_t ghn3_dwpw_scratch_floats(const ghn3_dwpw_desc* g, int backward) {
@@ -956,17 +938,17 @@ extern "C" int ghn3_dwpw_bn_fwd(const ghn3_dwpw_desc* g, const float* x, const f
     const Plan pl = make_plan(d);
     const int NT = nt_of(d.C_out);
     const size_t lds = fwd_lds(NT);
-#define FWD_CASE(n, t) case 10 * n + t: rc = set_lds(tnet_dwpw_fwd_kernel<n, t>, lds); if (rc) return rc; \
+#define FWD_CASE(n, t) case 10 * n + t: rc = tnet_raise_lds(tnet_dwpw_fwd_kernel<n, t>, lds); if (rc) return rc; \
         hipLaunchKernelGGL((tnet_dwpw_fwd_kernel<n, t>), dim3(pl.n_tiles), dim3(256), lds, s, x, w_dw, w_pw, z, scratch, d, pl.P); break;
     switch (10 * NT + terms_of(NT)) { FWD_CASE(4, 3) FWD_CASE(8, 3) FWD_CASE(16, 3) FWD_CASE(4, 2) FWD_CASE(8, 2) FWD_CASE(16, 2) FWD_CASE(32, 2) }
 #undef FWD_CASE
-    LAUNCH_CHECK("dwpw fwd")
+    TNET_LAUNCH_CHECK("dwpw fwd")
     hipLaunchKernelGGL(tnet_bn_finalize_kernel, dim3((d.C_out + 15) / 16), dim3(256), 0, s, scratch, pl.n_tiles, pl.P, d.C_out, d.eps, stats);
-    LAUNCH_CHECK("bn finalize")
+    TNET_LAUNCH_CHECK("bn finalize")
     const int64_t total4 = (int64_t)pl.P * d.C_out / 4;
     hipLaunchKernelGGL(tnet_bn_apply_kernel, dim3((int)std::min<int64_t>((total4 + 255) / 256, 4096)), dim3(256), 0, s, z, stats, gamma,
                        beta, out, total4, d.C_out);
-    LAUNCH_CHECK("bn apply")
+    TNET_LAUNCH_CHECK("bn apply")
     return GHN3_OK;
 }
 
@@ -997,10 +979,10 @@ extern "C" int ghn3_dwpw_bn_bwd(const ghn3_dwpw_desc* g, const float* dout, cons
         const int nq = d.C_out / 4, ng = std::max(1, 256 / nq);
         hipLaunchKernelGGL(tnet_bn_bwd_partial_kernel, dim3(pl.n_tiles), dim3(256), (size_t)ng * 2 * d.C_out * 4, s, dout, z, stats, part12,
                            pl.P, d.C_out);
-        LAUNCH_CHECK("bn bwd partial")
+        TNET_LAUNCH_CHECK("bn bwd partial")
         hipLaunchKernelGGL(tnet_reduce_rows_kernel, dim3((2 * d.C_out / 4 + 15) / 16), dim3(256), 0, s, part12, pl.n_tiles,
                            (int64_t)2 * d.C_out, s12, 0, 0);
-        LAUNCH_CHECK("bn bwd reduce")
+        TNET_LAUNCH_CHECK("bn bwd reduce")
         if (!s12_in_place) {
             hipMemcpyAsync(dbeta, s12, (size_t)d.C_out * 4, hipMemcpyDeviceToDevice, s);
             hipMemcpyAsync(dgamma, s12 + d.C_out, (size_t)d.C_out * 4, hipMemcpyDeviceToDevice, s);
@@ -1010,36 +992,36 @@ extern "C" int ghn3_dwpw_bn_bwd(const ghn3_dwpw_desc* g, const float* dout, cons
     {
         const int NT = nt_of(d.C_in);
         const size_t lds = bwd_lds(NT);
-#define BWD_CASE(n, t) case 10 * n + t: rc = set_lds(tnet_dwpw_bwd_data_kernel<n, t>, lds); if (rc) return rc; \
+#define BWD_CASE(n, t) case 10 * n + t: rc = tnet_raise_lds(tnet_dwpw_bwd_data_kernel<n, t>, lds); if (rc) return rc; \
         hipLaunchKernelGGL((tnet_dwpw_bwd_data_kernel<n, t>), dim3(pl.n_tiles), dim3(256), lds, s, dout, z, stats, gamma, s12, w_pw, dy, d, pl.P); break;
         switch (10 * NT + terms_of(NT)) { BWD_CASE(4, 3) BWD_CASE(8, 3) BWD_CASE(16, 3) BWD_CASE(4, 2) BWD_CASE(8, 2) BWD_CASE(16, 2) BWD_CASE(32, 2) }
 #undef BWD_CASE
-        LAUNCH_CHECK("dwpw bwd data")
+        TNET_LAUNCH_CHECK("dwpw bwd data")
     }
     // 3. dW_pw
     hipLaunchKernelGGL(tnet_pw_wgrad_kernel, dim3(pl.pw_chunks, (d.C_out + 63) / 64, (d.C_in + 63) / 64), dim3(256), 0, s, dout, z, stats,
                        gamma, s12, x, w_dw, part_pw, d, pl.P, pl.pw_chunk_px);
-    LAUNCH_CHECK("pw wgrad")
+    TNET_LAUNCH_CHECK("pw wgrad")
     {
         const int64_t cols = (int64_t)d.C_out * d.C_in;
         hipLaunchKernelGGL(tnet_reduce_rows_kernel, dim3((int)((cols / 4 + 15) / 16)), dim3(256), 0, s, part_pw, pl.pw_chunks, cols, dw_pw, 0, 0);
-        LAUNCH_CHECK("pw wgrad reduce")
+        TNET_LAUNCH_CHECK("pw wgrad reduce")
     }
     // 4. dx and dW_dw
     {
         const int64_t total4 = (int64_t)d.N * d.H * d.W * d.C_in / 4;
         hipLaunchKernelGGL(tnet_dw_bwd_data_kernel, dim3((int)std::min<int64_t>((total4 + 255) / 256, 8192)), dim3(256), 0, s, dy, x, w_dw,
                            dx, d, total4);
-        LAUNCH_CHECK("dw bwd data")
+        TNET_LAUNCH_CHECK("dw bwd data")
         if (w_dw) {
             const int nq = d.C_in / 4;
             hipLaunchKernelGGL(tnet_dw_wgrad_kernel, dim3(pl.dw_chunks), dim3(256), (size_t)std::max(1, 256 / nq) * 16 * nq * 16, s, dy, x,
                                part_dw, d, pl.P, pl.dw_chunk_px);
-            LAUNCH_CHECK("dw wgrad")
+            TNET_LAUNCH_CHECK("dw wgrad")
             const int64_t cols = (int64_t)taps * d.C_in;
             hipLaunchKernelGGL(tnet_reduce_rows_kernel, dim3((int)((cols / 4 + 15) / 16)), dim3(256), 0, s, part_dw, pl.dw_chunks, cols,
                                dw_dw, d.C_in, taps);
-            LAUNCH_CHECK("dw wgrad reduce")
+            TNET_LAUNCH_CHECK("dw wgrad reduce")
         }
     }
     return GHN3_OK;
@@ -1328,7 +1310,7 @@ int conv_repack(const CDesc& d, const CPlan& pl, const float* w, float* w_r, hip
     const int64_t total = (int64_t)d.C_out * d.C_in * pl.taps;
     hipLaunchKernelGGL(tnet_conv_w_repack_kernel, dim3((int)std::min<int64_t>((total + 255) / 256, 2048)), dim3(256), 0, s, w, w_r, d.C_out,
                        d.C_in, pl.taps);
-    LAUNCH_CHECK("conv weight repack")
+    TNET_LAUNCH_CHECK("conv weight repack")
     return GHN3_OK;
 }
 
@@ -1378,33 +1360,33 @@ extern "C" int ghn3_conv_bn_fwd(const ghn3_conv_desc* g, const float* x, const f
         const int64_t plane = (int64_t)pl.taps * d.C_out * ((d.C_in + KC - 1) / KC * KC);
         hipLaunchKernelGGL(tnet_conv_w_pack_kernel, dim3((int)std::min<int64_t>((plane + 255) / 256, 2048)), dim3(256), 0, s, w, wp, d.C_out,
                            d.C_in, pl.taps, 0);
-        LAUNCH_CHECK("conv weight pack")
+        TNET_LAUNCH_CHECK("conv weight pack")
         const int NT = conv2_nt(pl.n_tiles, d.C_out);
         const dim3 grid(pl.n_tiles, (d.C_out + 16 * NT - 1) / (16 * NT));
         const size_t lds = conv2_lds(NT);
-#define C2F_CASE(n) case n: rc = set_lds(tnet_conv2_kernel<n, false>, lds); if (rc) return rc; \
+#define C2F_CASE(n) case n: rc = tnet_raise_lds(tnet_conv2_kernel<n, false>, lds); if (rc) return rc; \
         hipLaunchKernelGGL((tnet_conv2_kernel<n, false>), grid, dim3(256), lds, s, x, wp, z, part, (const float*)nullptr, d, pl.P, pl.P_in); break;
         switch (NT) { C2F_CASE(2) C2F_CASE(4) C2F_CASE(8) }
 #undef C2F_CASE
-        LAUNCH_CHECK("conv fwd")
+        TNET_LAUNCH_CHECK("conv fwd")
     } else {
     rc = conv_repack(d, pl, w, w_r, s);
     if (rc) return rc;
     const int NT = nt_of(d.C_out);
     const size_t lds = cfwd_lds(NT);
-#define CFWD_CASE(n, t) case 10 * n + t: rc = set_lds(tnet_conv_fwd_kernel<n, t>, lds); if (rc) return rc; \
+#define CFWD_CASE(n, t) case 10 * n + t: rc = tnet_raise_lds(tnet_conv_fwd_kernel<n, t>, lds); if (rc) return rc; \
         hipLaunchKernelGGL((tnet_conv_fwd_kernel<n, t>), dim3(pl.n_tiles), dim3(256), lds, s, x, w_r, z, part, d, pl.P); break;
     switch (10 * NT + terms_of(NT)) { CFWD_CASE(4, 3) CFWD_CASE(8, 3) CFWD_CASE(16, 3) CFWD_CASE(4, 2) CFWD_CASE(8, 2) CFWD_CASE(16, 2) CFWD_CASE(32, 2) }
 #undef CFWD_CASE
-    LAUNCH_CHECK("conv fwd")
+    TNET_LAUNCH_CHECK("conv fwd")
     }
     if (no_norm) return GHN3_OK;
     hipLaunchKernelGGL(tnet_bn_finalize_kernel, dim3((d.C_out + 15) / 16), dim3(256), 0, s, part, pl.n_tiles, pl.P, d.C_out, d.eps, stats);
-    LAUNCH_CHECK("bn finalize")
+    TNET_LAUNCH_CHECK("bn finalize")
     const int64_t total4 = (int64_t)pl.P * d.C_out / 4;
     hipLaunchKernelGGL(tnet_bn_apply_kernel, dim3((int)std::min<int64_t>((total4 + 255) / 256, 4096)), dim3(256), 0, s, z, stats, gamma,
                        beta, out, total4, d.C_out);
-    LAUNCH_CHECK("bn apply")
+    TNET_LAUNCH_CHECK("bn apply")
     return GHN3_OK;
 }
 
@@ -1436,7 +1418,7 @@ extern "C" int ghn3_conv_bn_bwd(const ghn3_conv_desc* g, const float* dout, cons
         // (dout is dz: nothing to prepare)
     } else if (no_norm) {
         hipLaunchKernelGGL(tnet_identity_norm_kernel, dim3(1), dim3(256), 0, s, ident, d.C_out);
-        LAUNCH_CHECK("conv bwd identity")
+        TNET_LAUNCH_CHECK("conv bwd identity")
         if (hipMemsetAsync(s12, 0, (size_t)2 * d.C_out * 4, s) != hipSuccess) { ghn3_set_error("conv bwd: memset failed"); return GHN3_E_HIP; }
         z = dout;                                                  // (read, multiplied by the zero sums)
         stats = ident;
@@ -1447,10 +1429,10 @@ extern "C" int ghn3_conv_bn_bwd(const ghn3_conv_desc* g, const float* dout, cons
         const int nq = d.C_out / 4, ng = std::max(1, 256 / nq);
         hipLaunchKernelGGL(tnet_bn_bwd_partial_kernel, dim3(pl.n_tiles), dim3(256), (size_t)ng * 2 * d.C_out * 4, s, dout, z, stats, part12,
                            pl.P, d.C_out);
-        LAUNCH_CHECK("bn bwd partial")
+        TNET_LAUNCH_CHECK("bn bwd partial")
         hipLaunchKernelGGL(tnet_reduce_rows_kernel, dim3((2 * d.C_out / 4 + 15) / 16), dim3(256), 0, s, part12, pl.n_tiles,
                            (int64_t)2 * d.C_out, s12, 0, 0);
-        LAUNCH_CHECK("bn bwd reduce")
+        TNET_LAUNCH_CHECK("bn bwd reduce")
         if (!s12_in_place) {
             hipMemcpyAsync(dbeta, s12, (size_t)d.C_out * 4, hipMemcpyDeviceToDevice, s);
             hipMemcpyAsync(dgamma, s12 + d.C_out, (size_t)d.C_out * 4, hipMemcpyDeviceToDevice, s);
@@ -1462,29 +1444,29 @@ extern "C" int ghn3_conv_bn_bwd(const ghn3_conv_desc* g, const float* dout, cons
             const int64_t total4 = (int64_t)pl.P * d.C_out / 4;
             hipLaunchKernelGGL(tnet_dz_kernel, dim3((int)std::min<int64_t>((total4 + 255) / 256, 4096)), dim3(256), 0, s, dout, z, stats, gamma,
                                s12, dzbuf, total4, d.C_out, pl.P);
-            LAUNCH_CHECK("conv bwd dz")
+            TNET_LAUNCH_CHECK("conv bwd dz")
             dzp = dzbuf;
         }
         unsigned short* wp = reinterpret_cast<unsigned short*>(w_r);
         const int64_t plane = (int64_t)pl.taps * d.C_in * ((d.C_out + KC - 1) / KC * KC);
         hipLaunchKernelGGL(tnet_conv_w_pack_kernel, dim3((int)std::min<int64_t>((plane + 255) / 256, 2048)), dim3(256), 0, s, w, wp, d.C_out,
                            d.C_in, pl.taps, 1);
-        LAUNCH_CHECK("conv weight pack (transposed)")
+        TNET_LAUNCH_CHECK("conv weight pack (transposed)")
         const int NT = conv2_nt(pl.n_tiles_in, d.C_in);
         const dim3 grid(pl.n_tiles_in, (d.C_in + 16 * NT - 1) / (16 * NT));
         const size_t lds = conv2_lds(NT);
-#define C2B_CASE(n) case n: rc = set_lds(tnet_conv2_kernel<n, true>, lds); if (rc) return rc; \
+#define C2B_CASE(n) case n: rc = tnet_raise_lds(tnet_conv2_kernel<n, true>, lds); if (rc) return rc; \
         hipLaunchKernelGGL((tnet_conv2_kernel<n, true>), grid, dim3(256), lds, s, dzp, wp, dx, (float*)nullptr, x, d, pl.P_in, pl.P); break;
         switch (NT) { C2B_CASE(2) C2B_CASE(4) C2B_CASE(8) }
 #undef C2B_CASE
-        LAUNCH_CHECK("conv bwd data")
+        TNET_LAUNCH_CHECK("conv bwd data")
         hipLaunchKernelGGL(tnet_conv_wgrad_kernel, dim3(pl.w_chunks, (d.C_out + 63) / 64, ((d.C_in + 63) / 64) * pl.taps), dim3(256), 0, s, dzp,
                            (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, x, part_w, d, pl.P,
                            pl.w_chunk_px);
-        LAUNCH_CHECK("conv wgrad")
+        TNET_LAUNCH_CHECK("conv wgrad")
         hipLaunchKernelGGL(tnet_reduce_rows_kernel, dim3((int)((wr / 4 + 15) / 16)), dim3(256), 0, s, part_w, pl.w_chunks, wr, dw,
                            d.C_out * d.C_in, pl.taps);
-        LAUNCH_CHECK("conv wgrad reduce")
+        TNET_LAUNCH_CHECK("conv wgrad reduce")
         return GHN3_OK;
     }
     rc = conv_repack(d, pl, w, w_r, s);
@@ -1493,19 +1475,19 @@ extern "C" int ghn3_conv_bn_bwd(const ghn3_conv_desc* g, const float* dout, cons
     {
         const int NT = nt_of(d.C_in);
         const size_t lds = cbwd_lds(NT);
-#define CBWD_CASE(n, t) case 10 * n + t: rc = set_lds(tnet_conv_bwd_data_kernel<n, t>, lds); if (rc) return rc; \
+#define CBWD_CASE(n, t) case 10 * n + t: rc = tnet_raise_lds(tnet_conv_bwd_data_kernel<n, t>, lds); if (rc) return rc; \
         hipLaunchKernelGGL((tnet_conv_bwd_data_kernel<n, t>), dim3(pl.n_tiles_in), dim3(256), lds, s, dout, z, stats, gamma, s12, w_r, x, dx, d, pl.P, pl.P_in); break;
         switch (10 * NT + terms_of(NT)) { CBWD_CASE(4, 3) CBWD_CASE(8, 3) CBWD_CASE(16, 3) CBWD_CASE(4, 2) CBWD_CASE(8, 2) CBWD_CASE(16, 2) CBWD_CASE(32, 2) }
 #undef CBWD_CASE
-        LAUNCH_CHECK("conv bwd data")
+        TNET_LAUNCH_CHECK("conv bwd data")
     }
     // 3. dW (in the parameter's own [C_out][C_in][kh][kw] order)
     hipLaunchKernelGGL(tnet_conv_wgrad_kernel, dim3(pl.w_chunks, (d.C_out + 63) / 64, ((d.C_in + 63) / 64) * pl.taps), dim3(256), 0, s, dout, z,
                        stats, gamma, s12, x, part_w, d, pl.P, pl.w_chunk_px);
-    LAUNCH_CHECK("conv wgrad")
+    TNET_LAUNCH_CHECK("conv wgrad")
     hipLaunchKernelGGL(tnet_reduce_rows_kernel, dim3((int)((wr / 4 + 15) / 16)), dim3(256), 0, s, part_w, pl.w_chunks, wr, dw,
                        d.C_out * d.C_in, pl.taps);
-    LAUNCH_CHECK("conv wgrad reduce")
+    TNET_LAUNCH_CHECK("conv wgrad reduce")
     return GHN3_OK;
 }
 
@@ -1697,7 +1679,7 @@ extern "C" int ghn3_se_fwd(int N, int HW, int C, int J, const float* x, const fl
     if (!x || !w1 || !b1 || !w2 || !b2 || !y || !save) { ghn3_set_error("se fwd: null pointer"); return GHN3_E_ARG; }
     hipLaunchKernelGGL(tnet_se_fwd_kernel, dim3(N), dim3(256), (size_t)4096 + (2 * C + J) * 4, (hipStream_t)stream_, x, w1, b1, w2, b2, y, save,
                        HW, C, J);
-    LAUNCH_CHECK("se fwd")
+    TNET_LAUNCH_CHECK("se fwd")
     return GHN3_OK;
 }
 
@@ -1711,11 +1693,11 @@ extern "C" int ghn3_se_bwd(int N, int HW, int C, int J, const float* dy, const f
     }
     hipStream_t s = (hipStream_t)stream_;
     hipLaunchKernelGGL(tnet_se_bwd_kernel, dim3(N), dim3(256), (size_t)4096 + (2 * C + J) * 4, s, dy, x, w1, w2, save, dx, scratch, HW, C, J);
-    LAUNCH_CHECK("se bwd")
+    TNET_LAUNCH_CHECK("se bwd")
     const int64_t total = (int64_t)2 * C * J + C + J;
     hipLaunchKernelGGL(tnet_se_wgrad_kernel, dim3((int)std::min<int64_t>((total + 255) / 256, 4096)), dim3(256), 0, s, scratch, save, dw1, db1, dw2,
                        db2, N, C, J);
-    LAUNCH_CHECK("se wgrad")
+    TNET_LAUNCH_CHECK("se wgrad")
     return GHN3_OK;
 }
 
@@ -1840,7 +1822,7 @@ extern "C" int ghn3_pool_fwd(const ghn3_pool_desc* g, const float* x, float* y, 
     const int64_t total = (int64_t)d.N * d.Ho * d.Wo * (d.C / 4);
     hipLaunchKernelGGL(tnet_pool_fwd_kernel, dim3((int)std::min<int64_t>((total + 255) / 256, 8192)), dim3(256), 0, (hipStream_t)stream_, x, y, idx,
                        d, total);
-    LAUNCH_CHECK("pool fwd")
+    TNET_LAUNCH_CHECK("pool fwd")
     return GHN3_OK;
 }
 
@@ -1852,6 +1834,6 @@ extern "C" int ghn3_pool_bwd(const ghn3_pool_desc* g, const float* dy, const uns
     const int64_t total = (int64_t)d.N * d.H * d.W * (d.C / 4);
     hipLaunchKernelGGL(tnet_pool_bwd_kernel, dim3((int)std::min<int64_t>((total + 255) / 256, 8192)), dim3(256), 0, (hipStream_t)stream_, dy, idx,
                        dx, d, total);
-    LAUNCH_CHECK("pool bwd")
+    TNET_LAUNCH_CHECK("pool bwd")
     return GHN3_OK;
 }

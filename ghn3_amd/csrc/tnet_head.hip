@@ -13,9 +13,9 @@
 //                             between linears, applies ReLU, the mask and the scale.  The a_j are kept for the backward.
 //   backward  head_dgrad      one launch per linear, last first: dA = G_j W_j; between linears G_j-1 = dA (a_j-1 > 0 ? s : 0),
 //                             for the first linear dx (the pooling's broadcast / the flatten's scatter) in x's layout;
-//             head_wgrad      every dW_j = G_j^T a_j-1 and db_j = column sums of G_j in one launch: WG_ROWS-row chunks, each
-//                             32 x 32 output block a workgroup; with one chunk (B <= 256) written in place,
-//             head_reduce     else as fixed-order partials summed here.
+//             tnet_wgrad      (tnet_wgrad.hip) every dW_j = G_j^T a_j-1 and db_j = column sums of G_j in one launch: 256-row
+//                             chunks, each 32 x 32 output block a workgroup; with one chunk (B <= 256) written in place,
+//             tnet_reduce     (tnet_wgrad.hip) else as fixed-order partials summed here.
 //   xent      xent_fwd        a workgroup per network (up to 32 networks per launch, their pointers in the kernel arguments),
 //                             a wave per row: ce[n], the row log-sum-exps for the backward, the integer hit counts;
 //             xent_bwd        a wave per (network, row): dlogits = g_n / B (softmax - (1 - eps) onehot - eps / K).
@@ -27,32 +27,14 @@
 // element counts < 2^31.
 
 #include <math.h>
-#include "ghn3_internal.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "tnet_common.h"
 
 namespace {
 
 constexpr int NT = 256;                     // threads per workgroup (4 waves)
 constexpr int MAXL = GHN3_HEAD_MAX_LINEAR;
-constexpr int WG_ROWS = 256;                // rows per partial product of head_wgrad
+static_assert(MAXL <= TNET_WG_MAX && MAXL <= TNET_RED_MAX, "one tnet_wgrad / tnet_reduce launch takes every linear");
 constexpr int MAX_B = 4096, MAX_F = 32768, MAX_D = 4096;
-
-__device__ inline float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ inline float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ inline int wave_isum(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // Y[rows][Nout] tile (rows r0 .. r0 + 16 RT, columns 16 ct .. 16 ct + 16) = A op(W):
 //   A [rows][lda] row-major (K columns read);  WT = false: W [Nout][K] (nn.Linear, Y = A W^T);  WT = true: W [K][Nout], Y = A W.
@@ -187,75 +169,6 @@ __global__ __launch_bounds__(NT) void head_dgrad_kernel(BwdLin a) {
     });
 }
 
-// dW [Nout][K] = G^T X, db [Nout] = column sums of G (as column K of an X padded with ones): one WG_ROWS-row chunk and 32 x 32
-// output block per workgroup (a wave per 16 x 16 quarter); one chunk: written to w, b; else to part [chunk][Nout][K + 1]
-struct WgProb {
-    const float* G; const float* X; float* w; float* b; float* part;
-    int rows, Nout, K;
-    int tiles_n, tiles_k, chunks, block_start;
-};
-struct WgSet { WgProb p[MAXL]; int n; };
-
-__global__ __launch_bounds__(NT) void head_wgrad_kernel(WgSet set) {
-    int pi = 0;
-    for (int j = 1; j < set.n; ++j) pi = (int)blockIdx.x >= set.p[j].block_start ? j : pi;
-    const WgProb& P = set.p[pi];
-    const int local = blockIdx.x - P.block_start;
-    const int chunk = local % P.chunks, tile = local / P.chunks;
-    const int tn = tile % P.tiles_n, tk = tile / P.tiles_n;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, q = lane >> 4;
-    const int n0 = tn * 32 + (wave & 1) * 16, k0 = tk * 32 + (wave >> 1) * 16;
-    const int K1 = P.K + 1;
-    const int n = n0 + i, k = k0 + i;
-    const bool nok = n < P.Nout, kok = k < K1;
-    const int nc = nok ? n : 0, kc = k < P.K ? k : 0;
-    const int rb = chunk * WG_ROWS, re = min(rb + WG_ROWS, P.rows);
-    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int r0 = rb; r0 < re; r0 += 16) {
-        float a[4], b[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int r = r0 + 4 * q + j;
-            const bool rok = r < re;
-            const int rc = rok ? r : rb;
-            const float gv = P.G[(size_t)rc * P.Nout + nc];
-            const float xv = k < P.K ? P.X[(size_t)rc * P.K + kc] : 1.f;
-            a[j] = (rok && nok) ? gv : 0.f;
-            b[j] = (rok && kok) ? xv : 0.f;
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], b[j], acc, 0, 0, 0);
-    }
-    // C/D: row (n) 4 q + g, col (k) i
-    if (kok) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int nn = n0 + 4 * q + g;
-            if (nn >= P.Nout) continue;
-            if (P.chunks > 1) P.part[((size_t)chunk * P.Nout + nn) * K1 + k] = acc[g];
-            else if (k < P.K) P.w[(size_t)nn * P.K + k] = acc[g];
-            else P.b[nn] = acc[g];
-        }
-    }
-}
-
-// w / b = sum over chunks of part [chunks][Nout][K + 1], in chunk order (problems with one chunk were written in place)
-struct RedSet { WgProb p[MAXL]; int start[MAXL]; int n; };
-
-__global__ __launch_bounds__(NT) void head_reduce_kernel(RedSet set) {
-    int pi = 0;
-    for (int j = 1; j < set.n; ++j) pi = (int)blockIdx.x >= set.start[j] ? j : pi;
-    const WgProb& P = set.p[pi];
-    const int K1 = P.K + 1, M = P.Nout * K1;
-    const int e = (blockIdx.x - set.start[pi]) * NT + threadIdx.x;
-    if (e >= M) return;
-    float s = 0.f;
-    for (int c = 0; c < P.chunks; ++c) s += P.part[(size_t)c * M + e];
-    const int n = e / K1, k = e - n * K1;
-    if (k < P.K) P.w[(size_t)n * P.K + k] = s;
-    else P.b[n] = s;
-}
-
 // ------------------------------------------------------------------------------------------------ cross-entropy
 struct XentTable { const float* p[GHN3_XENT_MAX_NETS]; };
 struct XentArgs { const int64_t* targets; float* ce; float* lse; int* hits; int B, K, n0; float eps; };
@@ -375,9 +288,6 @@ int check(const ghn3_head_desc* g, HeadDims* out) {
     return GHN3_OK;
 }
 
-inline int64_t al(int64_t v) { return (v + 63) & ~(int64_t)63; }
-int chunks(int rows) { return (rows + WG_ROWS - 1) / WG_ROWS; }
-
 // forward scratch (kept for the backward): f (absent when x is f) | a_1 .. a_n-1
 struct FwdLayout { int64_t f, a[MAXL], total; };
 FwdLayout fwd_layout(const HeadDims& d) {
@@ -389,7 +299,7 @@ FwdLayout fwd_layout(const HeadDims& d) {
     return L;
 }
 
-// backward scratch: G_1 .. G_n-1 | partials of every linear (B > WG_ROWS only)
+// backward scratch: G_1 .. G_n-1 | partials of every linear (more than one row chunk only)
 struct BwdLayout { int64_t g[MAXL], part[MAXL + 1], total; };
 BwdLayout bwd_layout(const HeadDims& d) {
     BwdLayout L{};
@@ -397,13 +307,11 @@ BwdLayout bwd_layout(const HeadDims& d) {
     for (int j = 1; j < d.n; ++j) { L.g[j] = o; o += al((int64_t)d.B * d.d[j]); }
     for (int j = 1; j <= d.n; ++j) {
         L.part[j] = o;
-        if (chunks(d.B) > 1) o += al((int64_t)chunks(d.B) * d.d[j] * (d.d[j - 1] + 1));
+        if (tnet_wg_chunks(d.B) > 1) o += tnet_wg_part_floats(d.B, d.d[j], d.d[j - 1]);
     }
     L.total = o;
     return L;
 }
-
-#define HEAD_LAUNCH_CHECK(what) { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) { ghn3_set_error(what ": %s", hipGetErrorString(e_)); return GHN3_E_HIP; } }
 
 // 64-row blocks where that still gives 128 workgroups, else 16-row ones
 bool wide_rows(int rows, int Nout) { return rows >= 64 && (int64_t)((rows + 63) / 64) * ((Nout + 15) / 16) >= 128; }
@@ -414,7 +322,7 @@ int launch_fwd_lin(const FwdLin& a, hipStream_t s) {
         hipLaunchKernelGGL(head_fwd_lin_kernel<4>, dim3(tiles, (a.rows + 63) / 64), dim3(NT), 0, s, a);
     else
         hipLaunchKernelGGL(head_fwd_lin_kernel<1>, dim3(tiles, (a.rows + 15) / 16), dim3(NT), 0, s, a);
-    HEAD_LAUNCH_CHECK("head linear");
+    TNET_LAUNCH_CHECK("head linear");
     return GHN3_OK;
 }
 
@@ -424,7 +332,7 @@ int launch_dgrad(const BwdLin& a, hipStream_t s) {
         hipLaunchKernelGGL(head_dgrad_kernel<4>, dim3(tiles, (a.rows + 63) / 64), dim3(NT), 0, s, a);
     else
         hipLaunchKernelGGL(head_dgrad_kernel<1>, dim3(tiles, (a.rows + 15) / 16), dim3(NT), 0, s, a);
-    HEAD_LAUNCH_CHECK("head dgrad");
+    TNET_LAUNCH_CHECK("head dgrad");
     return GHN3_OK;
 }
 
@@ -452,7 +360,7 @@ extern "C" int ghn3_head_fwd(const ghn3_head_desc* desc, const float* x, const g
         FeatArgs fa{x, scratch + L.f, d.B, d.C, d.HW, d.layout, d.glob_avg};
         const int blocks = d.glob_avg && !d.layout ? (d.B * d.C + NT / 64 - 1) / (NT / 64) : (d.B * d.d[0] + NT - 1) / NT;
         hipLaunchKernelGGL(head_feat_kernel, dim3(blocks), dim3(NT), 0, s, fa);
-        HEAD_LAUNCH_CHECK("head feat");
+        TNET_LAUNCH_CHECK("head feat");
         f = scratch + L.f;
     }
     for (int j = 1; j <= d.n; ++j) {
@@ -496,28 +404,17 @@ extern "C" int ghn3_head_bwd(const ghn3_head_desc* desc, const float* dlogits, c
         }
         if ((rc = launch_dgrad(a, s))) return rc;
     }
-    WgSet ws;
-    RedSet rs;
-    ws.n = rs.n = d.n;
-    int blocks = 0, rblocks = 0;
+    // every dW_j = G_j^T a_j-1 and db_j in one launch: in place with one row chunk, else partials and their sums
+    const bool parts = tnet_wg_chunks(d.B) > 1;
+    TnetWgProb wg[MAXL];
+    TnetRedProb red[MAXL];
     for (int j = 1; j <= d.n; ++j) {
-        WgProb q{G[j], fwd_a[j], grads->w[j - 1], grads->b[j - 1], scratch + L.part[j], d.B, d.d[j], d.d[j - 1]};
-        q.tiles_n = (q.Nout + 31) / 32;
-        q.tiles_k = (q.K + 1 + 31) / 32;
-        q.chunks = chunks(d.B);
-        q.block_start = blocks;
-        blocks += q.tiles_n * q.tiles_k * q.chunks;
-        ws.p[j - 1] = q;
-        rs.p[j - 1] = q;
-        rs.start[j - 1] = rblocks;
-        rblocks += (q.Nout * (q.K + 1) + NT - 1) / NT;
+        wg[j - 1] = TnetWgProb{G[j], fwd_a[j], parts ? scratch + L.part[j] : nullptr, grads->w[j - 1], grads->b[j - 1],
+                               d.B, d.d[j], d.d[j - 1], 1};
+        red[j - 1] = tnet_wg_reduce(wg[j - 1]);
     }
-    hipLaunchKernelGGL(head_wgrad_kernel, dim3(blocks), dim3(NT), 0, s, ws);
-    HEAD_LAUNCH_CHECK("head wgrad");
-    if (chunks(d.B) > 1) {
-        hipLaunchKernelGGL(head_reduce_kernel, dim3(rblocks), dim3(NT), 0, s, rs);
-        HEAD_LAUNCH_CHECK("head reduce");
-    }
+    if ((rc = tnet_wgrad_launch(wg, d.n, s))) return rc;
+    if (parts && (rc = tnet_reduce_launch(red, d.n, s))) return rc;
     return GHN3_OK;
 }
 
@@ -548,7 +445,7 @@ extern "C" int ghn3_xent_fwd(const ghn3_xent_desc* desc, const float* const* log
         const int threads = g.B >= 1024 ? 1024 : ((g.B + 63) / 64) * 64;
         hipLaunchKernelGGL(xent_fwd_kernel, dim3(cnt), dim3(threads), 0, s, t,
                            XentArgs{targets, ce, lse, (int*)hits, g.B, g.K, n0, g.eps});
-        HEAD_LAUNCH_CHECK("xent fwd");
+        TNET_LAUNCH_CHECK("xent fwd");
     }
     return GHN3_OK;
 }
@@ -570,7 +467,7 @@ extern "C" int ghn3_xent_bwd(const ghn3_xent_desc* desc, const float* const* log
         }
         hipLaunchKernelGGL(xent_bwd_kernel, dim3(cnt, (g.B + NT / 64 - 1) / (NT / 64)), dim3(NT), 0, s, t,
                            XentBwdArgs{targets, lse, dce, g.B, g.K, n0, g.eps});
-        HEAD_LAUNCH_CHECK("xent bwd");
+        TNET_LAUNCH_CHECK("xent bwd");
     }
     return GHN3_OK;
 }

@@ -17,8 +17,10 @@
 //                             (dropped rows: zero); LN2 parameter partials per workgroup;
 //             ghn3_attn_bwd   -> dqkv;
 //             msa_qkv_bwd     da1 = dqkv Wqkv -> LN1 backward -> + dy1 -> dx in x's layout; LN1 parameter partials;
-//             msa_wgrad       the four weight (+ bias) gradients dW = G^T X as fixed row-chunk partial products;
-//             msa_reduce      fixed-order sums of every partial -> dense gradients.
+//             tnet_wgrad      (tnet_wgrad.hip) the four weight (+ bias) gradients dW = G^T X as fixed row-chunk partial
+//                             products;
+//             tnet_reduce     (tnet_wgrad.hip) fixed-order sums of every partial, the LayerNorm ones included -> dense
+//                             gradients.
 //
 // Every product runs on v_mfma_f32_16x16x4_f32 (exact fp32 products, fp32 accumulate; no 16-bit operands: the target networks
 // and their stock path are fp32).  Each lane feeds one float4 of A and of B per four MFMAs: instruction j of a 16-wide k step
@@ -27,14 +29,11 @@
 // <= 1024, element counts < 2^31.
 
 #include <algorithm>
-#include "ghn3_internal.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "tnet_common.h"
 
 namespace {
 
 constexpr int NT = 256;                     // threads per workgroup (4 waves)
-constexpr int WG_ROWS = 256;                // rows per partial product of msa_wgrad
 constexpr int MAX_LDS = 160 * 1024;
 
 struct MsaDims {
@@ -56,12 +55,6 @@ __device__ inline size_t x_off(const MsaDims& d, int r, int c) {
     if (d.layout) return (size_t)r * d.C + c;
     const int b = r / d.N, n = r - b * d.N;
     return ((size_t)b * d.C + c) * d.N + n;
-}
-
-__device__ inline float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 __device__ inline float gelu_erf(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752f)); }
@@ -398,77 +391,6 @@ __global__ __launch_bounds__(NT) void msa_qkv_bwd_kernel(MsaDims d, const float*
     }
 }
 
-// dW [Nout][K] (+ db [Nout] as column K) = sum over rows of G[r][n] X[r][k]: one partial per WG_ROWS-row chunk and 32 x 32
-// output block (a wave per 16 x 16 quarter), written to part [chunk][Nout][K + 1]
-struct WgProb {
-    const float* G; const float* X; float* part;
-    int rows, Nout, K, bias;
-    int tiles_n, tiles_k, chunks, block_start;
-};
-struct WgSet { WgProb p[4]; int n; };
-
-__global__ __launch_bounds__(NT) void msa_wgrad_kernel(WgSet set) {
-    int pi = 0;
-    for (int j = 1; j < set.n; ++j) pi = (int)blockIdx.x >= set.p[j].block_start ? j : pi;
-    const WgProb& P = set.p[pi];
-    const int local = blockIdx.x - P.block_start;
-    const int chunk = local % P.chunks, tile = local / P.chunks;
-    const int tn = tile % P.tiles_n, tk = tile / P.tiles_n;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, q = lane >> 4;
-    const int n0 = tn * 32 + (wave & 1) * 16, k0 = tk * 32 + (wave >> 1) * 16;
-    const int K1 = P.K + P.bias;
-    const int n = n0 + i, k = k0 + i;
-    const bool nok = n < P.Nout, kok = k < K1;
-    const int nc = nok ? n : 0, kc = k < P.K ? k : 0;
-    const int rb = chunk * WG_ROWS, re = min(rb + WG_ROWS, P.rows);
-    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int r0 = rb; r0 < re; r0 += 16) {
-        float a[4], b[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int r = r0 + 4 * q + j;
-            const bool rok = r < re;
-            const int rc = rok ? r : rb;
-            const float gv = P.G[(size_t)rc * P.Nout + nc];
-            const float xv = k < P.K ? P.X[(size_t)rc * P.K + kc] : 1.f;
-            a[j] = (rok && nok) ? gv : 0.f;
-            b[j] = (rok && kok) ? xv : 0.f;
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], b[j], acc, 0, 0, 0);
-    }
-    // C/D: row (n) 4 q + g, col (k) i
-    if (kok) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int nn = n0 + 4 * q + g;
-            if (nn < P.Nout) P.part[((size_t)chunk * P.Nout + nn) * K1 + k] = acc[g];
-        }
-    }
-}
-
-// out = sum over parts of part [parts][M] in part order; element e = n ld + k -> w[n K + k] (k < K) or b[n] (k == K);
-// ln != 0: M = 2 C, element e < C -> w[e] (gamma), else b[e - C] (beta)
-struct RedProb { const float* part; float* w; float* b; int parts, M, ld, K, ln, block_start; };
-struct RedSet { RedProb p[6]; int n; };
-
-__global__ __launch_bounds__(NT) void msa_reduce_kernel(RedSet set) {
-    int pi = 0;
-    for (int j = 1; j < set.n; ++j) pi = (int)blockIdx.x >= set.p[j].block_start ? j : pi;
-    const RedProb& P = set.p[pi];
-    const int e = (blockIdx.x - P.block_start) * NT + threadIdx.x;
-    if (e >= P.M) return;
-    float s = 0.f;
-    for (int c = 0; c < P.parts; ++c) s += P.part[(size_t)c * P.M + e];
-    if (P.ln) {
-        if (e < P.K) P.w[e] = s; else P.b[e - P.K] = s;
-    } else {
-        const int n = e / P.ld, k = e - n * P.ld;
-        if (k < P.K) P.w[(size_t)n * P.K + k] = s;
-        else if (P.b) P.b[n] = s;
-    }
-}
-
 // ------------------------------------------------------------------------------------------------ host side
 int check(const ghn3_msa_desc* g, MsaDims* out) {
     if (!g) { ghn3_set_error("msa: null descriptor"); return GHN3_E_ARG; }
@@ -501,8 +423,6 @@ int check(const ghn3_msa_desc* g, MsaDims* out) {
     return GHN3_OK;
 }
 
-inline int64_t al(int64_t v) { return (v + 63) & ~(int64_t)63; }
-
 // the row blocks: 32 rows unless the widest kernel of the pass needs more LDS than a CU has
 int lds_post(int RB, const MsaDims& d) { return RB * (2 * (r16(d.C) + 4) + r16(d.hidden) + 4) * 4; }
 int lds_post_bwd(int RB, const MsaDims& d) { return RB * (2 * (r16(d.C) + 4) + std::max(r16(d.hidden), r16(d.C)) + 4) * 4; }
@@ -528,9 +448,6 @@ FwdLayout fwd_layout(const MsaDims& d) {
     return f;
 }
 
-int wg_chunks(int rows) { return (rows + WG_ROWS - 1) / WG_ROWS; }
-int64_t wg_part(int rows, int Nout, int K) { return al((int64_t)wg_chunks(rows) * Nout * (K + 1)); }
-
 // backward scratch: dO | dy1 | dqkv | a1 | dh | gact | a2 | ln2 parts | ln1 parts | weight-gradient parts (qkv, o, 1, 2)
 struct BwdLayout { int64_t dO, dy1, dqkv, a1, dh, gact, a2, ln2, ln1, pq, po, p1, p2, total; };
 BwdLayout bwd_layout(const MsaDims& d) {
@@ -546,28 +463,13 @@ BwdLayout bwd_layout(const MsaDims& d) {
     b.a2 = o; o += al((int64_t)d.Kr * d.C);
     b.ln2 = o; o += al((int64_t)((d.Kr + RB - 1) / RB) * 2 * d.C);
     b.ln1 = o; o += al((int64_t)((d.R + RB - 1) / RB) * 2 * d.C);
-    b.pq = o; o += wg_part(d.R, 3 * d.C, d.C);
-    b.po = o; o += wg_part(d.R, d.C, d.C);
-    b.p1 = o; o += wg_part(d.Kr, d.hidden, d.C);
-    b.p2 = o; o += wg_part(d.Kr, d.C, d.hidden);
+    b.pq = o; o += tnet_wg_part_floats(d.R, 3 * d.C, d.C);
+    b.po = o; o += tnet_wg_part_floats(d.R, d.C, d.C);
+    b.p1 = o; o += tnet_wg_part_floats(d.Kr, d.hidden, d.C);
+    b.p2 = o; o += tnet_wg_part_floats(d.Kr, d.C, d.hidden);
     b.total = o;
     return b;
 }
-
-template <typename K> int raise_lds(K kern) {
-    // (once per kernel: the most a launch of this file may ask)
-    static const void* done[16];
-    static int n_done = 0;
-    const void* key = (const void*)kern;
-    for (int i = 0; i < n_done; ++i)
-        if (done[i] == key) return GHN3_OK;
-    hipError_t e = hipFuncSetAttribute(key, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS);
-    if (e != hipSuccess) { ghn3_set_error("msa: hipFuncSetAttribute: %s", hipGetErrorString(e)); return GHN3_E_HIP; }
-    if (n_done < 16) done[n_done++] = key;
-    return GHN3_OK;
-}
-
-#define MSA_LAUNCH_CHECK(what) { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) { ghn3_set_error(what ": %s", hipGetErrorString(e_)); return GHN3_E_HIP; } }
 
 template <int RB>
 int fwd_rb(const MsaDims& d, const float* x, const ghn3_msa_params& p, float* out, float* scratch, float* P, hipStream_t s) {
@@ -576,16 +478,16 @@ int fwd_rb(const MsaDims& d, const float* x, const ghn3_msa_params& p, float* ou
     const bool train = P != nullptr;
     int rc;
     size_t lds = (size_t)RB * (r16(d.C) + 4) * 4;
-    if ((rc = raise_lds(msa_ln_qkv_kernel<RB>))) return rc;
+    if ((rc = tnet_raise_lds(msa_ln_qkv_kernel<RB>, MAX_LDS))) return rc;
     hipLaunchKernelGGL(msa_ln_qkv_kernel<RB>, dim3((d.R + RB - 1) / RB), dim3(NT), lds, s, d, x, p, scratch + f.qkv,
                        scratch + f.stats1, nn);
-    MSA_LAUNCH_CHECK("msa ln_qkv");
+    TNET_LAUNCH_CHECK("msa ln_qkv");
     if ((rc = ghn3_attn_fwd(scratch + f.O, scratch + f.qkv, nullptr, P, nn, d.B, d.N, d.C, d.heads, s))) return rc;
-    if ((rc = raise_lds(msa_post_kernel<RB>))) return rc;
+    if ((rc = tnet_raise_lds(msa_post_kernel<RB>, MAX_LDS))) return rc;
     hipLaunchKernelGGL(msa_post_kernel<RB>, dim3((d.Kr + RB - 1) / RB), dim3(NT), (size_t)lds_post(RB, d), s, d, x,
                        (const float*)(scratch + f.O), p, out, train ? scratch + f.y1 : nullptr,
                        train ? scratch + f.stats2 : nullptr, train ? scratch + f.pre : nullptr);
-    MSA_LAUNCH_CHECK("msa post");
+    TNET_LAUNCH_CHECK("msa post");
     return GHN3_OK;
 }
 
@@ -601,57 +503,33 @@ int bwd_rb(const MsaDims& d, const float* dout, const float* x, const ghn3_msa_p
         if (e != hipSuccess) { ghn3_set_error("msa bwd: hipMemsetAsync: %s", hipGetErrorString(e)); return GHN3_E_HIP; }
     }
     const int nb_post = (d.Kr + RB - 1) / RB, nb_rows = (d.R + RB - 1) / RB;
-    if ((rc = raise_lds(msa_post_bwd_kernel<RB>))) return rc;
+    if ((rc = tnet_raise_lds(msa_post_bwd_kernel<RB>, MAX_LDS))) return rc;
     hipLaunchKernelGGL(msa_post_bwd_kernel<RB>, dim3(nb_post), dim3(NT), (size_t)lds_post_bwd(RB, d), s, d, dout, p,
                        fs + f.y1, fs + f.stats2, fs + f.pre, scratch + b.dh, scratch + b.gact, scratch + b.a2, scratch + b.dy1,
                        scratch + b.dO, scratch + b.ln2);
-    MSA_LAUNCH_CHECK("msa post bwd");
+    TNET_LAUNCH_CHECK("msa post bwd");
     if ((rc = ghn3_attn_bwd(scratch + b.dqkv, scratch + b.dO, fs + f.qkv, P, fs + f.O, nullptr, nullptr, nn, d.B, d.N, d.C,
                             d.heads, 0, s)))
         return rc;
-    if ((rc = raise_lds(msa_qkv_bwd_kernel<RB>))) return rc;
+    if ((rc = tnet_raise_lds(msa_qkv_bwd_kernel<RB>, MAX_LDS))) return rc;
     hipLaunchKernelGGL(msa_qkv_bwd_kernel<RB>, dim3(nb_rows), dim3(NT), (size_t)lds_qkv_bwd(RB, d), s, d, x, p,
                        (const float*)(scratch + b.dqkv), fs + f.stats1, (const float*)(scratch + b.dy1), scratch + b.a1, dx,
                        scratch + b.ln1);
-    MSA_LAUNCH_CHECK("msa qkv bwd");
+    TNET_LAUNCH_CHECK("msa qkv bwd");
     // weight gradients: dWqkv = dqkv^T a1, dWo = dy1^T O (rows of all tokens; dropped ones are zero), dW1 = dh^T a2, dW2 = dout^T gelu
-    WgSet ws;
-    ws.n = 4;
-    const WgProb probs[4] = {
-        {scratch + b.dqkv, scratch + b.a1, scratch + b.pq, d.R, 3 * d.C, d.C, g.b_qkv != nullptr},
-        {scratch + b.dy1, fs + f.O, scratch + b.po, d.R, d.C, d.C, 1},
-        {scratch + b.dh, scratch + b.a2, scratch + b.p1, d.Kr, d.hidden, d.C, 1},
-        {dout, scratch + b.gact, scratch + b.p2, d.Kr, d.C, d.hidden, 1},
+    const TnetWgProb wg[4] = {
+        {scratch + b.dqkv, scratch + b.a1, scratch + b.pq, g.w_qkv, g.b_qkv, d.R, 3 * d.C, d.C, g.b_qkv != nullptr},
+        {scratch + b.dy1, fs + f.O, scratch + b.po, g.w_o, g.b_o, d.R, d.C, d.C, 1},
+        {scratch + b.dh, scratch + b.a2, scratch + b.p1, g.w1, g.b1, d.Kr, d.hidden, d.C, 1},
+        {dout, scratch + b.gact, scratch + b.p2, g.w2, g.b2, d.Kr, d.C, d.hidden, 1},
     };
-    int blocks = 0;
-    for (int j = 0; j < 4; ++j) {
-        WgProb q = probs[j];
-        q.tiles_n = (q.Nout + 31) / 32;
-        q.tiles_k = (q.K + q.bias + 31) / 32;
-        q.chunks = wg_chunks(q.rows);
-        q.block_start = blocks;
-        blocks += q.tiles_n * q.tiles_k * q.chunks;
-        ws.p[j] = q;
-    }
-    hipLaunchKernelGGL(msa_wgrad_kernel, dim3(blocks), dim3(NT), 0, s, ws);
-    MSA_LAUNCH_CHECK("msa wgrad");
-    RedSet rs;
-    rs.n = 6;
-    float* wouts[4][2] = {{g.w_qkv, g.b_qkv}, {g.w_o, g.b_o}, {g.w1, g.b1}, {g.w2, g.b2}};
-    int rblocks = 0;
-    for (int j = 0; j < 4; ++j) {
-        const WgProb& q = ws.p[j];
-        const int ld = q.K + q.bias;
-        rs.p[j] = RedProb{q.part, wouts[j][0], q.bias ? wouts[j][1] : nullptr, q.chunks, q.Nout * ld, ld, q.K, 0, rblocks};
-        rblocks += (rs.p[j].M + NT - 1) / NT;
-    }
-    rs.p[4] = RedProb{scratch + b.ln1, g.ln1_w, g.ln1_b, nb_rows, 2 * d.C, d.C, d.C, 1, rblocks};
-    rblocks += (2 * d.C + NT - 1) / NT;
-    rs.p[5] = RedProb{scratch + b.ln2, g.ln2_w, g.ln2_b, nb_post, 2 * d.C, d.C, d.C, 1, rblocks};
-    rblocks += (2 * d.C + NT - 1) / NT;
-    hipLaunchKernelGGL(msa_reduce_kernel, dim3(rblocks), dim3(NT), 0, s, rs);
-    MSA_LAUNCH_CHECK("msa reduce");
-    return GHN3_OK;
+    if ((rc = tnet_wgrad_launch(wg, 4, s))) return rc;
+    const TnetRedProb red[6] = {
+        tnet_wg_reduce(wg[0]), tnet_wg_reduce(wg[1]), tnet_wg_reduce(wg[2]), tnet_wg_reduce(wg[3]),
+        {scratch + b.ln1, g.ln1_w, g.ln1_b, nb_rows, 2 * d.C, d.C, d.C, 1},
+        {scratch + b.ln2, g.ln2_w, g.ln2_b, nb_post, 2 * d.C, d.C, d.C, 1},
+    };
+    return tnet_reduce_launch(red, 6, s);
 }
 
 bool a16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }

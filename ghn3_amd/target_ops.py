@@ -64,13 +64,16 @@ def _stream():
 _SCRATCH = {}
 
 
-def _scratch_floats(lib, d, backward):
-    key = (d.N, d.H, d.W, d.C_in, d.C_out, d.ks, d.stride, d.pad, d.dil, backward)
+def _scratch_floats(fn_name, d, backward):
+    """What the C function `fn_name` (ghn3_*_scratch_floats) answers for the descriptor d (a ctypes structure), asked once per
+    descriptor."""
+    key = (fn_name, bytes(d), backward)
     n = _SCRATCH.get(key)
     if n is None:
-        n = int(lib.ghn3_dwpw_scratch_floats(ctypes.byref(d), backward))
+        lib = L.load()
+        n = int(getattr(lib, fn_name)(ctypes.byref(d), backward))
         if n < 0:
-            raise L.Ghn3Error('ghn3_dwpw_scratch_floats: %s' % lib.ghn3_last_error().decode())
+            raise L.Ghn3Error('%s: %s' % (fn_name, lib.ghn3_last_error().decode()))
         _SCRATCH[key] = n
     return n
 
@@ -116,7 +119,7 @@ class DwPwBn(torch.autograd.Function):
         out = torch.empty((d.N, C_out, d.Ho, d.Wo), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
         z = torch.empty_like(out)
         stats = torch.empty(3 * C_out, dtype=torch.float32, device=dev)
-        scratch = torch.empty(_scratch_floats(lib, d, 0), dtype=torch.float32, device=dev)
+        scratch = torch.empty(_scratch_floats('ghn3_dwpw_scratch_floats', d, 0), dtype=torch.float32, device=dev)
         stream = _stream()
         L._check(lib.ghn3_dwpw_bn_fwd(ctypes.byref(d), _ptr(xc), _ptr(wd) if wd is not None else None, _ptr(wp), _ptr(g), _ptr(b),
                                       _ptr(z), _ptr(out), _ptr(stats), _ptr(scratch), stream), 'ghn3_dwpw_bn_fwd')
@@ -142,7 +145,7 @@ class DwPwBn(torch.autograd.Function):
         # small layers of a CIFAR network)
         n_wd = 0 if wd is None else wd.numel()
         n_par = n_wd + wp.numel() + 2 * C_out
-        buf = torch.empty(n_par + 64 + _scratch_floats(lib, d, 1), dtype=torch.float32, device=dev)
+        buf = torch.empty(n_par + 64 + _scratch_floats('ghn3_dwpw_scratch_floats', d, 1), dtype=torch.float32, device=dev)
         dwd = None if wd is None else buf[:n_wd].view(wd.shape)
         dwp = buf[n_wd:n_wd + wp.numel()].view(wp.shape)
         db = buf[n_par - 2 * C_out:n_par - C_out]            # (dbeta directly followed by dgamma: the kernels' own pair of sums)
@@ -183,20 +186,6 @@ def _conv_desc(x, w, stride, pad, dil, relu, eps, no_norm=False):
                      int(bool(relu)) | (CONV_NO_NORM if no_norm else 0), float(eps))
 
 
-_CONV_SCRATCH = {}
-
-
-def _conv_scratch_floats(lib, d, backward):
-    key = tuple(getattr(d, f[0]) for f in d._fields_[:-1]) + (backward,)
-    n = _CONV_SCRATCH.get(key)
-    if n is None:
-        n = int(lib.ghn3_conv_scratch_floats(ctypes.byref(d), backward))
-        if n < 0:
-            raise L.Ghn3Error('ghn3_conv_scratch_floats: %s' % lib.ghn3_last_error().decode())
-        _CONV_SCRATCH[key] = n
-    return n
-
-
 class ConvBn(torch.autograd.Function):
     """[ReLU ->] dense kh x kw convolution -> BatchNorm (batch statistics) as ONE autograd node on ghn3_conv_bn_fwd / _bwd
     (round 6: `ReLUConvBN` with a k x k kernel, ops.py:180-198).  Same conventions as DwPwBn: channels_last storage inside,
@@ -225,7 +214,7 @@ class ConvBn(torch.autograd.Function):
         out = torch.empty((d.N, C_out, d.Ho, d.Wo), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
         z = torch.empty_like(out)
         stats = torch.empty(3 * C_out, dtype=torch.float32, device=dev)
-        scratch = torch.empty(_conv_scratch_floats(lib, d, 0), dtype=torch.float32, device=dev)
+        scratch = torch.empty(_scratch_floats('ghn3_conv_scratch_floats', d, 0), dtype=torch.float32, device=dev)
         stream = _stream()
         L._check(lib.ghn3_conv_bn_fwd(ctypes.byref(d), _ptr(xc), _ptr(wc), _ptr(g), _ptr(b), _ptr(z), _ptr(out), _ptr(stats),
                                       _ptr(scratch), stream), 'ghn3_conv_bn_fwd')
@@ -244,7 +233,7 @@ class ConvBn(torch.autograd.Function):
         do = dout.contiguous(memory_format=torch.channels_last)
         dx = torch.empty_like(xc)
         n_par = wc.numel() + 2 * C_out
-        buf = torch.empty((n_par + 63) // 64 * 64 + _conv_scratch_floats(lib, d, 1), dtype=torch.float32, device=dev)
+        buf = torch.empty((n_par + 63) // 64 * 64 + _scratch_floats('ghn3_conv_scratch_floats', d, 1), dtype=torch.float32, device=dev)
         dw = buf[:wc.numel()].view(wc.shape)
         db = buf[wc.numel():wc.numel() + C_out]              # (dbeta directly followed by dgamma: the kernels' own pair of sums)
         dg = buf[wc.numel() + C_out:n_par]
@@ -278,7 +267,7 @@ class ConvOnly(torch.autograd.Function):
         d = _conv_desc(xc, wc, stride, pad, dil, relu, 0.0, no_norm=True)
         z = torch.empty((d.N, int(wc.shape[0]), d.Ho, d.Wo), dtype=torch.float32, device=x.device,
                         memory_format=torch.channels_last)
-        scratch = torch.empty(_conv_scratch_floats(lib, d, 0), dtype=torch.float32, device=x.device)
+        scratch = torch.empty(_scratch_floats('ghn3_conv_scratch_floats', d, 0), dtype=torch.float32, device=x.device)
         stream = _stream()
         L._check(lib.ghn3_conv_bn_fwd(ctypes.byref(d), _ptr(xc), _ptr(wc), None, None, _ptr(z), None, None, _ptr(scratch), stream),
                  'ghn3_conv_bn_fwd')
@@ -295,7 +284,7 @@ class ConvOnly(torch.autograd.Function):
         do = dz.contiguous(memory_format=torch.channels_last)
         dx = torch.empty_like(xc)
         n_par = (wc.numel() + 63) // 64 * 64
-        buf = torch.empty(n_par + _conv_scratch_floats(lib, d, 1), dtype=torch.float32, device=xc.device)
+        buf = torch.empty(n_par + _scratch_floats('ghn3_conv_scratch_floats', d, 1), dtype=torch.float32, device=xc.device)
         dw = buf[:wc.numel()].view(wc.shape)
         stream = _stream()
         L._check(lib.ghn3_conv_bn_bwd(ctypes.byref(d), _ptr(do), _ptr(xc), None, None, _ptr(wc), None, _ptr(dx), _ptr(dw), None,
@@ -683,20 +672,6 @@ def _aligned(t):
     return t if t.data_ptr() % 16 == 0 else t.clone()
 
 
-_MSA_SCRATCH = {}
-
-
-def _msa_scratch_floats(lib, d, backward):
-    key = tuple(getattr(d, f[0]) for f in d._fields_) + (backward,)
-    n = _MSA_SCRATCH.get(key)
-    if n is None:
-        n = int(lib.ghn3_msa_scratch_floats(ctypes.byref(d), backward))
-        if n < 0:
-            raise L.Ghn3Error('ghn3_msa_scratch_floats: %s' % lib.ghn3_last_error().decode())
-        _MSA_SCRATCH[key] = n
-    return n
-
-
 def _no_dropout(m):
     if _is_kind(m, 'Identity'):
         return True
@@ -766,7 +741,7 @@ class MsaLayer(torch.autograd.Function):
         d = _MsaDesc(B, H, W, C, heads, int(ps[8].shape[0]), stride, Ho, Wo, layout, float(eps), int(ps[3] is not None))
         dev = x.device
         out = torch.empty((B, C, Ho, Wo), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
-        scratch = torch.empty(_msa_scratch_floats(lib, d, 0), dtype=torch.float32, device=dev)
+        scratch = torch.empty(_scratch_floats('ghn3_msa_scratch_floats', d, 0), dtype=torch.float32, device=dev)
         # (P and everything the backward reads only when the layer is differentiated)
         P = torch.empty(B * heads * H * W * H * W, dtype=torch.float32, device=dev) if train else None
         L._check(lib.ghn3_msa_fwd(ctypes.byref(d), _ptr(xc), ctypes.byref(_msa_ptrs(ps)), _ptr(out),
@@ -784,7 +759,7 @@ class MsaLayer(torch.autograd.Function):
         do = _aligned(dout.contiguous(memory_format=torch.channels_last))
         dx = torch.empty_like(xc)
         grads = [None if t is None else torch.empty_like(t, memory_format=torch.contiguous_format) for t in ps]
-        bscratch = torch.empty(_msa_scratch_floats(lib, d, 1), dtype=torch.float32, device=xc.device)
+        bscratch = torch.empty(_scratch_floats('ghn3_msa_scratch_floats', d, 1), dtype=torch.float32, device=xc.device)
         L._check(lib.ghn3_msa_bwd(ctypes.byref(d), _ptr(do), _ptr(xc), ctypes.byref(_msa_ptrs(ps)), _ptr(scratch), _ptr(P),
                                   _ptr(dx), ctypes.byref(_msa_ptrs(grads)), _ptr(bscratch), _stream()), 'ghn3_msa_bwd')
         return (dx, None) + tuple(grads)
@@ -841,20 +816,6 @@ def _head_desc(B, C, H, W, layout, glob_avg, dims, ps=()):
     for j, v in enumerate(ps[:HEAD_MAX_LINEAR - 1]):
         d.p[j] = float(v)
     return d
-
-
-_HEAD_SCRATCH = {}
-
-
-def _head_scratch_floats(lib, d, backward):
-    key = (d.B, d.C, d.H, d.W, d.layout, d.glob_avg, tuple(d.dims)[:d.n_lin + 1], backward)
-    n = _HEAD_SCRATCH.get(key)
-    if n is None:
-        n = int(lib.ghn3_head_scratch_floats(ctypes.byref(d), backward))
-        if n < 0:
-            raise L.Ghn3Error('ghn3_head_scratch_floats: %s' % lib.ghn3_last_error().decode())
-        _HEAD_SCRATCH[key] = n
-    return n
 
 
 def head_enabled():
@@ -945,7 +906,7 @@ class ClassifierHead(torch.autograd.Function):
         for j, m in enumerate(masks):
             hp.mask[j] = None if m is None else m.data_ptr()
         logits = torch.empty((B, dims[-1]), dtype=torch.float32, device=x.device)
-        scratch = torch.empty(_head_scratch_floats(lib, d, 0), dtype=torch.float32, device=x.device)
+        scratch = torch.empty(_scratch_floats('ghn3_head_scratch_floats', d, 0), dtype=torch.float32, device=x.device)
         L._check(lib.ghn3_head_fwd(ctypes.byref(d), _ptr(xc), ctypes.byref(hp), _ptr(logits), _ptr(scratch), _stream()),
                  'ghn3_head_fwd')
         if train:
@@ -968,7 +929,7 @@ class ClassifierHead(torch.autograd.Function):
             hg.w[j], hg.b[j] = grads[2 * j].data_ptr(), grads[2 * j + 1].data_ptr()
         for j, m in enumerate(masks):
             hp.mask[j] = None if m is None else m.data_ptr()
-        bscratch = torch.empty(_head_scratch_floats(lib, d, 1), dtype=torch.float32, device=xc.device)
+        bscratch = torch.empty(_scratch_floats('ghn3_head_scratch_floats', d, 1), dtype=torch.float32, device=xc.device)
         L._check(lib.ghn3_head_bwd(ctypes.byref(d), _ptr(do), _ptr(xc), ctypes.byref(hp), _ptr(scratch), _ptr(dx),
                                    ctypes.byref(hg), _ptr(bscratch), _stream()), 'ghn3_head_bwd')
         return (dx, None) + (None,) * (n - 1) + tuple(grads)
