@@ -40,6 +40,9 @@ constexpr int TP = 64;       // pixels per tile (4 waves x 16-row MFMA tiles)
 constexpr int KC = 32;       // reduction chunk = one v_mfma_f32_16x16x32_bf16 k-step
 constexpr int LDK = 40;      // LDS row pitch in 16-bit elements (80 bytes: 16-byte aligned fragments)
 constexpr int MAXT = 49;     // taps (ks <= 7)
+// operand pieces of the kernels templated on NT (16 NT columns per workgroup): three (fp32-equivalent products) up to 256
+// columns, two for the widest tiles (registers)
+constexpr int terms_of(int NT) { return NT <= 16 ? 3 : 2; }
 
 struct Desc {
     int N, H, W, C_in, C_out, ks, stride, pad, dil, Ho, Wo;
@@ -132,11 +135,6 @@ __device__ __forceinline__ void dz8(const float* __restrict__ dout, const float*
         const int cc = c + 4 * h;
         if (cc >= C) break;
         const f32x4 g = *reinterpret_cast<const f32x4*>(dout + (int64_t)p * C + cc);
-        if (!stats) {                                                      // (`dout` IS dz: tnet_dz_kernel ran before)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) out[4 * h + e] = g[e];
-            continue;
-        }
         const f32x4 zz = *reinterpret_cast<const f32x4*>(z + (int64_t)p * C + cc);
         const f32x4 mu = *reinterpret_cast<const f32x4*>(stats + cc), rs = *reinterpret_cast<const f32x4*>(stats + C + cc);
         const f32x4 ga = *reinterpret_cast<const f32x4*>(gamma + cc);
@@ -152,10 +150,11 @@ __device__ __forceinline__ void dz8(const float* __restrict__ dout, const float*
 // ---------------------------------------------------------------------------------------------------------------------
 // forward: z = pw(dw(relu(x))), per-tile channel statistics
 // ---------------------------------------------------------------------------------------------------------------------
-template <int NT, int S>
+template <int NT>
 __global__ __launch_bounds__(256) void tnet_dwpw_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w_dw,
                                                             const float* __restrict__ w_pw, float* __restrict__ z,
                                                             float* __restrict__ part, const Desc d, const int P) {
+    constexpr int S = terms_of(NT);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     int* pix = reinterpret_cast<int*>(smem);                                   // [3][TP]
     float* wt = reinterpret_cast<float*>(smem + 3 * TP * 4);                   // [MAXT][KC]
@@ -349,11 +348,12 @@ __global__ __launch_bounds__(256) void tnet_reduce_rows_kernel(const float* __re
 }
 
 // dy [P][C_in] = dz [P][C_out] W_pw [C_out][C_in]; dz formed on the fly
-template <int NT, int S>
+template <int NT>
 __global__ __launch_bounds__(256) void tnet_dwpw_bwd_data_kernel(const float* __restrict__ dout, const float* __restrict__ z,
                                                                  const float* __restrict__ stats, const float* __restrict__ gamma,
                                                                  const float* __restrict__ s12, const float* __restrict__ w_pw,
                                                                  float* __restrict__ dy, const Desc d, const int P) {
+    constexpr int S = terms_of(NT);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned short* As = reinterpret_cast<unsigned short*>(smem);              // [S][TP][LDK]
     unsigned short* Bs = As + S * TP * LDK;                                    // [S][16 NT][LDK]
@@ -497,8 +497,8 @@ __global__ __launch_bounds__(256) void tnet_dw_bwd_data_kernel(const float* __re
 __global__ __launch_bounds__(256) void tnet_dw_wgrad_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                             float* __restrict__ part, const Desc d, const int P, const int chunk_px) {
     // Threads = (channel quad) x (pixel lane): a thread sums its channels over every PL-th pixel of the chunk for up to TG taps at
-    // a time (registers), the pixel lanes are then added through LDS.  (The first version gave one (tap, channel quad) to a
-    // thread and walked the chunk's 128 pixels in sequence with taps x C / 4 of the 256 threads busy: 108 us per call, 9 ms of
+    // a time (registers), the pixel lanes are then added through LDS.  (One (tap, channel quad) per
+    // thread, walking the chunk's 128 pixels in sequence, keeps taps x C / 4 of the 256 threads busy: 108 us per call, 9 ms of
     // the training loop's 75 ms of GPU time per step.)
     constexpr int TG = 16;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -554,31 +554,24 @@ __global__ __launch_bounds__(256) void tnet_dw_wgrad_kernel(const float* __restr
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Round 6, second slice: the DENSE convolution chain  [ReLU ->] kh x kw convolution (stride, padding, dilation) -> BatchNorm
+// The DENSE convolution chain  [ReLU ->] kh x kw convolution (stride, padding, dilation) -> BatchNorm
 // = `ReLUConvBN` with a k x k kernel (the `conv_3x3 / 5x5 / 7x7` ops, /root/reference/ghn3/ops.py:180-198, 297) and its
 // 1 x k / k x 1 halves.  Implicit GEMM on the same machinery as the depthwise / pointwise family above: a workgroup owns 64
-// output pixels x all output channels, the reduction runs over (tap, 32 input channels) chunks -- the operand chunk of a tap is
-// the (ReLU of the) shifted input pixels, read straight from x; the weights come from a [tap][C_out][C_in] re-pack of the
-// predicted [C_out][C_in][kh][kw] tensor (one small launch: a workgroup's weight chunks are then coalesced rows instead of
-// 4-byte gathers with a stride of kh kw floats) -- split operands with three bf16 pieces, fp32 accumulate, z + per-tile
-// statistics in the epilogue.  Backward: dz on the fly (as above); dx by the transposed implicit GEMM over the taps that read
-// an input pixel; dW per (tap, 64 x 64 block, pixel chunk) partials + fixed-order reduction, written back in the parameter's
-// own [C_out][C_in][kh][kw] order.  The stock path runs these layers as MIOpen implicit-GEMM / Winograd kernels between two
-// layout transposes, ~4 launches forward and ~8 backward per layer, plus ReLU and BatchNorm launches.
+// output pixels x a group of output channels, the reduction runs over (tap, 32 input channels) chunks -- the operand chunk of a
+// tap is the (ReLU of the) shifted input pixels, read straight from x; the weights come as bf16 pieces from a
+// [piece][tap][C_out][C_in] pack of the predicted [C_out][C_in][kh][kw] tensor (one small launch) -- split operands with three
+// bf16 pieces, fp32 accumulate, z + per-tile statistics in the epilogue.  Backward: dz written once (tnet_dz_kernel); dx by the
+// transposed implicit GEMM over the taps that read an input pixel (the same kernel, on the transposed pack); dW per (tap,
+// 64 x 64 block, pixel chunk) partials + fixed-order reduction, written back in the parameter's own [C_out][C_in][kh][kw]
+// order.  The stock path runs these layers as MIOpen implicit-GEMM / Winograd kernels between two layout transposes, ~4
+// launches forward and ~8 backward per layer, plus ReLU and BatchNorm launches.
+// Here: the descriptor and the weight-gradient kernel; tnet_conv_w_pack_kernel, tnet_dz_kernel and tnet_conv2_kernel follow the
+// host side of the depthwise / pointwise family.
 // ---------------------------------------------------------------------------------------------------------------------
 struct CDesc {
     int N, H, W, C_in, C_out, kh, kw, sh, sw, ph, pw, dil, Ho, Wo, relu;
     float eps;
 };
-
-__global__ __launch_bounds__(256) void tnet_conv_w_repack_kernel(const float* __restrict__ w, float* __restrict__ w_r, int C_out,
-                                                                 int C_in, int taps) {
-    const int64_t total = (int64_t)C_out * C_in * taps, cc = (int64_t)C_out * C_in;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int64_t t = i / cc, r = i - t * cc;                      // r = co * C_in + ci
-        w_r[i] = w[r * taps + t];
-    }
-}
 
 // (relu of) 8 consecutive channels c .. c + 7 of input pixel (n, ih, iw); zeros outside the image / beyond C_in
 __device__ __forceinline__ void conv_in8(const float* __restrict__ x, const CDesc& d, int n, int ih, int iw, int c, float (&out)[8]) {
@@ -595,190 +588,26 @@ __device__ __forceinline__ void conv_in8(const float* __restrict__ x, const CDes
     }
 }
 
-template <int NT, int S>
-__global__ __launch_bounds__(256) void tnet_conv_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w_r,
-                                                            float* __restrict__ z, float* __restrict__ part, const CDesc d, const int P) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    int* pix = reinterpret_cast<int*>(smem);                                   // [3][TP]
-    unsigned short* As = reinterpret_cast<unsigned short*>(smem + 3 * TP * 4);                       // [S][TP][LDK]
-    unsigned short* Bs = As + S * TP * LDK;                                                          // [S][16 NT][LDK]
-    float* red = reinterpret_cast<float*>(Bs + S * 16 * NT * LDK);             // [5][16 NT]
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r16 = lane & 15, kc = lane >> 4;
-    const int tile = blockIdx.x, p0 = tile * TP, taps = d.kh * d.kw;
-    if (tid < TP) {
-        const int p = p0 + tid;
-        int n = -1, ih0 = 0, iw0 = 0;
-        if (p < P) {
-            const int hw = d.Ho * d.Wo;
-            n = p / hw;
-            const int r = p - n * hw, oh = r / d.Wo, ow = r - oh * d.Wo;
-            ih0 = oh * d.sh - d.ph;
-            iw0 = ow * d.sw - d.pw;
-        }
-        pix[tid] = n; pix[TP + tid] = ih0; pix[2 * TP + tid] = iw0;
-    }
-    f32x4 acc[NT];
+// 8 consecutive channels c .. c + 7 of row p of dz [P][C]; zeros for p >= P and for channels at or beyond C
+__device__ __forceinline__ void dz_in8(const float* __restrict__ dz, int C, int p, int P, int c, float (&out)[8]) {
 #pragma unroll
-    for (int j = 0; j < NT; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int t = 0; t < taps; ++t) {
-        const int dh = (t / d.kw) * d.dil, dw_ = (t % d.kw) * d.dil;
-        const float* wt = w_r + (int64_t)t * d.C_out * d.C_in;
-        for (int c0 = 0; c0 < d.C_in; c0 += KC) {
-            __syncthreads();                                                   // (previous chunk's fragments are consumed; pix is written)
-            for (int i = tid; i < 16 * NT * 8; i += 256) {
-                const int n = i >> 3, k = (i & 7) * 4, c = c0 + k;
-                f32x4 v = {0.f, 0.f, 0.f, 0.f};
-                if (n < d.C_out && c < d.C_in) v = *reinterpret_cast<const f32x4*>(wt + (int64_t)n * d.C_in + c);
+    for (int e = 0; e < 8; ++e) out[e] = 0.f;
+    if (p >= P) return;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) splitS<S>(v[e], Bs, n * LDK + k + e, 16 * NT * LDK);
-            }
-            {
-                const int i = tid >> 2, cc = (tid & 3) * 8;
-                float y[8];
-                conv_in8(x, d, pix[i], pix[TP + i] + dh, pix[2 * TP + i] + dw_, c0 + cc, y);
+    for (int h = 0; h < 2; ++h) {
+        const int cc = c + 4 * h;
+        if (cc >= C) break;
+        const f32x4 g = *reinterpret_cast<const f32x4*>(dz + (int64_t)p * C + cc);
 #pragma unroll
-                for (int e = 0; e < 8; ++e) splitS<S>(y[e], As, i * LDK + cc + e, TP * LDK);
-            }
-            __syncthreads();
-            u16x8 af[S];
-#pragma unroll
-            for (int q = 0; q < S; ++q) af[q] = frag(As + q * TP * LDK, 16 * w + r16, kc);
-#pragma unroll
-            for (int j = 0; j < NT; ++j) {
-                if (16 * j < d.C_out) {
-                    u16x8 bf[S];
-#pragma unroll
-                    for (int q = 0; q < S; ++q) bf[q] = frag(Bs + q * 16 * NT * LDK, 16 * j + r16, kc);
-                    acc[j] = mma_terms<S>(af, bf, acc[j]);
-                }
-            }
-        }
-    }
-    // ---- epilogue: z, then per-tile (mean, M2) of every channel (as tnet_dwpw_fwd_kernel)
-    const int prow = p0 + 16 * w + r16;
-    const bool valid = prow < P;
-    const int cnt = min(TP, P - p0);
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-        const int col = 16 * j + 4 * kc;
-        if (valid && col < d.C_out) *reinterpret_cast<f32x4*>(z + (int64_t)prow * d.C_out + col) = acc[j];
-    }
-    auto tile_sum = [&](bool centred) {
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            const int col = 16 * j + 4 * kc;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float v = 0.f;
-                if (valid) { v = acc[j][e]; if (centred) { v -= red[4 * 16 * NT + col + e]; v *= v; } }
-                v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64); v += __shfl_xor(v, 8, 64);
-                if (r16 == 0) red[w * 16 * NT + col + e] = v;
-            }
-        }
-        __syncthreads();
-    };
-    tile_sum(false);
-    for (int c = tid; c < 16 * NT; c += 256)
-        red[4 * 16 * NT + c] = (red[c] + red[16 * NT + c] + red[2 * 16 * NT + c] + red[3 * 16 * NT + c]) / (float)cnt;
-    tile_sum(true);
-    for (int c = tid; c < d.C_out; c += 256) {
-        part[((int64_t)tile * 2) * d.C_out + c] = red[4 * 16 * NT + c];
-        part[((int64_t)tile * 2 + 1) * d.C_out + c] = red[c] + red[16 * NT + c] + red[2 * 16 * NT + c] + red[3 * 16 * NT + c];
-    }
-}
-
-// dx [P_in][C_in] = relu'(x) . sum over taps of dz[output pixel that reads this input through the tap][C_out] W_tap [C_out][C_in]
-template <int NT, int S>
-__global__ __launch_bounds__(256) void tnet_conv_bwd_data_kernel(const float* __restrict__ dout, const float* __restrict__ z,
-                                                                 const float* __restrict__ stats, const float* __restrict__ gamma,
-                                                                 const float* __restrict__ s12, const float* __restrict__ w_r,
-                                                                 const float* __restrict__ x, float* __restrict__ dx, const CDesc d,
-                                                                 const int P_out, const int P_in) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    int* pix = reinterpret_cast<int*>(smem);                                   // [3][TP]: n, ih + ph, iw + pw of the input pixels
-    unsigned short* As = reinterpret_cast<unsigned short*>(smem + 3 * TP * 4);                       // [S][TP][LDK]
-    unsigned short* Bs = As + S * TP * LDK;                                                          // [S][16 NT][LDK]
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r16 = lane & 15, kc = lane >> 4;
-    const int p0 = blockIdx.x * TP, taps = d.kh * d.kw;
-    if (tid < TP) {
-        const int p = p0 + tid;
-        int n = -1, a = 0, b = 0;
-        if (p < P_in) {
-            const int hw = d.H * d.W;
-            n = p / hw;
-            const int r = p - n * hw, ih = r / d.W, iw = r - ih * d.W;
-            a = ih + d.ph; b = iw + d.pw;
-        }
-        pix[tid] = n; pix[TP + tid] = a; pix[2 * TP + tid] = b;
-    }
-    f32x4 acc[NT];
-#pragma unroll
-    for (int j = 0; j < NT; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int t = 0; t < taps; ++t) {
-        const int dh = (t / d.kw) * d.dil, dw_ = (t % d.kw) * d.dil;
-        const float* wt = w_r + (int64_t)t * d.C_out * d.C_in;
-        for (int c0 = 0; c0 < d.C_out; c0 += KC) {
-            __syncthreads();
-            {   // A[i][k] = dz[output pixel of (input pixel i, tap t)][c0 + k]
-                const int i = tid >> 2, cc = (tid & 3) * 8;
-                const int n = pix[i], th = pix[TP + i] - dh, tw = pix[2 * TP + i] - dw_;
-                int po = P_out;                                                // (no such output pixel: zeros)
-                if (n >= 0 && th >= 0 && tw >= 0 && th % d.sh == 0 && tw % d.sw == 0) {
-                    const int oh = th / d.sh, ow = tw / d.sw;
-                    if (oh < d.Ho && ow < d.Wo) po = (n * d.Ho + oh) * d.Wo + ow;
-                }
-                float v[8];
-                dz8(dout, z, stats, gamma, s12, d.C_out, po, P_out, c0 + cc, v);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) splitS<S>(v[e], As, i * LDK + cc + e, TP * LDK);
-            }
-            // B[n = ci][k] = W_tap[c0 + k][n]
-            for (int i = tid; i < KC * 4 * NT; i += 256) {
-                const int k = i / (4 * NT), n = (i % (4 * NT)) * 4, co = c0 + k;
-                f32x4 v = {0.f, 0.f, 0.f, 0.f};
-                if (co < d.C_out && n < d.C_in) v = *reinterpret_cast<const f32x4*>(wt + (int64_t)co * d.C_in + n);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) splitS<S>(v[e], Bs, (n + e) * LDK + k, 16 * NT * LDK);
-            }
-            __syncthreads();
-            u16x8 af[S];
-#pragma unroll
-            for (int q = 0; q < S; ++q) af[q] = frag(As + q * TP * LDK, 16 * w + r16, kc);
-#pragma unroll
-            for (int j = 0; j < NT; ++j) {
-                if (16 * j < d.C_in) {
-                    u16x8 bf[S];
-#pragma unroll
-                    for (int q = 0; q < S; ++q) bf[q] = frag(Bs + q * 16 * NT * LDK, 16 * j + r16, kc);
-                    acc[j] = mma_terms<S>(af, bf, acc[j]);
-                }
-            }
-        }
-    }
-    const int prow = p0 + 16 * w + r16;
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-        const int col = 16 * j + 4 * kc;
-        if (prow < P_in && col < d.C_in) {
-            f32x4 v = acc[j];
-            if (d.relu) {
-                const f32x4 xv = *reinterpret_cast<const f32x4*>(x + (int64_t)prow * d.C_in + col);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = xv[e] > 0.f ? v[e] : 0.f;
-            }
-            *reinterpret_cast<f32x4*>(dx + (int64_t)prow * d.C_in + col) = v;
-        }
+        for (int e = 0; e < 4; ++e) out[4 * h + e] = g[e];
     }
 }
 
 // part[chunk][t][co][ci] = sum over the chunk's output pixels of dz[p][co] act(x[tap t of p][ci]); workgroup = (chunk, 64 co, (t, 64 ci))
-__global__ __launch_bounds__(256) void tnet_conv_wgrad_kernel(const float* __restrict__ dout, const float* __restrict__ z,
-                                                              const float* __restrict__ stats, const float* __restrict__ gamma,
-                                                              const float* __restrict__ s12, const float* __restrict__ x,
+__global__ __launch_bounds__(256) void tnet_conv_wgrad_kernel(const float* __restrict__ dz, const float* __restrict__ x,
                                                               float* __restrict__ part, const CDesc d, const int P, const int chunk_px) {
-    // (round 6, second version: the loads of pixel step k + 1 are in flight during the products of step k -- registers -> the
-    // other LDS stage, one barrier per step; the first version loaded, cut and multiplied in sequence with two barriers)
+    // (the loads of pixel step k + 1 are in flight during the products of step k: registers -> the other LDS stage, one barrier
+    // per step)
     constexpr int S = 3;
     constexpr int STAGE = S * 64 * LDK;
     __shared__ __attribute__((aligned(16))) unsigned short As[2 * STAGE], Bs[2 * STAGE];
@@ -790,7 +619,7 @@ __global__ __launch_bounds__(256) void tnet_conv_wgrad_kernel(const float* __res
     // Thread = (pixel k of the step, 8 consecutive channels m8 ..): lanes of a wave hold 32 consecutive pixels of two channel
     // groups.  The operands need the pixel index along k, i.e. a transposition on the way into LDS: neighbouring lanes (pixels
     // k, k + 1) exchange halves so that every lane writes 32-bit words (two pixels of one channel) -- 12 conflict-free stores per
-    // operand instead of 24 two-byte ones that collided four ways (the first version's layout: 118 us per call).
+    // operand instead of 24 two-byte ones that collided four ways (two-byte stores: 118 us per call).
     const int k = tid & 31, m8 = (tid >> 5) * 8;
     float va[8], vb[8];
     auto put = [&](const float (&v)[8], unsigned short* base) {
@@ -817,7 +646,7 @@ __global__ __launch_bounds__(256) void tnet_conv_wgrad_kernel(const float* __res
     };
     auto fetch = [&](int pk) {
         const int p = pk + k;
-        dz8(dout, z, stats, gamma, s12, d.C_out, p < pb ? p : P, P, co0 + m8, va);       // A[m = co][k = pixel]
+        dz_in8(dz, d.C_out, p < pb ? p : P, P, co0 + m8, va);                            // A[m = co][k = pixel]
         int n = -1, ih = 0, iw = 0;                                                      // B[n = ci][k = pixel]: act(x) at the tap's input pixel
         if (p < pb) {
             n = p / hw;
@@ -866,12 +695,6 @@ __global__ __launch_bounds__(256) void tnet_conv_wgrad_kernel(const float* __res
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
 inline int nt_of(int C) { return C <= 64 ? 4 : C <= 128 ? 8 : C <= 256 ? 16 : 32; }
-// operand pieces: three (fp32-equivalent products) up to 256 output columns per workgroup, two for the widest tiles (registers)
-// (GHN3_TNET_TERMS=2: two pieces everywhere -- three products, ~1e-5 -- for the A/B of profiles/r06y_*)
-inline int terms_of(int NT) {
-    static const int small = getenv("GHN3_TNET_TERMS") ? atoi(getenv("GHN3_TNET_TERMS")) : 3;
-    return NT <= 16 ? (small == 2 ? 2 : 3) : 2;
-}
 inline size_t fwd_lds(int NT) { const int S = terms_of(NT); return 3 * TP * 4 + MAXT * KC * 4 + S * TP * LDK * 2 + S * 16 * NT * LDK * 2 + 5 * 16 * NT * 4; }
 inline size_t bwd_lds(int NT) { const int S = terms_of(NT); return S * TP * LDK * 2 + S * 16 * NT * LDK * 2; }
 
@@ -938,9 +761,9 @@ extern "C" int ghn3_dwpw_bn_fwd(const ghn3_dwpw_desc* g, const float* x, const f
     const Plan pl = make_plan(d);
     const int NT = nt_of(d.C_out);
     const size_t lds = fwd_lds(NT);
-#define FWD_CASE(n, t) case 10 * n + t: rc = tnet_raise_lds(tnet_dwpw_fwd_kernel<n, t>, lds); if (rc) return rc; \
-        hipLaunchKernelGGL((tnet_dwpw_fwd_kernel<n, t>), dim3(pl.n_tiles), dim3(256), lds, s, x, w_dw, w_pw, z, scratch, d, pl.P); break;
-    switch (10 * NT + terms_of(NT)) { FWD_CASE(4, 3) FWD_CASE(8, 3) FWD_CASE(16, 3) FWD_CASE(4, 2) FWD_CASE(8, 2) FWD_CASE(16, 2) FWD_CASE(32, 2) }
+#define FWD_CASE(n) case n: rc = tnet_raise_lds(tnet_dwpw_fwd_kernel<n>, lds); if (rc) return rc; \
+        hipLaunchKernelGGL((tnet_dwpw_fwd_kernel<n>), dim3(pl.n_tiles), dim3(256), lds, s, x, w_dw, w_pw, z, scratch, d, pl.P); break;
+    switch (NT) { FWD_CASE(4) FWD_CASE(8) FWD_CASE(16) FWD_CASE(32) }
 #undef FWD_CASE
     TNET_LAUNCH_CHECK("dwpw fwd")
     hipLaunchKernelGGL(tnet_bn_finalize_kernel, dim3((d.C_out + 15) / 16), dim3(256), 0, s, scratch, pl.n_tiles, pl.P, d.C_out, d.eps, stats);
@@ -992,9 +815,9 @@ extern "C" int ghn3_dwpw_bn_bwd(const ghn3_dwpw_desc* g, const float* dout, cons
     {
         const int NT = nt_of(d.C_in);
         const size_t lds = bwd_lds(NT);
-#define BWD_CASE(n, t) case 10 * n + t: rc = tnet_raise_lds(tnet_dwpw_bwd_data_kernel<n, t>, lds); if (rc) return rc; \
-        hipLaunchKernelGGL((tnet_dwpw_bwd_data_kernel<n, t>), dim3(pl.n_tiles), dim3(256), lds, s, dout, z, stats, gamma, s12, w_pw, dy, d, pl.P); break;
-        switch (10 * NT + terms_of(NT)) { BWD_CASE(4, 3) BWD_CASE(8, 3) BWD_CASE(16, 3) BWD_CASE(4, 2) BWD_CASE(8, 2) BWD_CASE(16, 2) BWD_CASE(32, 2) }
+#define BWD_CASE(n) case n: rc = tnet_raise_lds(tnet_dwpw_bwd_data_kernel<n>, lds); if (rc) return rc; \
+        hipLaunchKernelGGL((tnet_dwpw_bwd_data_kernel<n>), dim3(pl.n_tiles), dim3(256), lds, s, dout, z, stats, gamma, s12, w_pw, dy, d, pl.P); break;
+        switch (NT) { BWD_CASE(4) BWD_CASE(8) BWD_CASE(16) BWD_CASE(32) }
 #undef BWD_CASE
         TNET_LAUNCH_CHECK("dwpw bwd data")
     }
@@ -1027,18 +850,18 @@ extern "C" int ghn3_dwpw_bn_bwd(const ghn3_dwpw_desc* g, const float* dout, cons
     return GHN3_OK;
 }
 
-// ---- dense convolution family (round 6) ---------------------------------------------------------------------------------
+// ---- dense convolution family: the forward / input-gradient kernel and the host side -------------------------------------------
 namespace {
 
 // ---------------------------------------------------------------------------------------------------------------------
-// dense convolution, second version (round 6): the same implicit GEMM and the same three bf16 pieces per operand, but
-//  * the weight pieces are cut ONCE per call (tnet_conv_w_pack_kernel: [piece][tap][row][k], k padded to the chunk) instead of by
-//    every workgroup in every chunk, so the B tile is a plain 16-byte copy;
+// The implicit GEMM of the dense convolution, three bf16 pieces per operand:
+//  * the weight pieces are cut ONCE per call (tnet_conv_w_pack_kernel: [piece][tap][row][k], k padded to the chunk), so the B tile
+//    of a chunk is a plain 16-byte copy;
 //  * the output columns are split over blockIdx.y (NT <= 8 fragments per workgroup): the small-image / wide-layer shapes of the
 //    search space (4 x 4 x 256 channels: 16 pixel tiles) fill the chip;
 //  * global loads of chunk i + 1 are in flight during the matrix products of chunk i (registers -> the other LDS buffer: one
 //    barrier per chunk), the A pieces are stored as 16-byte vectors;
-//  * the backward reads dz from a buffer written once (tnet_dz_kernel) instead of re-deriving it per tap.
+//  * the backward reads dz from a buffer written once (tnet_dz_kernel).
 // BWD = false: dst = z[P_dst = output pixels][R = C_out] from src = x;  BWD = true: dst = dx[input pixels][R = C_in] from src = dz.
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void tnet_conv_w_pack_kernel(const float* __restrict__ w, unsigned short* __restrict__ wp, int C_out,
@@ -1224,7 +1047,7 @@ __global__ __launch_bounds__(256) void tnet_conv2_kernel(const float* __restrict
         }
     }
     if (BWD) return;
-    // ---- forward: per-tile (mean, M2) of every channel of this column group (as tnet_conv_fwd_kernel)
+    // ---- forward: per-tile (mean, M2) of every channel of this column group (as tnet_dwpw_fwd_kernel)
     const int cnt = min(TP, P_dst - p0);
     auto tile_sum = [&](bool centred) {
         __syncthreads();
@@ -1270,11 +1093,6 @@ CPlan make_cplan(const CDesc& d) {
     return pl;
 }
 
-inline bool conv2_on() {
-    static const bool on = !(getenv("GHN3_TNET_CONV2") && atoi(getenv("GHN3_TNET_CONV2")) == 0);
-    return on;
-}
-
 int check_cdesc(const ghn3_conv_desc* g, CDesc& d) {
     if (!g) { ghn3_set_error("conv: null descriptor"); return GHN3_E_ARG; }
     d = CDesc{g->N, g->H, g->W, g->C_in, g->C_out, g->kh, g->kw, g->stride_h, g->stride_w, g->pad_h, g->pad_w, g->dil, g->Ho, g->Wo,
@@ -1284,10 +1102,10 @@ int check_cdesc(const ghn3_conv_desc* g, CDesc& d) {
         ghn3_set_error("conv: non-positive size in the descriptor");
         return GHN3_E_ARG;
     }
-    // (the second-version kernels walk C_in in chunks and split it over blockIdx.y in the backward: wide inputs are fine)
-    if ((d.C_in & 3) || (d.C_out & 3) || d.C_in > (conv2_on() ? 4096 : 512) || d.C_out > 512 || d.kh > 7 || d.kw > 7) {
-        ghn3_set_error("conv: needs C_in, C_out multiples of 4, C_out <= 512, C_in <= 4096 (512 with GHN3_TNET_CONV2=0), kernel <= 7 x 7 "
-                       "(got %d -> %d, %d x %d)", d.C_in, d.C_out, d.kh, d.kw);
+    // (tnet_conv2_kernel walks C_in in chunks and splits it over blockIdx.y in the backward: wide inputs are fine)
+    if ((d.C_in & 3) || (d.C_out & 3) || d.C_in > 4096 || d.C_out > 512 || d.kh > 7 || d.kw > 7) {
+        ghn3_set_error("conv: needs C_in, C_out multiples of 4, C_out <= 512, C_in <= 4096, kernel <= 7 x 7 (got %d -> %d, %d x %d)",
+                       d.C_in, d.C_out, d.kh, d.kw);
         return GHN3_E_LIMIT;
     }
     const int ho = (d.H + 2 * d.ph - d.dil * (d.kh - 1) - 1) / d.sh + 1, wo = (d.W + 2 * d.pw - d.dil * (d.kw - 1) - 1) / d.sw + 1;
@@ -1303,22 +1121,9 @@ int check_cdesc(const ghn3_conv_desc* g, CDesc& d) {
     return GHN3_OK;
 }
 
-inline size_t cfwd_lds(int NT) { const int S = terms_of(NT); return 3 * TP * 4 + S * TP * LDK * 2 + S * 16 * NT * LDK * 2 + 5 * 16 * NT * 4; }
-inline size_t cbwd_lds(int NT) { const int S = terms_of(NT); return 3 * TP * 4 + S * TP * LDK * 2 + S * 16 * NT * LDK * 2; }
-
-int conv_repack(const CDesc& d, const CPlan& pl, const float* w, float* w_r, hipStream_t s) {
-    const int64_t total = (int64_t)d.C_out * d.C_in * pl.taps;
-    hipLaunchKernelGGL(tnet_conv_w_repack_kernel, dim3((int)std::min<int64_t>((total + 255) / 256, 2048)), dim3(256), 0, s, w, w_r, d.C_out,
-                       d.C_in, pl.taps);
-    TNET_LAUNCH_CHECK("conv weight repack")
-    return GHN3_OK;
-}
-
-}  // namespace
-
-// 16-bit weight pieces of the second-version kernels, in floats: [3][taps][rows][k padded to the chunk]
+// 16-bit weight pieces, in floats: [3][taps][rows][k padded to the chunk]
 inline int64_t pack_floats(int taps, int rows, int k) { return (((int64_t)3 * taps * rows * ((k + KC - 1) / KC * KC) + 1) / 2 + 3) / 4 * 4; }
-// columns per workgroup of the second-version kernels: as wide as possible while the grid still covers the chip
+// columns per workgroup of tnet_conv2_kernel: as wide as possible while the grid still covers the chip
 inline int conv2_nt(int tiles, int cols) {
     int nt = cols <= 32 ? 2 : cols <= 64 ? 4 : 8;
     while (nt > 2 && (int64_t)tiles * ((cols + 16 * nt - 1) / (16 * nt)) < 256) nt >>= 1;
@@ -1326,19 +1131,34 @@ inline int conv2_nt(int tiles, int cols) {
 }
 inline size_t conv2_lds(int NT) { return 3 * TP * 4 + 2 * (3 * TP * LDK + 3 * 16 * NT * LDK) * 2; }
 
+// The scratch buffer of the conv op: where each area starts, in floats (every area a multiple of four), and the size the caller
+// allocates.  Forward: part, wp.  Backward: all of them; wp holds the transposed pack.
+struct CScratch { int64_t part, s12, wp, part_w, dz, total; };
+
+CScratch conv_scratch(const CDesc& d, const CPlan& pl, bool backward) {
+    CScratch sc = {};
+    int64_t at = 0;
+    auto take = [&at](int64_t n) { const int64_t o = at; at += n; return o; };
+    sc.part = take((int64_t)pl.n_tiles * 2 * d.C_out);             // per tile: (mean, M2) forward, (sum dout, sum dout xhat) backward
+    if (!backward) {
+        sc.wp = take(pack_floats(pl.taps, d.C_out, d.C_in));
+        sc.total = at + 64;
+        return sc;
+    }
+    sc.s12 = take(2 * d.C_out);                                    // the reduced pair, when dbeta / dgamma cannot take it in place
+    sc.wp = take(pack_floats(pl.taps, d.C_in, d.C_out));
+    sc.part_w = take((int64_t)pl.w_chunks * pl.taps * d.C_out * d.C_in);
+    sc.dz = take((int64_t)pl.P * d.C_out);
+    sc.total = at + 256;
+    return sc;
+}
+
+}  // namespace
+
 extern "C" int64_t ghn3_conv_scratch_floats(const ghn3_conv_desc* g, int backward) {
     CDesc d;
     if (check_cdesc(g, d)) return -1;
-    const CPlan pl = make_cplan(d);
-    const int64_t wr = (int64_t)pl.taps * d.C_out * d.C_in;
-    if (!backward) return (int64_t)pl.n_tiles * 2 * d.C_out + std::max(wr, pack_floats(pl.taps, d.C_out, d.C_in)) + 64;
-    return (int64_t)pl.n_tiles * 2 * d.C_out + 2 * d.C_out + std::max(wr, pack_floats(pl.taps, d.C_in, d.C_out)) + (int64_t)pl.w_chunks * wr + 256 +
-           3 * (int64_t)d.C_out + (int64_t)pl.P * d.C_out;
-}
-
-// mean 0 | 1 / std 1 | gamma 1: with these and zero sums dz8() passes the upstream gradient through (GHN3_CONV_NO_NORM)
-__global__ __launch_bounds__(256) void tnet_identity_norm_kernel(float* __restrict__ p, int C) {
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < 3 * C; i += gridDim.x * 256) p[i] = i < C ? 0.f : 1.f;
+    return conv_scratch(d, make_cplan(d), backward != 0).total;
 }
 
 extern "C" int ghn3_conv_bn_fwd(const ghn3_conv_desc* g, const float* x, const float* w, const float* gamma, const float* beta, float* z,
@@ -1353,33 +1173,21 @@ extern "C" int ghn3_conv_bn_fwd(const ghn3_conv_desc* g, const float* x, const f
     }
     hipStream_t s = (hipStream_t)stream_;
     const CPlan pl = make_cplan(d);
-    float* part = scratch;
-    float* w_r = part + (int64_t)pl.n_tiles * 2 * d.C_out;
-    if (conv2_on()) {
-        unsigned short* wp = reinterpret_cast<unsigned short*>(w_r);
-        const int64_t plane = (int64_t)pl.taps * d.C_out * ((d.C_in + KC - 1) / KC * KC);
-        hipLaunchKernelGGL(tnet_conv_w_pack_kernel, dim3((int)std::min<int64_t>((plane + 255) / 256, 2048)), dim3(256), 0, s, w, wp, d.C_out,
-                           d.C_in, pl.taps, 0);
-        TNET_LAUNCH_CHECK("conv weight pack")
-        const int NT = conv2_nt(pl.n_tiles, d.C_out);
-        const dim3 grid(pl.n_tiles, (d.C_out + 16 * NT - 1) / (16 * NT));
-        const size_t lds = conv2_lds(NT);
+    const CScratch sc = conv_scratch(d, pl, false);
+    float* part = scratch + sc.part;
+    unsigned short* wp = reinterpret_cast<unsigned short*>(scratch + sc.wp);
+    const int64_t plane = (int64_t)pl.taps * d.C_out * ((d.C_in + KC - 1) / KC * KC);
+    hipLaunchKernelGGL(tnet_conv_w_pack_kernel, dim3((int)std::min<int64_t>((plane + 255) / 256, 2048)), dim3(256), 0, s, w, wp, d.C_out,
+                       d.C_in, pl.taps, 0);
+    TNET_LAUNCH_CHECK("conv weight pack")
+    const int NT = conv2_nt(pl.n_tiles, d.C_out);
+    const dim3 grid(pl.n_tiles, (d.C_out + 16 * NT - 1) / (16 * NT));
+    const size_t lds = conv2_lds(NT);
 #define C2F_CASE(n) case n: rc = tnet_raise_lds(tnet_conv2_kernel<n, false>, lds); if (rc) return rc; \
-        hipLaunchKernelGGL((tnet_conv2_kernel<n, false>), grid, dim3(256), lds, s, x, wp, z, part, (const float*)nullptr, d, pl.P, pl.P_in); break;
-        switch (NT) { C2F_CASE(2) C2F_CASE(4) C2F_CASE(8) }
+    hipLaunchKernelGGL((tnet_conv2_kernel<n, false>), grid, dim3(256), lds, s, x, wp, z, part, (const float*)nullptr, d, pl.P, pl.P_in); break;
+    switch (NT) { C2F_CASE(2) C2F_CASE(4) C2F_CASE(8) }
 #undef C2F_CASE
-        TNET_LAUNCH_CHECK("conv fwd")
-    } else {
-    rc = conv_repack(d, pl, w, w_r, s);
-    if (rc) return rc;
-    const int NT = nt_of(d.C_out);
-    const size_t lds = cfwd_lds(NT);
-#define CFWD_CASE(n, t) case 10 * n + t: rc = tnet_raise_lds(tnet_conv_fwd_kernel<n, t>, lds); if (rc) return rc; \
-        hipLaunchKernelGGL((tnet_conv_fwd_kernel<n, t>), dim3(pl.n_tiles), dim3(256), lds, s, x, w_r, z, part, d, pl.P); break;
-    switch (10 * NT + terms_of(NT)) { CFWD_CASE(4, 3) CFWD_CASE(8, 3) CFWD_CASE(16, 3) CFWD_CASE(4, 2) CFWD_CASE(8, 2) CFWD_CASE(16, 2) CFWD_CASE(32, 2) }
-#undef CFWD_CASE
     TNET_LAUNCH_CHECK("conv fwd")
-    }
     if (no_norm) return GHN3_OK;
     hipLaunchKernelGGL(tnet_bn_finalize_kernel, dim3((d.C_out + 15) / 16), dim3(256), 0, s, part, pl.n_tiles, pl.P, d.C_out, d.eps, stats);
     TNET_LAUNCH_CHECK("bn finalize")
@@ -1403,29 +1211,15 @@ extern "C" int ghn3_conv_bn_bwd(const ghn3_conv_desc* g, const float* dout, cons
     }
     hipStream_t s = (hipStream_t)stream_;
     const CPlan pl = make_cplan(d);
+    const CScratch sc = conv_scratch(d, pl, true);
     const int64_t wr = (int64_t)pl.taps * d.C_out * d.C_in;
-    float* part12 = scratch;
-    float* const s12_scratch = part12 + (int64_t)pl.n_tiles * 2 * d.C_out;
-    // (dbeta directly followed by dgamma -- how target_ops.py lays them out -- IS the [sum dout | sum dout xhat] pair: no copies)
-    const bool s12_in_place = dbeta && dgamma == dbeta + d.C_out;
-    float* s12 = s12_in_place ? dbeta : s12_scratch;
-    float* w_r = s12_scratch + 2 * d.C_out;
-    float* part_w = w_r + std::max(wr, pack_floats(pl.taps, d.C_in, d.C_out));
-    float* ident = part_w + (int64_t)pl.w_chunks * wr;             // [mean 0 | 1 / std 1 | gamma 1]
-    float* dzbuf = ident + 3 * d.C_out;                            // [P][C_out]: dz, written once (second-version kernels)
-    const bool v2 = conv2_on();
-    if (no_norm && v2) {
-        // (dout is dz: nothing to prepare)
-    } else if (no_norm) {
-        hipLaunchKernelGGL(tnet_identity_norm_kernel, dim3(1), dim3(256), 0, s, ident, d.C_out);
-        TNET_LAUNCH_CHECK("conv bwd identity")
-        if (hipMemsetAsync(s12, 0, (size_t)2 * d.C_out * 4, s) != hipSuccess) { ghn3_set_error("conv bwd: memset failed"); return GHN3_E_HIP; }
-        z = dout;                                                  // (read, multiplied by the zero sums)
-        stats = ident;
-        gamma = ident + 2 * d.C_out;
-    } else
-    // 1. dgamma / dbeta
-    {
+    const float* dz = dout;
+    if (!no_norm) {
+        // 1. dgamma / dbeta
+        float* part12 = scratch + sc.part;
+        // (dbeta directly followed by dgamma -- how target_ops.py lays them out -- IS the [sum dout | sum dout xhat] pair: no copies)
+        const bool s12_in_place = dgamma == dbeta + d.C_out;
+        float* s12 = s12_in_place ? dbeta : scratch + sc.s12;
         const int nq = d.C_out / 4, ng = std::max(1, 256 / nq);
         hipLaunchKernelGGL(tnet_bn_bwd_partial_kernel, dim3(pl.n_tiles), dim3(256), (size_t)ng * 2 * d.C_out * 4, s, dout, z, stats, part12,
                            pl.P, d.C_out);
@@ -1437,53 +1231,31 @@ extern "C" int ghn3_conv_bn_bwd(const ghn3_conv_desc* g, const float* dout, cons
             hipMemcpyAsync(dbeta, s12, (size_t)d.C_out * 4, hipMemcpyDeviceToDevice, s);
             hipMemcpyAsync(dgamma, s12 + d.C_out, (size_t)d.C_out * 4, hipMemcpyDeviceToDevice, s);
         }
+        // 2. dz [P][C_out], written once for the two kernels that read it
+        const int64_t total4 = (int64_t)pl.P * d.C_out / 4;
+        hipLaunchKernelGGL(tnet_dz_kernel, dim3((int)std::min<int64_t>((total4 + 255) / 256, 4096)), dim3(256), 0, s, dout, z, stats, gamma,
+                           s12, scratch + sc.dz, total4, d.C_out, pl.P);
+        TNET_LAUNCH_CHECK("conv bwd dz")
+        dz = scratch + sc.dz;
     }
-    if (v2) {
-        const float* dzp = dout;
-        if (!no_norm) {
-            const int64_t total4 = (int64_t)pl.P * d.C_out / 4;
-            hipLaunchKernelGGL(tnet_dz_kernel, dim3((int)std::min<int64_t>((total4 + 255) / 256, 4096)), dim3(256), 0, s, dout, z, stats, gamma,
-                               s12, dzbuf, total4, d.C_out, pl.P);
-            TNET_LAUNCH_CHECK("conv bwd dz")
-            dzp = dzbuf;
-        }
-        unsigned short* wp = reinterpret_cast<unsigned short*>(w_r);
-        const int64_t plane = (int64_t)pl.taps * d.C_in * ((d.C_out + KC - 1) / KC * KC);
-        hipLaunchKernelGGL(tnet_conv_w_pack_kernel, dim3((int)std::min<int64_t>((plane + 255) / 256, 2048)), dim3(256), 0, s, w, wp, d.C_out,
-                           d.C_in, pl.taps, 1);
-        TNET_LAUNCH_CHECK("conv weight pack (transposed)")
-        const int NT = conv2_nt(pl.n_tiles_in, d.C_in);
-        const dim3 grid(pl.n_tiles_in, (d.C_in + 16 * NT - 1) / (16 * NT));
-        const size_t lds = conv2_lds(NT);
+    // 3. dx
+    unsigned short* wp = reinterpret_cast<unsigned short*>(scratch + sc.wp);
+    const int64_t plane = (int64_t)pl.taps * d.C_in * ((d.C_out + KC - 1) / KC * KC);
+    hipLaunchKernelGGL(tnet_conv_w_pack_kernel, dim3((int)std::min<int64_t>((plane + 255) / 256, 2048)), dim3(256), 0, s, w, wp, d.C_out,
+                       d.C_in, pl.taps, 1);
+    TNET_LAUNCH_CHECK("conv weight pack (transposed)")
+    const int NT = conv2_nt(pl.n_tiles_in, d.C_in);
+    const dim3 grid(pl.n_tiles_in, (d.C_in + 16 * NT - 1) / (16 * NT));
+    const size_t lds = conv2_lds(NT);
 #define C2B_CASE(n) case n: rc = tnet_raise_lds(tnet_conv2_kernel<n, true>, lds); if (rc) return rc; \
-        hipLaunchKernelGGL((tnet_conv2_kernel<n, true>), grid, dim3(256), lds, s, dzp, wp, dx, (float*)nullptr, x, d, pl.P_in, pl.P); break;
-        switch (NT) { C2B_CASE(2) C2B_CASE(4) C2B_CASE(8) }
+    hipLaunchKernelGGL((tnet_conv2_kernel<n, true>), grid, dim3(256), lds, s, dz, wp, dx, (float*)nullptr, x, d, pl.P_in, pl.P); break;
+    switch (NT) { C2B_CASE(2) C2B_CASE(4) C2B_CASE(8) }
 #undef C2B_CASE
-        TNET_LAUNCH_CHECK("conv bwd data")
-        hipLaunchKernelGGL(tnet_conv_wgrad_kernel, dim3(pl.w_chunks, (d.C_out + 63) / 64, ((d.C_in + 63) / 64) * pl.taps), dim3(256), 0, s, dzp,
-                           (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, x, part_w, d, pl.P,
-                           pl.w_chunk_px);
-        TNET_LAUNCH_CHECK("conv wgrad")
-        hipLaunchKernelGGL(tnet_reduce_rows_kernel, dim3((int)((wr / 4 + 15) / 16)), dim3(256), 0, s, part_w, pl.w_chunks, wr, dw,
-                           d.C_out * d.C_in, pl.taps);
-        TNET_LAUNCH_CHECK("conv wgrad reduce")
-        return GHN3_OK;
-    }
-    rc = conv_repack(d, pl, w, w_r, s);
-    if (rc) return rc;
-    // 2. dx
-    {
-        const int NT = nt_of(d.C_in);
-        const size_t lds = cbwd_lds(NT);
-#define CBWD_CASE(n, t) case 10 * n + t: rc = tnet_raise_lds(tnet_conv_bwd_data_kernel<n, t>, lds); if (rc) return rc; \
-        hipLaunchKernelGGL((tnet_conv_bwd_data_kernel<n, t>), dim3(pl.n_tiles_in), dim3(256), lds, s, dout, z, stats, gamma, s12, w_r, x, dx, d, pl.P, pl.P_in); break;
-        switch (10 * NT + terms_of(NT)) { CBWD_CASE(4, 3) CBWD_CASE(8, 3) CBWD_CASE(16, 3) CBWD_CASE(4, 2) CBWD_CASE(8, 2) CBWD_CASE(16, 2) CBWD_CASE(32, 2) }
-#undef CBWD_CASE
-        TNET_LAUNCH_CHECK("conv bwd data")
-    }
-    // 3. dW (in the parameter's own [C_out][C_in][kh][kw] order)
-    hipLaunchKernelGGL(tnet_conv_wgrad_kernel, dim3(pl.w_chunks, (d.C_out + 63) / 64, ((d.C_in + 63) / 64) * pl.taps), dim3(256), 0, s, dout, z,
-                       stats, gamma, s12, x, part_w, d, pl.P, pl.w_chunk_px);
+    TNET_LAUNCH_CHECK("conv bwd data")
+    // 4. dW (in the parameter's own [C_out][C_in][kh][kw] order)
+    float* part_w = scratch + sc.part_w;
+    hipLaunchKernelGGL(tnet_conv_wgrad_kernel, dim3(pl.w_chunks, (d.C_out + 63) / 64, ((d.C_in + 63) / 64) * pl.taps), dim3(256), 0, s, dz, x,
+                       part_w, d, pl.P, pl.w_chunk_px);
     TNET_LAUNCH_CHECK("conv wgrad")
     hipLaunchKernelGGL(tnet_reduce_rows_kernel, dim3((int)((wr / 4 + 15) / 16)), dim3(256), 0, s, part_w, pl.w_chunks, wr, dw,
                        d.C_out * d.C_in, pl.taps);

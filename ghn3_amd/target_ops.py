@@ -87,6 +87,19 @@ def lazy_layout(*layers):
     return all(not isinstance(m, torch.nn.Module) for m in layers)
 
 
+def _hand_on(out, keep_layout, *layers):
+    """A fused block's NHWC output as the next layer takes it: as it is when the caller keeps the layout or the block's layers
+    are of the light flavour (lazy_layout), else as a plain NCHW-contiguous tensor."""
+    return out if (keep_layout or lazy_layout(*layers)) else out.contiguous(memory_format=torch.contiguous_format)
+
+
+def _norm_inputs(bn):
+    """(gamma, beta, has_run, batch_stats) of a BatchNorm-like module: its affine pair, whether it carries running statistics,
+    and whether this call normalises with the batch's own."""
+    has_run = getattr(bn, 'running_mean', None) is not None
+    return getattr(bn, 'weight', None), getattr(bn, 'bias', None), has_run, getattr(bn, 'training', True) or not has_run
+
+
 def enabled():
     """GHN3_NATIVE_OPS=0 keeps every target-network layer on the stock ATen / MIOpen path (A/B measurements)."""
     return os.environ.get('GHN3_NATIVE_OPS', '1') != '0'
@@ -169,11 +182,20 @@ def _pair(v):
 
 
 CONV_NO_NORM = 2                  # include/ghn3_hip.h GHN3_CONV_NO_NORM
+CONV_MAX_IN = 4096                # widest input of the dense-convolution op (the kernels walk C_in in chunks)
 
 
-def _conv_max_in():
-    """Widest input of the dense-convolution op (include/ghn3_hip.h: the second-version kernels walk C_in in chunks)."""
-    return 4096 if os.environ.get('GHN3_TNET_CONV2', '1') != '0' else 512
+def _conv_applicable(x, w):
+    """What ConvBn and ConvOnly both ask of the input and the weight: fp32 CUDA tensors of four dimensions within the kernels'
+    limits, and none of the switches that keep the layer on the stock path."""
+    if not (enabled() and os.environ.get('GHN3_NATIVE_CONV', '1') != '0' and torch.is_tensor(x) and x.is_cuda and
+            x.dtype == torch.float32 and x.dim() == 4 and not _autocast_excludes()):
+        return False
+    if not (torch.is_tensor(w) and w.is_cuda and w.dtype == torch.float32 and w.dim() == 4):
+        return False
+    C_in, C_out = x.shape[1], w.shape[0]
+    return C_in % 4 == 0 and C_out % 4 == 0 and C_in <= CONV_MAX_IN and C_out <= 512 and w.shape[1] == C_in and \
+        max(w.shape[2], w.shape[3]) <= 7 and x.numel() < 2 ** 31
 
 
 def _conv_desc(x, w, stride, pad, dil, relu, eps, no_norm=False):
@@ -193,16 +215,8 @@ class ConvBn(torch.autograd.Function):
 
     @staticmethod
     def applicable(x, w, gamma, beta, training_stats=True):
-        if not (enabled() and os.environ.get('GHN3_NATIVE_CONV', '1') != '0' and torch.is_tensor(x) and x.is_cuda and
-                x.dtype == torch.float32 and x.dim() == 4):
-            return False
-        if _autocast_excludes() or not training_stats:
-            return False
-        if not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in (w, gamma, beta)) or w.dim() != 4:
-            return False
-        C_in, C_out = x.shape[1], w.shape[0]
-        return C_in % 4 == 0 and C_out % 4 == 0 and C_in <= _conv_max_in() and C_out <= 512 and w.shape[1] == C_in and \
-            max(w.shape[2], w.shape[3]) <= 7 and x.numel() < 2 ** 31 and gamma.numel() == C_out
+        return bool(training_stats) and all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in (gamma, beta)) and \
+            _conv_applicable(x, w) and gamma.numel() == w.shape[0]
 
     @staticmethod
     def forward(ctx, x, w, gamma, beta, stride, pad, dil, relu, eps):
@@ -250,14 +264,7 @@ class ConvOnly(torch.autograd.Function):
 
     @staticmethod
     def applicable(x, w):
-        if not (enabled() and os.environ.get('GHN3_NATIVE_CONV', '1') != '0' and torch.is_tensor(x) and x.is_cuda and
-                x.dtype == torch.float32 and x.dim() == 4 and not _autocast_excludes()):
-            return False
-        if not (torch.is_tensor(w) and w.is_cuda and w.dtype == torch.float32 and w.dim() == 4):
-            return False
-        C_in, C_out = x.shape[1], w.shape[0]
-        return C_in % 4 == 0 and C_out % 4 == 0 and C_in <= _conv_max_in() and C_out <= 512 and w.shape[1] == C_in and \
-            max(w.shape[2], w.shape[3]) <= 7 and x.numel() < 2 ** 31
+        return _conv_applicable(x, w)
 
     @staticmethod
     def forward(ctx, x, w, stride, pad, dil, relu):
@@ -370,7 +377,7 @@ def run_se_layer(fc1, fc2, x, keep_layout=False):
     if not SqueezeExcite.applicable(x, w1, b1, w2, b2):
         return None
     y = se_layer(x, w1, b1, w2, b2)
-    return y if (keep_layout or lazy_layout(fc1, fc2)) else y.contiguous(memory_format=torch.contiguous_format)
+    return _hand_on(y, keep_layout, fc1, fc2)
 
 
 class _PoolDesc(ctypes.Structure):
@@ -435,19 +442,16 @@ def run_conv_block(layers, x, keep_layout=False):
     """[ReLU, k x k Conv2d, BatchNorm2d] -- `ReLUConvBN` (ops.py:180-198) -- on the fused dense-convolution op where it applies,
     else layer by layer.  Same layout contract as run_block."""
     relu, conv, bn = layers
-    w, gamma, beta = getattr(conv, 'weight', None), getattr(bn, 'weight', None), getattr(bn, 'bias', None)
-    has_run = getattr(bn, 'running_mean', None) is not None
-    batch_stats = getattr(bn, 'training', True) or not has_run
-    ok = hasattr(bn, 'eps') and getattr(conv, 'bias', None) is None and hasattr(conv, 'kernel_size') and \
-        not isinstance(conv.padding, str) and getattr(conv, 'groups', 1) == 1 and torch.is_tensor(w) and \
-        len(set(_pair(getattr(conv, 'dilation', 1)))) == 1 and ConvBn.applicable(x, w, gamma, beta, batch_stats)
+    gamma, beta, has_run, batch_stats = _norm_inputs(bn)
+    w = getattr(conv, 'weight', None)
+    ok = hasattr(bn, 'eps') and _plain_conv(conv) and ConvBn.applicable(x, w, gamma, beta, batch_stats)
     if not ok:
         for m in layers:
             x = m(x)
         return x
     out, stats = conv_bn(x, w, gamma, beta, conv.stride, conv.padding, _pair(conv.dilation)[0], True, bn.eps)
     _update_running_stats(bn, stats, out, has_run)
-    return out if (keep_layout or lazy_layout(conv, bn)) else out.contiguous(memory_format=torch.contiguous_format)
+    return _hand_on(out, keep_layout, conv, bn)
 
 
 def _plain_conv(conv):
@@ -462,9 +466,7 @@ def run_conv_pair_block(layers, x, keep_layout=False):
     298) -- as two dense-convolution nodes: ReLU + the first convolution alone (ConvOnly), then the second one with the norm
     (ConvBn without a ReLU); the intermediate stays NHWC.  Else layer by layer."""
     relu, conv_a, conv_b, bn = layers
-    gamma, beta = getattr(bn, 'weight', None), getattr(bn, 'bias', None)
-    has_run = getattr(bn, 'running_mean', None) is not None
-    batch_stats = getattr(bn, 'training', True) or not has_run
+    gamma, beta, has_run, batch_stats = _norm_inputs(bn)
     ok = hasattr(bn, 'eps') and _plain_conv(conv_a) and _plain_conv(conv_b) and ConvOnly.applicable(x, conv_a.weight) and \
         conv_b.weight.shape[1] == conv_a.weight.shape[0]
     if ok:
@@ -478,7 +480,7 @@ def run_conv_pair_block(layers, x, keep_layout=False):
     y = conv_only(x, conv_a.weight, conv_a.stride, conv_a.padding, _pair(conv_a.dilation)[0], relu=True)
     out, stats = conv_bn(y, conv_b.weight, gamma, beta, conv_b.stride, conv_b.padding, _pair(conv_b.dilation)[0], False, bn.eps)
     _update_running_stats(bn, stats, out, has_run)
-    return out if (keep_layout or lazy_layout(conv_a, conv_b, bn)) else out.contiguous(memory_format=torch.contiguous_format)
+    return _hand_on(out, keep_layout, conv_a, conv_b, bn)
 
 
 def run_conv_layer(conv, x):
@@ -513,9 +515,8 @@ def run_layer_seq(seq, x):
         done = False
         if _is_kind(conv, 'Conv2d') and bn is not None and _is_kind(bn, 'BatchNorm2d') and hasattr(bn, 'eps') and \
                 _plain_conv(conv) and torch.is_tensor(x) and x.is_cuda and x.dim() == 4:
-            w, gamma, beta = conv.weight, getattr(bn, 'weight', None), getattr(bn, 'bias', None)
-            has_run = getattr(bn, 'running_mean', None) is not None
-            batch_stats = getattr(bn, 'training', True) or not has_run
+            w = conv.weight
+            gamma, beta, has_run, batch_stats = _norm_inputs(bn)
             xin = x
             if x.shape[1] == 3 and w.shape[1] == 3:
                 xin = F.pad(x, (0, 0, 0, 0, 0, 1))
@@ -528,8 +529,7 @@ def run_layer_seq(seq, x):
                     xin, fold = m(xin), False
                 x, stats = conv_bn(xin, w, gamma, beta, conv.stride, conv.padding, _pair(conv.dilation)[0], fold, bn.eps)
                 _update_running_stats(bn, stats, x, has_run)
-                if not lazy_layout(conv, bn):
-                    x = x.contiguous(memory_format=torch.contiguous_format)
+                x = _hand_on(x, False, conv, bn)
                 k += 3 if relu else 2
                 done = True
         if not done:
@@ -546,9 +546,7 @@ def run_factorized_reduce(relu, conv_1, conv_2, bn, x, stride=2, keep_layout=Fal
     reach conv_1 / conv_2 (views of the GHN's prediction buffer) through autograd.  Returns None when the fused op does not
     apply (the caller keeps the stock layers)."""
     w1, w2 = getattr(conv_1, 'weight', None), getattr(conv_2, 'weight', None)
-    gamma, beta = getattr(bn, 'weight', None), getattr(bn, 'bias', None)
-    has_run = getattr(bn, 'running_mean', None) is not None
-    batch_stats = getattr(bn, 'training', True) or not has_run
+    gamma, beta, has_run, batch_stats = _norm_inputs(bn)
     if not (stride == 2 and hasattr(bn, 'eps') and torch.is_tensor(w1) and torch.is_tensor(w2) and x.dim() == 4 and
             x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0 and getattr(conv_1, 'bias', None) is None and
             getattr(conv_2, 'bias', None) is None and w1.shape == w2.shape and tuple(w1.shape[2:]) == (1, 1)):
@@ -561,7 +559,7 @@ def run_factorized_reduce(relu, conv_1, conv_2, bn, x, stride=2, keep_layout=Fal
         return None
     out, stats = conv_bn(x, w, gamma, beta, 2, 0, 1, True, bn.eps)
     _update_running_stats(bn, stats, out, has_run)
-    return out if (keep_layout or lazy_layout(conv_1, conv_2, bn)) else out.contiguous(memory_format=torch.contiguous_format)
+    return _hand_on(out, keep_layout, conv_1, conv_2, bn)
 
 
 def dwpw_bn(x, w_dw, w_pw, gamma, beta, stride=1, padding=0, dilation=1, eps=1e-5):
@@ -578,9 +576,8 @@ def run_pointwise_block(layers, x, keep_layout=False):
     """[ReLU, 1 x 1 Conv2d, BatchNorm2d] -- `ReLUConvBN` with a 1 x 1 kernel (ops.py:180-198: the preprocessing layer of every
     cell, the `conv_1x1` op) -- on the fused op without a depthwise stage where it applies, else layer by layer."""
     relu, pw, bn = layers
-    w_pw, gamma, beta = getattr(pw, 'weight', None), getattr(bn, 'weight', None), getattr(bn, 'bias', None)
-    has_run = getattr(bn, 'running_mean', None) is not None
-    batch_stats = getattr(bn, 'training', True) or not has_run
+    w_pw = getattr(pw, 'weight', None)
+    gamma, beta, has_run, batch_stats = _norm_inputs(bn)
     ok = hasattr(bn, 'eps') and getattr(pw, 'bias', None) is None and hasattr(pw, 'kernel_size') and \
         tuple(pw.kernel_size) == (1, 1) and pw.stride[0] == pw.stride[1] and not isinstance(pw.padding, str) and \
         tuple(pw.padding) == (0, 0) and getattr(pw, 'groups', 1) == 1 and torch.is_tensor(w_pw) and \
@@ -590,7 +587,7 @@ def run_pointwise_block(layers, x, keep_layout=False):
         return run_conv_block(layers, x, keep_layout)
     out, stats = dwpw_bn(x, None, w_pw, gamma, beta, pw.stride[0], 0, 1, bn.eps)
     _update_running_stats(bn, stats, out, has_run)
-    return out if (keep_layout or lazy_layout(pw, bn)) else out.contiguous(memory_format=torch.contiguous_format)
+    return _hand_on(out, keep_layout, pw, bn)
 
 
 def _update_running_stats(bn, stats, out, has_run):
@@ -628,9 +625,7 @@ def run_block(layers, x, keep_layout=False):
     direction at the op's boundary until the neighbouring layers are native as well."""
     relu, dw, pw, bn = layers
     w_dw, w_pw = getattr(dw, 'weight', None), getattr(pw, 'weight', None)
-    gamma, beta = getattr(bn, 'weight', None), getattr(bn, 'bias', None)
-    has_run = getattr(bn, 'running_mean', None) is not None
-    batch_stats = getattr(bn, 'training', True) or not has_run
+    gamma, beta, has_run, batch_stats = _norm_inputs(bn)
     ks = dw.kernel_size[0] if hasattr(dw, 'kernel_size') else 0
     ok = hasattr(bn, 'eps') and getattr(dw, 'bias', None) is None and getattr(pw, 'bias', None) is None and \
         hasattr(dw, 'kernel_size') and dw.kernel_size[0] == dw.kernel_size[1] and dw.stride[0] == dw.stride[1] and \
@@ -646,7 +641,7 @@ def run_block(layers, x, keep_layout=False):
         return x
     out, stats = dwpw_bn(x, w_dw, w_pw, gamma, beta, dw.stride[0], dw.padding[0], dw.dilation[0], bn.eps)
     _update_running_stats(bn, stats, out, has_run)
-    return out if (keep_layout or lazy_layout(dw, pw, bn)) else out.contiguous(memory_format=torch.contiguous_format)
+    return _hand_on(out, keep_layout, dw, pw, bn)
 
 
 class _MsaDesc(ctypes.Structure):
@@ -782,7 +777,7 @@ def run_msa_layer(layer, x):
     train = torch.is_grad_enabled() and (x.requires_grad or any(t is not None and t.requires_grad for t in params))
     cfg = (int(layer.attn.num_heads), int(layer.stride), float(layer.ln1.eps), bool(train))
     y = MsaLayer.apply(x, cfg, *params)
-    return y if lazy_layout(layer.ln1, layer.attn.to_qkv) else y.contiguous(memory_format=torch.contiguous_format)
+    return _hand_on(y, False, layer.ln1, layer.attn.to_qkv)
 
 
 # ---- the classifier head and the meta-batch cross-entropy (ghn3_head_* / ghn3_xent_*, ghn3_amd/csrc/tnet_head.hip) ----------
