@@ -15,6 +15,35 @@ def rel_l2(a, b):
     return float(np.linalg.norm(a - b) / den) if den > 0 else float(np.linalg.norm(a - b))
 
 
+def _f64(t):
+    return t.detach().cpu().double().numpy() if torch.is_tensor(t) else np.asarray(t, dtype=np.float64)
+
+
+def slice_errors(got, ref, axes_list):
+    """Worst per-slice error of `got` against `ref` (tensors or arrays of one shape).  For every axis set in `axes_list` the
+    tensors are cut into slices indexed by those axes (e.g. (1,) = per channel of an NCHW tensor, (2, 3) = per position); a
+    slice's error is the L2 norm of got - ref over all OTHER axes, divided by the reference's RMS slice norm
+    ||ref|| / sqrt(n_slices) -- not by the slice's own norm, so a slice whose true value is near zero cannot blow the ratio
+    up, while an error confined to one slice is no longer divided by the norm of everything else.  Returns
+    (worst ratio, (axes, index of the slice)); a NaN or infinity in `got` gives inf.  An all-zero reference: absolute norms."""
+    g, r = _f64(got), _f64(ref)
+    assert g.shape == r.shape, (g.shape, r.shape)
+    total = float(np.linalg.norm(r))
+    worst, where = 0.0, None
+    for axes in axes_list:
+        axes = tuple(sorted(int(a) % r.ndim for a in axes))
+        others = tuple(a for a in range(r.ndim) if a not in axes)
+        with np.errstate(invalid='ignore', over='ignore'):
+            err = np.sqrt(np.sum((g - r) ** 2, axis=others))       # (its axes: `axes` in ascending order)
+        err = np.where(np.isfinite(err), err, np.inf)
+        den = total / np.sqrt(err.size)
+        k = int(np.argmax(err))
+        v = float(err.reshape(-1)[k] / den) if den > 0 else float(err.reshape(-1)[k])
+        if where is None or v > worst:
+            worst, where = v, (axes, tuple(int(j) for j in np.unravel_index(k, err.shape)) if err.ndim else ())
+    return worst, where
+
+
 def make_models(cfg, seed, index_mode='reference', compute='f32', device='cuda'):
     """(hip model on device, oracle model on CPU) sharing one seeded state dict."""
     from ghn3_amd import GHN3
