@@ -282,8 +282,11 @@ enum ghn3_op_kind {
      * With r6 the normalised rows are x + sum_p r6[p] (summed in plane order) and the sum is written back to x (the
      * planes are the further K slices of the GEMM that produced x, split over several workgroup sets). */
     GHN3_OP_LAYERNORM_FWD = 6,
-    /* graphormer.py:121-140 ; r0=out(B*N,C) r1=qkv(B*N,3C) r2=bias(B,H,N,N) r3=P save or absent r4=n_nodes
-     * i: B,N,C,H */
+    /* graphormer.py:121-140 ; r0=out(B*N,C) r1=qkv(B*N,3C) r2=bias(B,H,N,N) or absent r3=P save or absent r4=n_nodes
+     * i: B,N,C,H
+     * Padded nodes (i >= n_nodes[b]): `out` and P are written for EVERY query row below N.  A padded query has all its scores
+     * masked to -32768, so its P row is exactly 1 / N over all N keys and its output row the mean of all N value rows (as the
+     * reference computes them); padded keys get probability 0 from valid queries. */
     GHN3_OP_ATTN_FWD = 7,
     /* r0=flat out, r1..r6 = sources, r7 = descriptors (device)
      * i: n_desc, n_work_blocks, byte offset from r7 to the int64 (descriptor, start) work-block table, LDS bytes
@@ -335,7 +338,9 @@ enum ghn3_op_kind {
     /* r0=dqkv r1=dO r2=qkv r3=P r4=O (saved attention output) r5=optional device float: running max of |dBias| as
      * written by this launch (atomic max on a zeroed slot -- the program passes it to the LAST launch that accumulates into
      * r6, whose values are final: GHN3_OP_BIAS_HIST then needs no pass for its scale; ABI v15) r6=dBias (accumulated)
-     * r7=n_nodes ; i: B,N,C,H, i4 = 1: the general kernel (operands straight from memory) also where the LDS-staged kernel for
+     * r7=n_nodes ; every dqkv row below N is written: dQ and dK of padded nodes are exact zeros, dV = P^T dO over ALL query
+     * rows (the uniform P rows of padded queries included); dBias outside the valid square keeps its value (+ 0) ;
+     * i: B,N,C,H, i4 = 1: the general kernel (operands straight from memory) also where the LDS-staged kernel for
      * graphs of up to 256 nodes would run -- both give the same bits; tests compare them */
     GHN3_OP_ATTN_BWD = 16,
     /* dT[p][h] += sum_{pair==p} dBias[b,h,i,j] ; r0=dT r1=dBias r2=pair r3=scratch: 8 * V * V * H + 16 bytes, ZEROED by

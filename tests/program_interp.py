@@ -478,8 +478,8 @@ class Interp:
         def tab(t, w):
             n = len(t) // w
             return t[:n * w].reshape(n, w)
-        Et, Ech, Esp, Ein, Eout, Ed = tab(T[0], C), tab(T[1], cq), tab(T[2], cq), tab(T[3], C), tab(T[4], C), \
-            tab(T[5], C)
+        out = [tab(T[0], C), tab(T[1], cq), tab(T[2], cq), tab(T[3], C), tab(T[4], C), tab(T[5], C)]
+        Et, Ech, Esp, Ein, Eout, Ed = (np.zeros(t.shape, np.float64) for t in out)      # float64 sums, added to the tables once
         for b in range(B):
             for i in range(int(n_nodes[b])):
                 row = b * N + i
@@ -493,6 +493,9 @@ class Interp:
                 Ein[deg_in[row]] += g
                 Eout[deg_out[row]] += g
                 Ed[dist0[row]] += g
+        for t, acc in zip(out, (Et, Ech, Esp, Ein, Eout, Ed)):
+            nz = np.any(acc != 0, axis=1)              # (table views run to the end of a shared buffer: only the rows indexed)
+            t[nz] = t[nz] + acc[nz]
 
     def op_edge_hidden(self, o, problems):
         V, C = int(o['i'][0]), int(o['i'][1])
@@ -506,8 +509,8 @@ class Interp:
         dhid = self.fview(o['r'][2], V * V * C).reshape(V, V, C)
         hid = self.fview(o['r'][3], V * V * C).reshape(V, V, C)
         dhid[:] = np.where(hid > 0, dhid, 0)
-        self.fview(o['r'][0], V * C).reshape(V, C)[:] = dhid.sum(1)
-        self.fview(o['r'][1], V * C).reshape(V, C)[:] = dhid.sum(0)
+        self.fview(o['r'][0], V * C).reshape(V, C)[:] = dhid.sum(1, dtype=np.float64)
+        self.fview(o['r'][1], V * C).reshape(V, C)[:] = dhid.sum(0, dtype=np.float64)
 
     def op_bias_gather(self, o, problems):
         B, N, H = (int(v) for v in o['i'][:3])
@@ -527,8 +530,10 @@ class Interp:
         if int(o['i'][4]):                               # the scale comes from the slot GHN3_OP_ATTN_BWD (r5) filled
             am = self.tail(o['r'][3], np.uint8)[8 * V * V * H:8 * V * V * H + 4].view(np.float32)[0]
             assert abs(float(am) - float(np.abs(dB).max())) <= 1e-6 * float(np.abs(dB).max()) + 1e-30, 'stale max |dBias|'
+        acc = np.zeros(dT.shape, np.float64)
         for h in range(H):
-            np.add.at(dT, pair * ldT + h, dB[:, h, :].reshape(-1))
+            np.add.at(acc, pair * ldT + h, dB[:, h, :].reshape(-1).astype(np.float64))
+        dT[:] = dT + acc
 
     def op_layernorm_fwd(self, o, problems):
         rows, C = int(o['i'][0]), int(o['i'][1])
@@ -840,7 +845,7 @@ class Interp:
             X[ii[:rows_parts]] = acc
         if dact == L.DACT_RELU:
             X[ii] = np.where(z > 0, X[ii], 0.0)
-        else:
+        elif dact == L.DACT_GELU:
             X[ii] = X[ii] * (0.5 * (1 + erf(z / math.sqrt(2))) + z * np.exp(-0.5 * z * z) / math.sqrt(2 * math.pi))
         amax = self.tail(o['r'][2], np.float32)
         if amax is not None:
