@@ -73,7 +73,7 @@ EXPORTS = ['ghn3_abi_version', 'ghn3_last_error', 'ghn3_ctx_create', 'ghn3_ctx_d
            'ghn3_profile_read_tags', 'ghn3_dwpw_scratch_floats', 'ghn3_dwpw_bn_fwd', 'ghn3_dwpw_bn_bwd',
            'ghn3_conv_scratch_floats', 'ghn3_conv_bn_fwd', 'ghn3_conv_bn_bwd', 'ghn3_se_fwd', 'ghn3_se_bwd', 'ghn3_pool_fwd', 'ghn3_pool_bwd',
            'ghn3_msa_scratch_floats', 'ghn3_msa_fwd', 'ghn3_msa_bwd', 'ghn3_head_scratch_floats', 'ghn3_head_fwd',
-           'ghn3_head_bwd', 'ghn3_xent_fwd', 'ghn3_xent_bwd']
+           'ghn3_head_bwd', 'ghn3_xent_fwd', 'ghn3_xent_bwd', 'ghn3_join_fwd', 'ghn3_join_bwd', 'ghn3_posenc_bwd']
 OPFLAG_TIMED = 0x100
 OPFLAG_SIDE = 0x200
 
@@ -95,6 +95,9 @@ def load():
             raise Ghn3Error('%s is missing: build it with `python -m ghn3_amd.build` (hipcc, gfx950). '
                             'ghn3_amd has no CPU fallback.' % LIB_PATH)
         lib = ctypes.CDLL(LIB_PATH)
+        missing = [n for n in EXPORTS if not hasattr(lib, n)]
+        if missing:                              # (entry points added without an ABI version step, e.g. the joins)
+            raise Ghn3Error('libghn3_hip.so lacks %s: rebuild' % ', '.join(missing))
         lib.ghn3_abi_version.restype = ctypes.c_int
         lib.ghn3_last_error.restype = ctypes.c_char_p
         lib.ghn3_ctx_create.argtypes = [ctypes.POINTER(ctypes.c_void_p)]
@@ -135,6 +138,9 @@ def load():
         lib.ghn3_head_bwd.argtypes = [ctypes.c_void_p] * 9
         lib.ghn3_xent_fwd.argtypes = [ctypes.c_void_p] * 7
         lib.ghn3_xent_bwd.argtypes = [ctypes.c_void_p] * 7
+        lib.ghn3_join_fwd.argtypes = [ctypes.c_void_p] * 3
+        lib.ghn3_join_bwd.argtypes = [ctypes.c_void_p] * 3
+        lib.ghn3_posenc_bwd.argtypes = [ctypes.c_int] * 5 + [ctypes.c_void_p] * 3
         if lib.ghn3_abi_version() != ABI_VERSION:
             raise Ghn3Error('libghn3_hip.so ABI %d != expected %d: rebuild' % (lib.ghn3_abi_version(), ABI_VERSION))
         _lib = lib

@@ -243,6 +243,11 @@ class _PosEnc:
         self.weight = [1, C, ks, ks] if self.L.light else nn.Parameter(torch.randn(1, C, ks, ks))
 
     def forward(self, x):
+        if torch.is_tensor(x) and x.is_cuda and target_ops.join_enabled():
+            # (one native node, ghn3_amd/csrc/tnet_join.hip; NHWC for the light flavour's cells, as every fused layer hands on)
+            y = target_ops.pos_enc(x, self.weight, nhwc=target_ops.lazy_layout(self))
+            if y is not None:
+                return y
         return x + self.weight
 
 
@@ -425,10 +430,18 @@ class _Cell:
         s0 = None if (s0 is None or _is_none(self.preprocess0)) else self.preprocess0(s0)
         s1 = None if (s1 is None or _is_none(self.preprocess1)) else self.preprocess1(s1)
         states = [s0, s1]
+        # the sums and the concatenation as native nodes on CUDA tensors (target_ops.pair_sum / cell_concat,
+        # ghn3_amd/csrc/tnet_join.hip): NHWC out where the fused layers hand NHWC on (light flavour), plain NCHW otherwise
+        native = target_ops.join_enabled()
+        nhwc = native and target_ops.lazy_layout(self)
         for k in range(self._steps):
             a = self._branch(self._ops[2 * k], states[self._indices[2 * k]], drop_path_prob)
             b = self._branch(self._ops[2 * k + 1], states[self._indices[2 * k + 1]], drop_path_prob)
-            states.append(a if b is None else (b if a is None else a + b))
+            if a is None or b is None:
+                states.append(a if b is None else b)
+                continue
+            y = target_ops.pair_sum(a, b, nhwc=nhwc) if (native and a.is_cuda) else None
+            states.append(a + b if y is None else y)
         outs = [states[k] for k in self._concat]
         if any(s is None for s in outs):
             # states that received nothing ('none' ops) are replaced by zeros of a live state's shape
@@ -436,8 +449,10 @@ class _Cell:
             live = next((s for s in outs if s is not None), None)
             if live is None:
                 return None
-            outs = [live * 0 if s is None else s for s in outs]
-        return torch.cat(outs, dim=1)
+            # (rare, and 0 * inf must stay NaN: this case keeps the stock concatenation)
+            return torch.cat([live * 0 if s is None else s for s in outs], dim=1)
+        y = target_ops.cell_concat(outs, nhwc=nhwc) if (native and outs[0].is_cuda) else None
+        return torch.cat(outs, dim=1) if y is None else y
 
 
 def _layer_seq(Lyr, norm, spec):

@@ -1029,3 +1029,229 @@ def meta_cross_entropy(logits, targets, label_smoothing=0.0):
         hit = top == targets.view(1, -1, 1)
         hits = torch.stack([hit[..., :1].any(-1).sum(), hit.any(-1).sum()])
     return ce, hits
+
+
+# ---- a cell's state sums, its concatenation and the positional encoding (ghn3_join_* / ghn3_posenc_bwd, csrc/tnet_join.hip) --
+JOIN_MAX_SLICES = 16                  # include/ghn3_hip.h GHN3_JOIN_MAX_SLICES
+NCHW, NHWC = 0, 1
+
+
+class _JoinSrc(ctypes.Structure):
+    _fields_ = [('p', ctypes.c_void_p), ('grad', ctypes.c_void_p)] + \
+        [(n, ctypes.c_int32) for n in ('H', 'W', 'step', 'layout', 'broadcast_n', '_pad')]
+
+
+class _JoinSlice(ctypes.Structure):
+    _fields_ = [('a', _JoinSrc), ('b', _JoinSrc), ('c0', ctypes.c_int32), ('C', ctypes.c_int32)]
+
+
+class _JoinDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ('N', 'H', 'W', 'C', 'layout', 'n_slices')] + [('s', _JoinSlice * JOIN_MAX_SLICES)]
+
+
+def join_enabled():
+    """GHN3_NATIVE_JOIN=0 (or GHN3_NATIVE_OPS=0) keeps the stock expressions (a + b, torch.cat, x + weight) everywhere."""
+    return enabled() and os.environ.get('GHN3_NATIVE_JOIN', '1') != '0'
+
+
+def _layout(t):
+    """NCHW / NHWC when the 4-d tensor t is dense in that order in memory, else None."""
+    if t.is_contiguous():
+        return NCHW
+    return NHWC if t.is_contiguous(memory_format=torch.channels_last) else None
+
+
+def _fmt(layout):
+    return torch.channels_last if layout else torch.contiguous_format
+
+
+def join_refusal(slices, broadcast_b=False):
+    """Why ghn3_join_fwd / _bwd do not take `slices` = [(a, b or None, a_step, b_step), ...] (the output's channel slices in
+    order, each a[:, :, ::a_step, ::a_step] (+ b[...])), or None when they do.  The rules, in the order they are checked --
+    the shape rules come before the device's, so they can be asked of CPU and meta tensors, and they mirror the limits of
+    include/ghn3_hip.h, so a step never meets the C refusal:
+      'slices'   1 .. JOIN_MAX_SLICES slices;
+      'type'     every source a 4-d fp32 tensor, every step 1 or 2;
+      'channels' C_j % 4 == 0 (so every c0_j % 4 == 0), both sources of a slice of one width;
+      'dense'    every source dense in memory in NCHW or in NHWC order;
+      'map'      one N (a broadcast b: N == 1) and one output map ceil(H_j / step_j) x ceil(W_j / step_j) for all sources;
+      'size'     every source and the output below 2^31 elements;
+      'align'    an NHWC source starts on 16 bytes;
+      'device'   CUDA tensors of one device;
+      'switch'   GHN3_NATIVE_JOIN / GHN3_NATIVE_OPS / GHN3_NATIVE_AMP under autocast."""
+    if not 1 <= len(slices) <= JOIN_MAX_SLICES:
+        return 'slices'
+    srcs = [(t, st, broadcast_b and k == 1) for sl in slices for k, (t, st) in enumerate(((sl[0], sl[2]), (sl[1], sl[3])))
+            if k == 0 or t is not None]
+    if not all(torch.is_tensor(t) and t.dim() == 4 and t.dtype == torch.float32 and st in (1, 2) for t, st, _ in srcs):
+        return 'type'
+    if any(a.shape[1] % 4 or (b is not None and b.shape[1] != a.shape[1]) for a, b, _, _ in slices):
+        return 'channels'
+    if any(_layout(t) is None for t, _, _ in srcs):
+        return 'dense'
+    a0, _, s0, _ = slices[0]
+    N, H, W = a0.shape[0], -(-a0.shape[2] // s0), -(-a0.shape[3] // s0)
+    if any(t.shape[0] != (1 if bc else N) or -(-t.shape[2] // st) != H or -(-t.shape[3] // st) != W for t, st, bc in srcs):
+        return 'map'
+    if any(t.numel() >= 2 ** 31 for t, _, _ in srcs) or N * H * W * sum(sl[0].shape[1] for sl in slices) >= 2 ** 31:
+        return 'size'
+    if any(_layout(t) == NHWC and t.data_ptr() % 16 for t, _, _ in srcs if t.device.type != 'meta'):
+        return 'align'
+    if not all(t.is_cuda and t.device == a0.device for t, _, _ in srcs):
+        return 'device'
+    if not join_enabled() or _autocast_excludes():
+        return 'switch'
+    return None
+
+
+def join_applicable(slices, broadcast_b=False):
+    """What the join kernels take (join_refusal lists the rules)."""
+    return join_refusal(slices, broadcast_b) is None
+
+
+def _src(t, step, broadcast=False):
+    return _JoinSrc(t.data_ptr(), None, t.shape[2], t.shape[3], step, _layout(t), int(broadcast), 0)
+
+
+def _join_fwd(slices, nhwc, broadcast_b=False):
+    """One ghn3_join_fwd launch for slices that passed join_refusal; returns (out, metas) with metas[j] = the
+    (shape, step, layout) of slice j's sources, what the backward needs of them."""
+    a0, _, s0, _ = slices[0]
+    N, H, W = a0.shape[0], -(-a0.shape[2] // s0), -(-a0.shape[3] // s0)
+    C = sum(sl[0].shape[1] for sl in slices)
+    out = torch.empty((N, C, H, W), dtype=torch.float32, device=a0.device, memory_format=_fmt(nhwc))
+    d = _JoinDesc(N, H, W, C, int(bool(nhwc)), len(slices))
+    c0, metas = 0, []
+    for j, (a, b, sa, sb) in enumerate(slices):
+        s = d.s[j]
+        s.a, s.c0, s.C = _src(a, sa), c0, a.shape[1]
+        if b is not None:
+            s.b = _src(b, sb, broadcast_b)
+        metas.append(((a.shape, sa, _layout(a)), None if b is None else (b.shape, sb, _layout(b))))
+        c0 += a.shape[1]
+    L._check(L.load().ghn3_join_fwd(ctypes.byref(d), _ptr(out), _stream()), 'ghn3_join_fwd')
+    return out, metas
+
+
+def _dense_grad(dout, nhwc):
+    """(dout as a dense tensor the kernels read, its layout): as it is when it is dense (and starts on 16 bytes if NHWC), else
+    a copy (a fresh allocation: aligned) in the forward output's layout."""
+    lo = _layout(dout)
+    if lo is None or (lo == NHWC and dout.data_ptr() % 16):
+        lo = int(bool(nhwc))
+        dout = dout.clone(memory_format=_fmt(lo))
+    return dout, lo
+
+
+def _join_bwd(metas, wanted, dout, nhwc):
+    """The gradients of the sources of a join, [(grad a, grad b or None), ...]: dout itself for a source that spans all of its
+    channels in dout's layout at step 1 (no launch), else a dense tensor of the source's layout and size written by ONE
+    ghn3_join_bwd launch for all of them.  wanted[j] = (a needs one, b needs one)."""
+    dout, lo = _dense_grad(dout, nhwc)
+    N, C, H, W = dout.shape
+    d = _JoinDesc(N, H, W, C, lo, len(metas))
+    c0, grads, launch = 0, [], False
+    for j, (pair, want) in enumerate(zip(metas, wanted)):
+        s, row = d.s[j], []
+        s.c0, s.C = c0, pair[0][0][1]
+        for k, m in enumerate(pair):
+            g = None
+            if m is not None and want[k]:
+                shape, step, layout = m
+                if len(metas) == 1 and step == 1 and layout == lo and shape[0] == N:
+                    g = dout
+                else:
+                    g = torch.empty(tuple(shape), dtype=torch.float32, device=dout.device, memory_format=_fmt(layout))
+                    src = _JoinSrc(None, g.data_ptr(), shape[2], shape[3], step, layout, 0, 0)
+                    if k:
+                        s.b = src
+                    else:
+                        s.a = src
+                    launch = True
+            row.append(g)
+        grads.append(tuple(row))
+        c0 += s.C
+    if launch:
+        L._check(L.load().ghn3_join_bwd(ctypes.byref(d), _ptr(dout), _stream()), 'ghn3_join_bwd')
+    return grads, dout, lo
+
+
+class Join(torch.autograd.Function):
+    """Channel slices a_j[:, :, ::sa_j, ::sa_j] (+ b_j[:, :, ::sb_j, ::sb_j]) written side by side as ONE autograd node on
+    ghn3_join_fwd / _bwd: one slice of two sources is an intermediate state of a cell (pair_sum), single-source slices are the
+    cell's concatenation (cell_concat).  spec[j] = (a_step, b_step or 0 for a single source); the tensors follow in slice
+    order.  Nothing is saved for the backward but the sources' shapes; the stock backward of torch.cat hands out strided
+    slices of dout, which every fused layer below then copies for itself -- here every source gets a dense gradient from one
+    launch, or dout itself where that is the gradient (a sum's source in dout's layout at step 1)."""
+
+    @staticmethod
+    def forward(ctx, spec, nhwc, *tensors):
+        slices, k = [], 0
+        for sa, sb in spec:
+            slices.append((tensors[k], tensors[k + 1] if sb else None, sa, sb or 1))
+            k += 2 if sb else 1
+        out, ctx.metas = _join_fwd(slices, nhwc)
+        ctx.nhwc = nhwc
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        need, wanted = list(ctx.needs_input_grad[2:]), []
+        for _, b in ctx.metas:
+            wanted.append((need.pop(0), need.pop(0) if b is not None else False))
+        grads = _join_bwd(ctx.metas, wanted, dout, ctx.nhwc)[0]
+        return (None, None) + tuple(g for (ga, gb), (_, b) in zip(grads, ctx.metas) for g in ((ga, gb) if b is not None else (ga,)))
+
+
+class PosEnc(torch.autograd.Function):
+    """x + w for w (1, C, ks, ks), the learned positional encoding of the ViT-style networks: the forward is a join whose second
+    source is read for every n; dx is dout (copied only when x was stored in the other order), dw = the sum of dout over n in
+    a fixed order (ghn3_posenc_bwd), a dense tensor of w's shape."""
+
+    @staticmethod
+    def forward(ctx, x, w, nhwc):
+        out, ctx.metas = _join_fwd([(x, w.contiguous(), 1, 1)], nhwc, broadcast_b=True)
+        ctx.nhwc = nhwc
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        grads, dout, lo = _join_bwd(ctx.metas, [(ctx.needs_input_grad[0], False)], dout, ctx.nhwc)
+        dx, dw = grads[0][0], None
+        if ctx.needs_input_grad[1]:
+            N, C, H, W = dout.shape
+            dw = torch.empty((1, C, H, W), dtype=torch.float32, device=dout.device)
+            L._check(L.load().ghn3_posenc_bwd(N, C, H, W, lo, _ptr(dout), _ptr(dw), _stream()), 'ghn3_posenc_bwd')
+        return dx, dw, None
+
+
+def join(slices, nhwc=True):
+    """The general form: slices = [(a, b or None, a_step, b_step), ...] -> one native node writing the (N, sum of C_j, H, W)
+    tensor in NHWC (channels_last) or NCHW storage; None where the kernels do not apply (join_refusal): the caller keeps its
+    torch expression."""
+    slices = list(slices)
+    if join_refusal(slices) is not None:
+        return None
+    spec = tuple((int(sa), 0 if b is None else int(sb)) for _, b, sa, sb in slices)
+    return Join.apply(spec, bool(nhwc), *[t for a, b, _, _ in slices for t in ((a,) if b is None else (a, b))])
+
+
+def pair_sum(a, b, a_step=1, b_step=1, nhwc=True):
+    """a[:, :, ::a_step, ::a_step] + b[:, :, ::b_step, ::b_step], one intermediate state of a cell, as one native node (or
+    None, as join).  In the backward a source stored as dout is and read at step 1 receives dout itself, without a launch."""
+    return join([(a, b, a_step, b_step)], nhwc)
+
+
+def cell_concat(states, nhwc=True):
+    """torch.cat(states, dim=1), the end of a cell, as one native node (or None, as join)."""
+    return join([(t, None, 1, 1) for t in states], nhwc)
+
+
+def pos_enc(x, w, nhwc=None):
+    """x + w for the (1, C, ks, ks) weight view the GHN assigned, as one native node; the output is stored as x is unless nhwc
+    says otherwise.  None where the kernels do not apply."""
+    if not (torch.is_tensor(x) and torch.is_tensor(w) and x.dim() == 4 and tuple(w.shape) == (1,) + tuple(x.shape[1:])):
+        return None
+    if join_refusal([(x, w if w.is_contiguous() else w.contiguous(), 1, 1)], broadcast_b=True) is not None:
+        return None
+    return PosEnc.apply(x, w, _layout(x) == NHWC if nhwc is None else bool(nhwc))

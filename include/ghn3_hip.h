@@ -664,6 +664,39 @@ int ghn3_xent_fwd(const ghn3_xent_desc* desc, const float* const* logits, const 
 int ghn3_xent_bwd(const ghn3_xent_desc* desc, const float* const* logits, const int64_t* targets, const float* lse,
                   const float* dce, float* const* dlogits, void* stream);
 
+/* ---- target-network joins (ABI v21, added without a version step): a cell's state sums, its concatenation and the positional encoding ------------------
+ * The glue between the layers of a cell (ghn3/ops.py:381-401, 278-291) on the op family's storage.
+ * ghn3_join_fwd: ONE launch writes the dense (N, C, H, W) tensor `out` (layout: 0 = NCHW, 1 = NHWC in memory) made of n_slices
+ * channel slices; slice j covers channels [c0, c0 + C) (the slices are listed in channel order and cover [0, desc.C) without
+ * gaps) and is a or a + b (b.p == NULL: a alone).  A source is a dense fp32 tensor (N, C_j, src.H, src.W) in its own `layout`,
+ * read at pixels (h step, w step), step 1 or 2 -- the `[:, :, ::2, ::2]` of a strided branch, so src.H = H step up to the odd
+ * size's rounding: (src.H + step - 1) / step == H, and the same for W.  broadcast_n: the source is (1, C_j, src.H, src.W) and
+ * is read for every n (the positional encoding's weight).  n_slices == 1 with two sources: the sum of two branch outputs;
+ * single sources: the concatenation; one slice a + broadcast b: x + pos_enc.weight.  Every element is one fp32 add or a copy.
+ * ghn3_join_bwd: ONE launch reads the dense dout (desc's N, C, H, W, layout) and writes, for every source whose `grad` is not
+ * NULL, its gradient as a dense tensor of the source's own layout and full size (N, C_j, src.H, src.W): dout's slice at the
+ * pixels the forward read, zeros at the pixels a step-2 read skipped.  `p` is not read.  A broadcast source takes no gradient
+ * here (GHN3_E_ARG): its gradient is ghn3_posenc_bwd's, a function of its own because it is a reduction, not a copy.
+ * ghn3_posenc_bwd: dw [C][H][W] (dense, NCHW order) = sum over n of dy (N, C, H, W) in `layout`, added in the order
+ * n = 0, 1, ..., one lane per (h, w, four channels): deterministic, no atomics.
+ * Limits (GHN3_E_LIMIT: the caller keeps its torch expression): C_j and c0_j multiples of 4, n_slices <= GHN3_JOIN_MAX_SLICES,
+ * every tensor below 2^31 elements.  An NHWC tensor must start on 16 bytes (GHN3_E_ARG); an NCHW one may start anywhere. */
+#define GHN3_JOIN_MAX_SLICES 16
+typedef struct ghn3_join_src {
+    const float* p;                         /* forward: the source; NULL in slot b: the slice has one source */
+    float* grad;                            /* backward: where this source's gradient goes; NULL: not asked for */
+    int32_t H, W;                           /* the source's own map */
+    int32_t step, layout, broadcast_n, _pad;
+} ghn3_join_src;
+typedef struct ghn3_join_slice { ghn3_join_src a, b; int32_t c0, C; } ghn3_join_slice;
+typedef struct ghn3_join_desc {
+    int32_t N, H, W, C, layout, n_slices;   /* the output (forward) / dout (backward) */
+    ghn3_join_slice s[GHN3_JOIN_MAX_SLICES];
+} ghn3_join_desc;
+int ghn3_join_fwd(const ghn3_join_desc* desc, float* out, void* stream);
+int ghn3_join_bwd(const ghn3_join_desc* desc, const float* dout, void* stream);
+int ghn3_posenc_bwd(int N, int C, int H, int W, int layout, const float* dy, float* dw, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
