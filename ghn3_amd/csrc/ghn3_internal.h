@@ -70,6 +70,8 @@ int ghn3_attn_fwd(float* out, const float* qkv, const float* bias, float* P, con
                   int B, int N, int C, int H, hipStream_t s);
 int ghn3_attn_bwd(float* dqkv, const float* dO, const float* qkv, const float* P, const float* O, float* amax_out,
                   float* dBias, const int* n_nodes, int B, int N, int C, int H, int general, hipStream_t s);
+// tnet_attn.hip: ghn3_attn_lean_fwd / _bwd, the attention of the target networks' msa layers without a saved P.  They are part
+// of the C ABI (ghn3_hip.h), and tnet_msa.hip calls them through those declarations.
 
 int ghn3_graph_prologue(const int64_t* A, int* deg_in, int* deg_out, int* dist0, int* pair,
                         int B, int N, int V, hipStream_t s);

@@ -588,3 +588,153 @@ extern "C" int ghn3_msa_bwd(const ghn3_msa_desc* desc, const float* dout, const 
     return pick_rb(d) == 32 ? bwd_rb<32>(d, dout, x, p, fwd_scratch, P, dx, gg, scratch, s)
                             : bwd_rb<16>(d, dout, x, p, fwd_scratch, P, dx, gg, scratch, s);
 }
+
+// ------------------------------------------------------------------------------------------------ lean attention
+// ghn3_msa_lean_*: the same layer on the attention of tnet_attn.hip, which recomputes the probabilities in the backward from one
+// float per query row (lse) instead of reading a saved P [B][heads][N][N].  Every other kernel runs as above, unchanged.
+namespace {
+
+// check() without its B heads N^2 term -- no tensor of that size exists here.  (Stated in full rather than shared, so that the
+// saved-P entry points and their refusals stay as they are, text included.)
+int check_lean(const ghn3_msa_desc* g, MsaDims* out) {
+    if (!g) { ghn3_set_error("msa lean: null descriptor"); return GHN3_E_ARG; }
+    const ghn3_msa_desc& s = *g;
+    if (s.B <= 0 || s.H <= 0 || s.W <= 0 || s.C <= 0 || s.heads <= 0 || s.hidden <= 0 || s.stride <= 0 || s.Ho <= 0 || s.Wo <= 0) {
+        ghn3_set_error("msa lean: non-positive size in the descriptor");
+        return GHN3_E_ARG;
+    }
+    if (s.layout != 0 && s.layout != 1) { ghn3_set_error("msa lean: layout %d is neither 0 (NCHW) nor 1 (NHWC)", s.layout); return GHN3_E_ARG; }
+    if (s.Ho != (s.H - 1) / s.stride + 1 || s.Wo != (s.W - 1) / s.stride + 1) {
+        ghn3_set_error("msa lean: output grid %d x %d does not match H, W, stride", s.Ho, s.Wo);
+        return GHN3_E_ARG;
+    }
+    const int64_t N = (int64_t)s.H * s.W;
+    if (s.C % 4 || s.C > 256 || s.C % s.heads || s.C / s.heads > 32) {
+        ghn3_set_error("msa lean: needs C %% 4 == 0, C <= 256, C %% heads == 0 and head dim <= 32 (C %d, heads %d)", s.C, s.heads);
+        return GHN3_E_LIMIT;
+    }
+    if (N > 4096) { ghn3_set_error("msa lean: %lld tokens per sequence (limit 4096)", (long long)N); return GHN3_E_LIMIT; }
+    if (s.hidden % 4 || s.hidden > 1024) { ghn3_set_error("msa lean: hidden %d not a multiple of 4 or above 1024", s.hidden); return GHN3_E_LIMIT; }
+    const int64_t R = s.B * N;
+    if (s.B > 65535 || R * 3 * s.C >= (1ll << 31) || R * s.hidden >= (1ll << 31)) {
+        ghn3_set_error("msa lean: more than 65535 sequences, or activations of 2^31 elements or more");
+        return GHN3_E_LIMIT;
+    }
+    if (out) {
+        *out = MsaDims{s.B, s.H, s.W, s.C, s.heads, s.hidden, s.stride, s.Ho, s.Wo, s.layout, s.eps, (int)N, (int)R,
+                       s.B * s.Ho * s.Wo};
+    }
+    return GHN3_OK;
+}
+
+// forward scratch: the saved-P layout, then lse [B][heads][N] (the last section: not rounded up, so that the lean state is never
+// larger than the saved-P path's scratch and P together, a single token included)
+int64_t lean_lse_off(const MsaDims& d) { return fwd_layout(d).total; }
+int64_t lean_fwd_total(const MsaDims& d) { return lean_lse_off(d) + (int64_t)d.B * d.heads * d.N; }
+
+template <int RB>
+int lean_fwd_rb(const MsaDims& d, const float* x, const ghn3_msa_params& p, float* out, float* scratch, bool save, hipStream_t s) {
+    const FwdLayout f = fwd_layout(d);
+    int rc;
+    if ((rc = tnet_raise_lds(msa_ln_qkv_kernel<RB>, MAX_LDS))) return rc;
+    hipLaunchKernelGGL(msa_ln_qkv_kernel<RB>, dim3((d.R + RB - 1) / RB), dim3(NT), (size_t)RB * (r16(d.C) + 4) * 4, s, d, x, p,
+                       scratch + f.qkv, scratch + f.stats1, reinterpret_cast<int*>(scratch + f.nn));
+    TNET_LAUNCH_CHECK("msa lean ln_qkv");
+    if ((rc = ghn3_attn_lean_fwd(scratch + f.O, save ? scratch + lean_lse_off(d) : nullptr, scratch + f.qkv, d.B, d.N, d.C,
+                                 d.heads, s)))
+        return rc;
+    if ((rc = tnet_raise_lds(msa_post_kernel<RB>, MAX_LDS))) return rc;
+    hipLaunchKernelGGL(msa_post_kernel<RB>, dim3((d.Kr + RB - 1) / RB), dim3(NT), (size_t)lds_post(RB, d), s, d, x,
+                       (const float*)(scratch + f.O), p, out, save ? scratch + f.y1 : nullptr,
+                       save ? scratch + f.stats2 : nullptr, save ? scratch + f.pre : nullptr);
+    TNET_LAUNCH_CHECK("msa lean post");
+    return GHN3_OK;
+}
+
+template <int RB>
+int lean_bwd_rb(const MsaDims& d, const float* dout, const float* x, const ghn3_msa_params& p, const float* fs, float* dx,
+                const ghn3_msa_grads& g, float* scratch, hipStream_t s) {
+    const FwdLayout f = fwd_layout(d);
+    const BwdLayout b = bwd_layout(d);
+    int rc;
+    if (d.Kr != d.R) {                           // (dropped rows: no gradient reaches them through y)
+        hipError_t e = hipMemsetAsync(scratch + b.dO, 0, (size_t)(b.dy1 - b.dO + (int64_t)d.R * d.C) * sizeof(float), s);  // dO, dy1
+        if (e != hipSuccess) { ghn3_set_error("msa lean bwd: hipMemsetAsync: %s", hipGetErrorString(e)); return GHN3_E_HIP; }
+    }
+    const int nb_post = (d.Kr + RB - 1) / RB, nb_rows = (d.R + RB - 1) / RB;
+    if ((rc = tnet_raise_lds(msa_post_bwd_kernel<RB>, MAX_LDS))) return rc;
+    hipLaunchKernelGGL(msa_post_bwd_kernel<RB>, dim3(nb_post), dim3(NT), (size_t)lds_post_bwd(RB, d), s, d, dout, p,
+                       fs + f.y1, fs + f.stats2, fs + f.pre, scratch + b.dh, scratch + b.gact, scratch + b.a2, scratch + b.dy1,
+                       scratch + b.dO, scratch + b.ln2);
+    TNET_LAUNCH_CHECK("msa lean post bwd");
+    if ((rc = ghn3_attn_lean_bwd(scratch + b.dqkv, scratch + b.dO, fs + f.qkv, fs + lean_lse_off(d), fs + f.O, d.B, d.N, d.C,
+                                 d.heads, s)))
+        return rc;
+    if ((rc = tnet_raise_lds(msa_qkv_bwd_kernel<RB>, MAX_LDS))) return rc;
+    hipLaunchKernelGGL(msa_qkv_bwd_kernel<RB>, dim3(nb_rows), dim3(NT), (size_t)lds_qkv_bwd(RB, d), s, d, x, p,
+                       (const float*)(scratch + b.dqkv), fs + f.stats1, (const float*)(scratch + b.dy1), scratch + b.a1, dx,
+                       scratch + b.ln1);
+    TNET_LAUNCH_CHECK("msa lean qkv bwd");
+    const TnetWgProb wg[4] = {
+        {scratch + b.dqkv, scratch + b.a1, scratch + b.pq, g.w_qkv, g.b_qkv, d.R, 3 * d.C, d.C, g.b_qkv != nullptr},
+        {scratch + b.dy1, fs + f.O, scratch + b.po, g.w_o, g.b_o, d.R, d.C, d.C, 1},
+        {scratch + b.dh, scratch + b.a2, scratch + b.p1, g.w1, g.b1, d.Kr, d.hidden, d.C, 1},
+        {dout, scratch + b.gact, scratch + b.p2, g.w2, g.b2, d.Kr, d.C, d.hidden, 1},
+    };
+    if ((rc = tnet_wgrad_launch(wg, 4, s))) return rc;
+    const TnetRedProb red[6] = {
+        tnet_wg_reduce(wg[0]), tnet_wg_reduce(wg[1]), tnet_wg_reduce(wg[2]), tnet_wg_reduce(wg[3]),
+        {scratch + b.ln1, g.ln1_w, g.ln1_b, nb_rows, 2 * d.C, d.C, d.C, 1},
+        {scratch + b.ln2, g.ln2_w, g.ln2_b, nb_post, 2 * d.C, d.C, d.C, 1},
+    };
+    return tnet_reduce_launch(red, 6, s);
+}
+
+}  // namespace
+
+extern "C" int64_t ghn3_msa_lean_scratch_floats(const ghn3_msa_desc* desc, int backward) {
+    MsaDims d;
+    const int rc = check_lean(desc, &d);
+    if (rc) return rc;
+    return backward ? bwd_layout(d).total : lean_fwd_total(d);
+}
+
+extern "C" int ghn3_msa_lean_fwd(const ghn3_msa_desc* desc, const float* x, const ghn3_msa_params* params, float* out,
+                                 float* scratch, int save, void* stream) {
+    MsaDims d;
+    int rc = check_lean(desc, &d);
+    if (rc) return rc;
+    if (!x || !out || !scratch || !params_ok(params, desc->has_qkv_bias) || !a16(x) || !a16(scratch)) {
+        ghn3_set_error("msa lean fwd: null or misaligned pointer (x, scratch and the weight matrices need 16-byte alignment)");
+        return GHN3_E_ARG;
+    }
+    ghn3_msa_params p = *params;
+    if (!desc->has_qkv_bias) p.b_qkv = nullptr;
+    hipStream_t s = (hipStream_t)stream;
+    return pick_rb(d) == 32 ? lean_fwd_rb<32>(d, x, p, out, scratch, save != 0, s)
+                            : lean_fwd_rb<16>(d, x, p, out, scratch, save != 0, s);
+}
+
+extern "C" int ghn3_msa_lean_bwd(const ghn3_msa_desc* desc, const float* dout, const float* x, const ghn3_msa_params* params,
+                                 const float* fwd_scratch, float* dx, const ghn3_msa_grads* grads, float* scratch, void* stream) {
+    MsaDims d;
+    int rc = check_lean(desc, &d);
+    if (rc) return rc;
+    if (!dout || !x || !fwd_scratch || !dx || !scratch || !grads || !params_ok(params, desc->has_qkv_bias) || !a16(dout) ||
+        !a16(x) || !a16(fwd_scratch) || !a16(dx) || !a16(scratch)) {
+        ghn3_set_error("msa lean bwd: null or misaligned pointer");
+        return GHN3_E_ARG;
+    }
+    const ghn3_msa_grads& g = *grads;
+    if (!g.ln1_w || !g.ln1_b || !g.w_qkv || (desc->has_qkv_bias && !g.b_qkv) || !g.w_o || !g.b_o || !g.ln2_w || !g.ln2_b ||
+        !g.w1 || !g.b1 || !g.w2 || !g.b2) {
+        ghn3_set_error("msa lean bwd: null gradient pointer");
+        return GHN3_E_ARG;
+    }
+    ghn3_msa_params p = *params;
+    ghn3_msa_grads gg = g;
+    if (!desc->has_qkv_bias) { p.b_qkv = nullptr; gg.b_qkv = nullptr; }
+    hipStream_t s = (hipStream_t)stream;
+    return pick_rb(d) == 32 ? lean_bwd_rb<32>(d, dout, x, p, fwd_scratch, dx, gg, scratch, s)
+                            : lean_bwd_rb<16>(d, dout, x, p, fwd_scratch, dx, gg, scratch, s);
+}

@@ -686,11 +686,73 @@ def _msa_modules(layer):
     return (layer.ln1, attn.to_qkv, to_out[0], layer.ln2, net[0], net[3], (attn.attn_drop, to_out[1], net[2], net[4]), net[1])
 
 
+# ---- attention without a saved P ("lean": ghn3_attn_lean_* / ghn3_msa_lean_*, ghn3_amd/csrc/tnet_attn.hip) -----------------------
+# The saved-P path keeps the attention probabilities, B heads N^2 floats per layer, for its backward and refuses 2^31 elements or
+# more; the lean path keeps one float per query row and recomputes P, so it reaches those shapes.  MSA_LEAN_THRESHOLD is the
+# element count of P from which `auto` takes the lean path.  It is 2^31: the default adds only the shapes the saved-P path
+# refuses.  The measurement (profiles/r09a_tnet_msa_lean.txt) has the lean path level below 2^24 elements and faster from 3.4e7
+# on (0.87 of the saved-P time there, 0.62 - 0.76 at 5e8 - 6e8), so its rule would allow 2^24 -- never less: the shapes of the
+# layer tests, at most 64 * 8 * 121^2 = 7.5e6, stay on the saved-P path under the default setting --, but the whole GPU suite has
+# not been run with a lower value yet, and until it has the default moves no existing shape to another kernel.
+MSA_LEAN_THRESHOLD = 2 ** 31
+
+
+def msa_lean(B, heads, N):
+    """Whether an msa layer of B sequences of N tokens runs on the lean attention.  GHN3_MSA_LEAN=0: never (the saved-P path
+    with its refusal at 2^31 elements of P); 1: wherever the lean limits allow; auto (default): iff B heads N^2 >=
+    MSA_LEAN_THRESHOLD.  The rule reads the shape and the environment only -- never the grad mode: a no_grad forward and a
+    training forward of one layer take the same attention kernel and agree bit for bit."""
+    mode = os.environ.get('GHN3_MSA_LEAN', 'auto')
+    if mode == '0':
+        return False
+    if mode == '1':
+        return True
+    return B * heads * N * N >= MSA_LEAN_THRESHOLD
+
+
+class LeanAttention(torch.autograd.Function):
+    """Plain multi-head self-attention softmax(q k^T / sqrt(d)) v on qkv (B, N, 3 C) -- columns q | k | v, head h at columns
+    h d .. h d + d - 1 of each -- returning (B, N, C), on ghn3_attn_lean_fwd / _bwd: the backward recomputes the probabilities
+    from qkv and one saved float per query row.  fp32 CUDA tensors, C % 4 == 0, d = C / heads <= 32, N <= 4096."""
+
+    @staticmethod
+    def forward(ctx, qkv, heads):
+        if not (torch.is_tensor(qkv) and qkv.is_cuda and qkv.dtype == torch.float32 and qkv.dim() == 3 and qkv.shape[2] % 3 == 0):
+            raise L.Ghn3Error('lean_attention takes a float32 CUDA tensor (B, N, 3 C); there is no other implementation')
+        lib = L.load()
+        q = _aligned(qkv.contiguous())
+        B, N, C = q.shape[0], q.shape[1], q.shape[2] // 3
+        out = torch.empty((B, N, C), dtype=torch.float32, device=q.device)
+        lse = torch.empty((B, heads, N), dtype=torch.float32, device=q.device) if ctx.needs_input_grad[0] else None
+        L._check(lib.ghn3_attn_lean_fwd(_ptr(out), None if lse is None else _ptr(lse), _ptr(q), B, N, C, heads, _stream()),
+                 'ghn3_attn_lean_fwd')
+        if lse is not None:
+            ctx.save_for_backward(q, lse, out)
+            ctx.heads = heads
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, lse, out = ctx.saved_tensors
+        B, N, C = out.shape
+        do = _aligned(dout.contiguous())
+        dqkv = torch.empty_like(q)
+        L._check(L.load().ghn3_attn_lean_bwd(_ptr(dqkv), _ptr(do), _ptr(q), _ptr(lse), _ptr(out), B, N, C, ctx.heads, _stream()),
+                 'ghn3_attn_lean_bwd')
+        return dqkv, None
+
+
+def lean_attention(qkv, heads):
+    """LeanAttention as a function: qkv (B, N, 3 C) -> (B, N, C)."""
+    return LeanAttention.apply(qkv, int(heads))
+
+
 class MsaLayer(torch.autograd.Function):
     """The pre-LN transformer layer of the ViT-style target networks -- the `msa` op, ops._TransformerLayer with edge_dim = 0
     (graphormer.py:144-248) -- as ONE autograd node on ghn3_msa_fwd / _bwd (ghn3_amd/csrc/tnet_msa.hip): x (B, C, H, W) in NCHW or
     channels_last storage, read as it is; the output (B, C, Ho, Wo) in channels_last storage.  The twelve tensors (MSA_PARAM_NAMES;
-    b_qkv may be None) are read in place; their gradients leave as tensors of their own."""
+    b_qkv may be None) are read in place; their gradients leave as tensors of their own.  Where `msa_lean` says so the node runs
+    on ghn3_msa_lean_fwd / _bwd instead: no P tensor exists, and B heads N^2 may be anything."""
 
     @staticmethod
     def applicable(layer, x):
@@ -722,7 +784,8 @@ class MsaLayer(torch.autograd.Function):
                 (ln2.weight, (C,)), (ln2.bias, (C,)), (ff1.weight, (hidden, C)), (ff1.bias, (hidden,)), (ff2.weight, (C, hidden)),
                 (ff2.bias, (C,))] + ([] if qkv.bias is None else [(qkv.bias, (3 * C,))])
         return all(tuple(t.shape) == s for t, s in want) and hidden % 4 == 0 and hidden <= 1024 and \
-            B * H * W * 3 * C < 2 ** 31 and B * H * W * hidden < 2 ** 31 and B * heads * (H * W) ** 2 < 2 ** 31
+            B * H * W * 3 * C < 2 ** 31 and B * H * W * hidden < 2 ** 31 and \
+            (B <= 65535 if msa_lean(B, heads, H * W) else B * heads * (H * W) ** 2 < 2 ** 31)
 
     @staticmethod
     def forward(ctx, x, cfg, *params):
@@ -736,6 +799,15 @@ class MsaLayer(torch.autograd.Function):
         d = _MsaDesc(B, H, W, C, heads, int(ps[8].shape[0]), stride, Ho, Wo, layout, float(eps), int(ps[3] is not None))
         dev = x.device
         out = torch.empty((B, C, Ho, Wo), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
+        if msa_lean(B, heads, H * W):
+            # (lse instead of P; it and everything else the backward reads only when the layer is differentiated)
+            scratch = torch.empty(_scratch_floats('ghn3_msa_lean_scratch_floats', d, 0), dtype=torch.float32, device=dev)
+            L._check(lib.ghn3_msa_lean_fwd(ctypes.byref(d), _ptr(xc), ctypes.byref(_msa_ptrs(ps)), _ptr(out), _ptr(scratch),
+                                           int(train), _stream()), 'ghn3_msa_lean_fwd')
+            if train:
+                ctx.save_for_backward(xc, scratch, None, *ps)
+                ctx.desc = d
+            return out
         scratch = torch.empty(_scratch_floats('ghn3_msa_scratch_floats', d, 0), dtype=torch.float32, device=dev)
         # (P and everything the backward reads only when the layer is differentiated)
         P = torch.empty(B * heads * H * W * H * W, dtype=torch.float32, device=dev) if train else None
@@ -754,6 +826,11 @@ class MsaLayer(torch.autograd.Function):
         do = _aligned(dout.contiguous(memory_format=torch.channels_last))
         dx = torch.empty_like(xc)
         grads = [None if t is None else torch.empty_like(t, memory_format=torch.contiguous_format) for t in ps]
+        if P is None:                                      # (the forward ran on the lean attention)
+            bscratch = torch.empty(_scratch_floats('ghn3_msa_lean_scratch_floats', d, 1), dtype=torch.float32, device=xc.device)
+            L._check(lib.ghn3_msa_lean_bwd(ctypes.byref(d), _ptr(do), _ptr(xc), ctypes.byref(_msa_ptrs(ps)), _ptr(scratch), _ptr(dx),
+                                           ctypes.byref(_msa_ptrs(grads)), _ptr(bscratch), _stream()), 'ghn3_msa_lean_bwd')
+            return (dx, None) + tuple(grads)
         bscratch = torch.empty(_scratch_floats('ghn3_msa_scratch_floats', d, 1), dtype=torch.float32, device=xc.device)
         L._check(lib.ghn3_msa_bwd(ctypes.byref(d), _ptr(do), _ptr(xc), ctypes.byref(_msa_ptrs(ps)), _ptr(scratch), _ptr(P),
                                   _ptr(dx), ctypes.byref(_msa_ptrs(grads)), _ptr(bscratch), _stream()), 'ghn3_msa_bwd')

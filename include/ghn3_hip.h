@@ -616,6 +616,26 @@ int ghn3_msa_fwd(const ghn3_msa_desc* desc, const float* x, const ghn3_msa_param
 int ghn3_msa_bwd(const ghn3_msa_desc* desc, const float* dout, const float* x, const ghn3_msa_params* params,
                  const float* fwd_scratch, const float* P, float* dx, const ghn3_msa_grads* grads, float* scratch, void* stream);
 
+/* ---- msa without a saved P ("lean" attention; entry points added without an ABI version step) ------------------------------
+ * Plain multi-head self-attention on qkv [B N][3 C] (row = token, columns q | k | v, head h at columns h d .. h d + d - 1 of
+ * each): no bias, no padding, scale 1 / sqrt(d), d = C / heads.  The forward writes out [B N][C] and, when lse != NULL,
+ * lse [B][heads][N] = ln sum_j exp(scale q_i . k_j), one float per query row; the backward recomputes the probabilities from
+ * qkv and lse (and reads the forward's output O for delta = rowsum(dO . O)) and writes EVERY element of dqkv [B N][3 C]: the
+ * state kept between the two is O(N) per sequence where ghn3_msa_fwd's P is O(N^2).  Exact fp32 products (tnet_attn.hip), no
+ * float atomics.  Limits (GHN3_E_LIMIT): C % 4 == 0, C % heads == 0, d <= 32, 1 <= N <= 4096, B and heads <= 65535.
+ * ghn3_msa_lean_* are ghn3_msa_* on that attention: same descriptor, parameters, gradients, layouts and limits, except that
+ * B heads N^2 may be anything (no tensor of that size exists).  The forward scratch (ghn3_msa_lean_scratch_floats(desc, 0)
+ * floats) holds lse next to what ghn3_msa_fwd's holds; save == 0 is inference: nothing is kept for a backward and lse is not
+ * written.  ghn3_msa_lean_bwd takes only a forward scratch written with save != 0. */
+int ghn3_attn_lean_fwd(float* out, float* lse, const float* qkv, int B, int N, int C, int heads, void* stream);
+int ghn3_attn_lean_bwd(float* dqkv, const float* dO, const float* qkv, const float* lse, const float* O, int B, int N, int C,
+                       int heads, void* stream);
+int64_t ghn3_msa_lean_scratch_floats(const ghn3_msa_desc* desc, int backward); /* host only; < 0: outside the limits */
+int ghn3_msa_lean_fwd(const ghn3_msa_desc* desc, const float* x, const ghn3_msa_params* params, float* out, float* scratch,
+                      int save, void* stream);
+int ghn3_msa_lean_bwd(const ghn3_msa_desc* desc, const float* dout, const float* x, const ghn3_msa_params* params,
+                      const float* fwd_scratch, float* dx, const ghn3_msa_grads* grads, float* scratch, void* stream);
+
 /* ---- target-network end (ABI v21): the classifier head and the meta-batch cross-entropy ------------------------------------
  * The head of every network (ghn3/ops.py:565-569; global pooling + `classifier`, built at ops.py:489-494), forward and backward:
  *   f = mean_{h,w} x (glob_avg = 1) or x flattened in logical NCHW order, feature c H W + h W + w (glob_avg = 0);
