@@ -530,7 +530,7 @@ __global__ __launch_bounds__(512, 2) void gemm_p8_kernel(const GemmProbDev* __re
 #ifdef GHN3_P8W_PROBE
 __device__ long long g_p8w_probe[48];
 #endif
-template <int CT, int QUIET>
+template <int CT>
 __global__ __launch_bounds__(512, 2) void gemm_p8w_kernel(const GemmProbDev* __restrict__ probs, int n_probs, int total_tiles_all,
                                                            int vgrid, int tpw) {
     constexpr int MI = 4, BK = 64;
@@ -546,8 +546,6 @@ __global__ __launch_bounds__(512, 2) void gemm_p8w_kernel(const GemmProbDev* __r
     // walks tpw of them and exits -- the launch then has vgrid * chunks workgroups that the dispatcher starts in order as CUs
     // free up, so a higher-priority stream (the dependent chain this weight gradient runs beside) gets CUs every few tiles
     // instead of never, at the price of one un-overlapped prologue / store phase per tpw tiles.
-    const bool nt_store = rfl(tpw >> 30) != 0;      // (GHN3_WGRAD_NT=1: streaming stores of the 1.8 GB output; experiment)
-    tpw &= 0x3fffffff;
     const int stride = vgrid;
     const int w_v = (int)blockIdx.x % vgrid, w_c = (int)blockIdx.x / vgrid;
     const int t_first = w_v + vgrid * w_c * tpw;
@@ -742,8 +740,7 @@ __global__ __launch_bounds__(512, 2) void gemm_p8w_kernel(const GemmProbDev* __r
 #if defined(GHN3_P8W_PROBE) && defined(P8W_X)
                         if (P8W_X == 2) { asm volatile("" :: "v"(v[u][h])); } else     // (tools/p8w_probe: 2 = no store instruction)
 #endif
-                        if (nt_store) __builtin_nontemporal_store(v[u][h], reinterpret_cast<gf4>(dst));
-                        else *reinterpret_cast<gf4>(dst) = v[u][h];
+                        *reinterpret_cast<gf4>(dst) = v[u][h];
                     }
                 }
         }
@@ -787,18 +784,16 @@ __global__ __launch_bounds__(512, 2) void gemm_p8w_kernel(const GemmProbDev* __r
 #endif
         const char* ring = sm + (G & 1) * KT;
         const bool st = first && p_valid;
-        // QUIET store k-tile (round 5, default; GHN3_P8W_QUIET=0 turns it off): stores and LDS-DMA share the wave's vmcnt, so a counted
+        // QUIET store k-tile (round 5; profiles/r05h_ab_wgrad_quiet_store_ktile.txt): stores and LDS-DMA share the wave's vmcnt, so a counted
         // wait behind stores also waits for their write acknowledgements -- in the k-tile that carries a tile's 256 KB of
         // stores that wait (and the store instructions queueing behind DMA requests) cost most of its 21-27k cycles.  Quiet:
         // the k-tile first lets everything in flight land (one exposed round trip for the newest half-tile), issues NO DMA
         // while it stores, and issues its three half-tiles at its very end; the first counted wait that sees the stores
         // again is the next k-tile's, a whole k-tile later.
-        const bool quiet = QUIET && st;
 #ifdef GHN3_P8W_PROBE
         if (st) pr_last = P8W_CLK();
 #endif
-        if (!quiet) {
-            if (st) P8W_ST_T(store_prev(0, 0));
+        if (!st) {
             read_b(ring, 0);                          // (first: retired by the counted lgkmcnt below)
             __builtin_amdgcn_sched_barrier(0);
             read_a(ring, 0);
@@ -833,20 +828,18 @@ __global__ __launch_bounds__(512, 2) void gemm_p8w_kernel(const GemmProbDev* __r
         P8W_MARK(4);
         P8W_BAR_T();
         P8W_MARK(5);
-        if (st && !quiet) P8W_ST_T(store_prev(0, 1));
         P8W_MARK(6);
         read_b(ring, 1);
-        if (!quiet) issue(0);
+        if (!st) issue(0);
         P8W_BAR_T();
         P8W_MARK(7);
         mfma_q(0, 1, first);
         P8W_MARK(8);
         P8W_BAR_T();
         P8W_MARK(9);
-        if (st && !quiet) P8W_ST_T(store_prev(1, 1));
         P8W_MARK(10);
         read_a(ring, 1);
-        if (!quiet) issue(1);
+        if (!st) issue(1);
         P8W_BAR_T();
         P8W_MARK(11);
         mfma_q(1, 1, first);
@@ -856,13 +849,12 @@ __global__ __launch_bounds__(512, 2) void gemm_p8w_kernel(const GemmProbDev* __r
 #ifdef GHN3_P8W_PROBE
         const long long pr_w0 = P8W_CLK();
 #endif
-        if (!quiet) { issue(2); wait_next_ktile(); }
+        if (!st) { issue(2); wait_next_ktile(); }
 #ifdef GHN3_P8W_PROBE
         pr_wait[st ? 0 : 1] += P8W_CLK() - pr_w0;
 #endif
-        if (st && !quiet) { P8W_ST_T(store_prev(1, 0)); finish_sq(); }    // (behind the wait: these stores are not waited for with the DMA)
         P8W_MARK(14);
-        if (quiet) { issue(0); issue(1); issue(2); }  // (k-tile G + 1 had landed before the stores; these are for G + 2)
+        if (st) { issue(0); issue(1); issue(2); }     // (k-tile G + 1 had landed before the stores; these are for G + 2)
         P8W_BAR_T();
         P8W_MARK(15);
         mfma_q(1, 0, first);
@@ -1243,13 +1235,9 @@ int ghn3_gemm_p8_init() {
     if (e == hipSuccess)
         e = hipFuncSetAttribute((const void*)gemm_p8_kernel<GHN3_CT_BF16>, hipFuncAttributeMaxDynamicSharedMemorySize, kP8Lds);
     if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)gemm_p8w_kernel<GHN3_CT_F16, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, kP8wLds);
+        e = hipFuncSetAttribute((const void*)gemm_p8w_kernel<GHN3_CT_F16>, hipFuncAttributeMaxDynamicSharedMemorySize, kP8wLds);
     if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)gemm_p8w_kernel<GHN3_CT_BF16, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, kP8wLds);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)gemm_p8w_kernel<GHN3_CT_F16, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, kP8wLds);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)gemm_p8w_kernel<GHN3_CT_BF16, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, kP8wLds);
+        e = hipFuncSetAttribute((const void*)gemm_p8w_kernel<GHN3_CT_BF16>, hipFuncAttributeMaxDynamicSharedMemorySize, kP8wLds);
     if (e == hipSuccess)
         e = hipFuncSetAttribute((const void*)gemm_p8d_kernel<GHN3_CT_F16>, hipFuncAttributeMaxDynamicSharedMemorySize, kP8dLds);
     if (e == hipSuccess)
@@ -1303,23 +1291,12 @@ int ghn3_gemm_p8w_launch(const GemmProbDev* d_probs, int n_probs, int total_tile
     if (total_tiles >= 8 && grid % 8) grid = 8;
     const int per_worker = (total_tiles + grid - 1) / grid;
     const int chunks = tpw > 0 ? (per_worker + tpw - 1) / tpw : 1;
-    static const int nt = getenv("GHN3_WGRAD_NT") ? atoi(getenv("GHN3_WGRAD_NT")) != 0 : 0;
-    const int tpw_arg = tpw | (nt << 30);
-    // quiet store k-tile (see the kernel): on by default since round 5 -- 0.95-0.97 -> 0.91-0.93 ms for the ghn3xlm16 bench
-    // workload, bit-identical results (profiles/r05h_ab_wgrad_quiet_store_ktile.txt); GHN3_P8W_QUIET=0 = the round-4 loop
-    static const int quiet = getenv("GHN3_P8W_QUIET") ? atoi(getenv("GHN3_P8W_QUIET")) != 0 : 1;
-    if (ctype == GHN3_CT_F16 && quiet)
-        hipLaunchKernelGGL((gemm_p8w_kernel<GHN3_CT_F16, 1>), dim3(grid * chunks), dim3(512), kP8wLds, stream, d_probs, n_probs,
-                           total_tiles, grid, tpw_arg);
-    else if (ctype == GHN3_CT_F16)
-        hipLaunchKernelGGL((gemm_p8w_kernel<GHN3_CT_F16, 0>), dim3(grid * chunks), dim3(512), kP8wLds, stream, d_probs, n_probs,
-                           total_tiles, grid, tpw_arg);
-    else if (quiet)
-        hipLaunchKernelGGL((gemm_p8w_kernel<GHN3_CT_BF16, 1>), dim3(grid * chunks), dim3(512), kP8wLds, stream, d_probs, n_probs,
-                           total_tiles, grid, tpw_arg);
+    if (ctype == GHN3_CT_F16)
+        hipLaunchKernelGGL(gemm_p8w_kernel<GHN3_CT_F16>, dim3(grid * chunks), dim3(512), kP8wLds, stream, d_probs, n_probs,
+                           total_tiles, grid, tpw);
     else
-        hipLaunchKernelGGL((gemm_p8w_kernel<GHN3_CT_BF16, 0>), dim3(grid * chunks), dim3(512), kP8wLds, stream, d_probs, n_probs,
-                           total_tiles, grid, tpw_arg);
+        hipLaunchKernelGGL(gemm_p8w_kernel<GHN3_CT_BF16>, dim3(grid * chunks), dim3(512), kP8wLds, stream, d_probs, n_probs,
+                           total_tiles, grid, tpw);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { ghn3_set_error("p8w gemm launch: %s", hipGetErrorString(e)); return GHN3_E_HIP; }
     return GHN3_OK;

@@ -59,9 +59,6 @@ struct ghn3_ctx {
     GemmProbDev* d_stage[kStageSlots];
     hipEvent_t ev[kStageSlots];        // the slot's upload has completed (host buffer reusable)
     bool ev_used[kStageSlots];
-    hipEvent_t ev_done[kStageSlots];   // the run that used the slot has been fully enqueued behind this event
-    bool done_used[kStageSlots];
-    hipStream_t copy;                  // problem tables are uploaded here, ahead of the stream that will read them
     size_t cap;            // problems per slot
     int ctype;             // compute type for GEMM operands
     // profiling: 0 off, 1 = every op bracketed + synchronised (diagnostic), 2 = only ops carrying
@@ -88,7 +85,6 @@ static int ctx_reserve(ghn3_ctx* c, size_t n) {
     size_t cap = std::max<size_t>(n, 1024);
     for (int i = 0; i < kStageSlots; ++i) {
         if (c->ev_used[i]) { HIPCHK(hipEventSynchronize(c->ev[i])); c->ev_used[i] = false; }
-        if (c->done_used[i]) { HIPCHK(hipEventSynchronize(c->ev_done[i])); c->done_used[i] = false; }
         if (c->h_stage[i]) HIPCHK(hipHostFree(c->h_stage[i]));
         if (c->d_stage[i]) HIPCHK(hipFree(c->d_stage[i]));
         c->h_stage[i] = nullptr; c->d_stage[i] = nullptr;
@@ -111,11 +107,7 @@ extern "C" int ghn3_ctx_create(ghn3_ctx** out) {
     c->pool = new std::vector<hipEvent_t>();
     c->pool_tag = new std::vector<int>();
     c->cache = new SlotCache[kStageSlots];
-    for (int i = 0; i < kStageSlots; ++i) {
-        HIPCHK(hipEventCreateWithFlags(&c->ev[i], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&c->ev_done[i], hipEventDisableTiming));
-    }
-    HIPCHK(hipStreamCreateWithFlags(&c->copy, hipStreamNonBlocking));
+    for (int i = 0; i < kStageSlots; ++i) HIPCHK(hipEventCreateWithFlags(&c->ev[i], hipEventDisableTiming));
     HIPCHK(hipEventCreate(&c->pe0));
     HIPCHK(hipEventCreate(&c->pe1));
     {
@@ -151,9 +143,7 @@ extern "C" void ghn3_ctx_destroy(ghn3_ctx* c) {
         if (c->h_stage[i]) hipHostFree(c->h_stage[i]);
         if (c->d_stage[i]) hipFree(c->d_stage[i]);
         hipEventDestroy(c->ev[i]);
-        hipEventDestroy(c->ev_done[i]);
     }
-    hipStreamDestroy(c->copy);
     hipEventDestroy(c->pe0);
     hipEventDestroy(c->pe1);
     hipStreamSynchronize(c->side);
@@ -288,8 +278,6 @@ extern "C" int ghn3_run(ghn3_ctx* c, const ghn3_op* ops, int n_ops, const ghn3_g
     for (int k = 0; k < n_ops; ++k)
         if (ops[k].kind == GHN3_OP_GEMM) need += (size_t)ops[k].i[1];
     GemmProbDev* hs = nullptr; GemmProbDev* ds = nullptr;
-    int used_slot = -1;
-    static const bool use_copy_stream = getenv("GHN3_COPY_STREAM") && atoi(getenv("GHN3_COPY_STREAM")) != 0;
     static const bool use_cache = !(getenv("GHN3_RUN_CACHE") && atoi(getenv("GHN3_RUN_CACHE")) == 0);
     int hit = -1;
     if (need > 0) {
@@ -313,7 +301,6 @@ extern "C" int ghn3_run(ghn3_ctx* c, const ghn3_op* ops, int n_ops, const ghn3_g
         hs = c->h_stage[hit]; ds = c->d_stage[hit];
         launches = &e.launches;
         if (e.up_stream != stream && c->ev_used[hit]) HIPCHK(hipStreamWaitEvent(stream, c->ev[hit], 0));
-        if (use_copy_stream) used_slot = hit;
     } else if (need > 0) {
         int slot = 0;                                    // the least recently used slot (never used ones first)
         for (int i = 1; i < kStageSlots; ++i)
@@ -566,23 +553,11 @@ extern "C" int ghn3_run(ghn3_ctx* c, const ghn3_op* ops, int n_ops, const ghn3_g
                     }
         }
         if (R.bad) { ghn3_set_error("ghn3_run: a GEMM problem references an absent buffer"); return GHN3_E_ARG; }
-        // Upload on the copy stream: stream-ordered behind `stream` the ~100 KB table sat on the critical path of every run
-        // (in 4 KB pieces: ~170 us in front of the backward program).  The copy stream only waits for the kernels of the
-        // run that used this slot last (kStageSlots runs ago); `stream` waits for the copy.
-        // (GHN3_COPY_STREAM=1: upload on a separate copy stream ahead of `stream`; measured 9.11 vs 9.02 ms per step --
-        // the host runs far enough ahead that the in-stream copy is never waited for -- so off by default)
-        if (use_copy_stream) {
-            if (c->done_used[slot]) HIPCHK(hipStreamWaitEvent(c->copy, c->ev_done[slot], 0));
-            HIPCHK(hipMemcpyAsync(ds, hs, pos * sizeof(GemmProbDev), hipMemcpyHostToDevice, c->copy));
-            HIPCHK(hipEventRecord(c->ev[slot], c->copy));
-            c->ev_used[slot] = true;
-            HIPCHK(hipStreamWaitEvent(stream, c->ev[slot], 0));
-            used_slot = slot;
-        } else {
-            HIPCHK(hipMemcpyAsync(ds, hs, pos * sizeof(GemmProbDev), hipMemcpyHostToDevice, stream));
-            HIPCHK(hipEventRecord(c->ev[slot], stream));
-            c->ev_used[slot] = true;
-        }
+        // Upload in `stream` itself: the host runs far enough ahead that the copy is never waited for, and a run that repeats
+        // finds its table on the device (SlotCache), so a separate copy stream gains nothing (docs/EXPERIMENTS.md, round 6).
+        HIPCHK(hipMemcpyAsync(ds, hs, pos * sizeof(GemmProbDev), hipMemcpyHostToDevice, stream));
+        HIPCHK(hipEventRecord(c->ev[slot], stream));
+        c->ev_used[slot] = true;
         if (use_cache) {
             SlotCache& e = c->cache[slot];
             e.n_ops = n_ops; e.n_problems = n_problems; e.n_bufs = n_bufs;
@@ -591,7 +566,7 @@ extern "C" int ghn3_run(ghn3_ctx* c, const ghn3_op* ops, int n_ops, const ghn3_g
             e.bufs.assign(bufs, bufs + n_bufs);
             e.launches.swap(fresh_launches);
             launches = &e.launches;
-            e.up_stream = use_copy_stream ? c->copy : stream;
+            e.up_stream = stream;
             e.stamp = ++c->clock;
             e.valid = true;
         } else {
@@ -904,27 +879,12 @@ extern "C" int ghn3_run(ghn3_ctx* c, const ghn3_op* ops, int n_ops, const ghn3_g
             c->launches[o.kind] += 1;
         }
     }
-    auto mark_done = [&]() -> int {                  // the slot's table may be overwritten once these kernels are done
-        if (used_slot >= 0) {
-            if (side_dirty || c->side_pending) {         // (side-stream kernels read the table too)
-                HIPCHK(hipEventRecord(c->ev_join, c->side));
-                HIPCHK(hipStreamWaitEvent(c->copy, c->ev_join, 0));
-            }
-            HIPCHK(hipEventRecord(c->ev_done[used_slot], main_stream));
-            c->done_used[used_slot] = true;
-        }
-        return GHN3_OK;
-    };
     if (detach && side_dirty) {                          // joined by the next run / ghn3_ctx_side_wait
         c->side_pending = true;
-        return mark_done();
+        return GHN3_OK;
     }
-    if (!touches_side) {                                 // (side state untouched, see above)
-        return mark_done();
-    }
-    int rc_join = join();
-    if (rc_join) return rc_join;
-    return mark_done();
+    if (!touches_side) return GHN3_OK;                   // (side state untouched, see above)
+    return join();
 }
 
 extern "C" int ghn3_ctx_cache_stats(ghn3_ctx* c, int64_t* hits, int64_t* misses) {

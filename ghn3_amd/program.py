@@ -65,12 +65,6 @@ class Program:
         # dependent chain of the program) carry GHN3_OPFLAG_SIDE and overlap with the chain on a second stream;
         # the temporaries they read are then per-layer buffers instead of reused ones.
         self.SIDE = L.OPFLAG_SIDE if side_stream else 0
-        # fuse_ln (off by default): the LayerNorms of the Graphormer layers run as row prologues of the GEMMs that
-        # consume them (forward: LN1 -> to_qkv, LN2 -> ff.net.0; backward: LN2' -> to_out dgrad, LN1' -> the next
-        # layer's ff.net.3 dgrad) instead of ~95 separate launches.  Measured a LOSS at ghn3xlm16: the prologue's
-        # registers (123 VGPRs against 52-60) halve the occupancy of the 1024-thread workgroups, a fused GEMM takes 34 us
-        # against 13 + 6 us for the separate kernels (11.2 -> 12.2 ms per step); kept for narrower models / as a record.
-        self.fuse_ln = os.environ.get('GHN3_FUSE_LN', '0') != '0'
         self.split_k2 = os.environ.get('GHN3_SPLIT_K2', '1') != '0'       # see split_small()
         self.split_k2_min = int(os.environ.get('GHN3_SPLIT_K2_MIN', '768'))  # (lowered by the CPU tests)
         # MFMA operand type of the decoder GEMMs (fc / W0 / W2, forward and backward): None = context default.
@@ -109,10 +103,6 @@ class Program:
         # partial planes -- and the LayerNorms as row prologues of the GEMMs that consume them: 5 dependent launches per
         # layer forward / backward instead of 7.  Needs a kernel for K = C, 3C and 4C (every released width).
         self.x3s = self.x3 and C in (64, 128, 256, 384) and os.environ.get('GHN3_X3S', '1') != '0'
-        # x3_exact_last: the LAST n Graphormer layers keep the exact-fp32 matrix instruction (experiment of round 5: does the
-        # ~1e-5 deviation of the node embeddings -- which flips knife-edge ReLU masks of the decoders -- come from the end of
-        # the chain?  It does not: docs/EXPERIMENTS.md)
-        self.x3_exact_last = int(os.environ.get('GHN3_X3_EXACT_LAST', '0')) if self.x3 else 0
         # x3f16 (round 5): the FORWARD linears of the staged kernels multiply F16 pieces (11 + 11 bits of mantissa, fp32-grade)
         # instead of bf16 pieces (8 + 8): same matrix instruction rate, the straight weight copies hold f16 pieces of
         # W * 2^6 (GHN3_CAST_SPLIT_F16) and alpha carries 2^-6.  Forward operands are O(1) (LayerNorm / attention / GELU
@@ -490,8 +480,7 @@ class Program:
         per 128-wide K chunk); two K halves as two problems of the same launch use twice the CUs.  The second half
         goes to a plane that the consuming LayerNorm kernel adds (and writes back), so no extra launch and a fixed
         summation order."""
-        return self.split_k2 and not self.fuse_ln and K >= self.split_k2_min and \
-            ((M + 31) // 32) * ((N + 31) // 32) <= 128
+        return self.split_k2 and K >= self.split_k2_min and ((M + 31) // 32) * ((N + 31) // 32) <= 128
 
     def gemm_k2(self, A, B, C, plane, M, N, K, lda, ldb, ldc, b_mode, **epilogue):
         """ROW-mode A.  Problem 1: columns [0, k0) with the epilogue -> C; problem 2: [k0, K) -> plane [M][N]."""
@@ -564,7 +553,6 @@ class Program:
 
     # cost of one k-tile step of a (64 mi) x 256 tile of the 8-phase kernel, mi = 3, 4, 5 (tools/gemm_lab.hip, relative)
     P8_COST = {3: 1.72, 4: 2.0, 5: 2.42}
-    FC_DGRAD_T = os.environ.get('GHN3_FC_DGRAD_T', '0') != '0'
     P8_MI = tuple(int(v) for v in os.environ.get('GHN3_P8_MI', '3,4,5').split(','))
 
     @classmethod
@@ -606,7 +594,6 @@ class Program:
     P8_COSTN = {2: 1.5, 4: 1.55, 6: 1.72, 7: 1.86, 8: 2.0, 9: 2.21, 10: 2.42}   # (2 / 4: bound by the W2 stream, not the matrix cores)
     P8_HEIGHTS = (2, 4, 6, 7, 8, 9, 10)                                    # row-tile heights / 32 the kernel has
     P8_BALANCED = os.environ.get('GHN3_P8_BALANCED', '1') != '0'            # forward: dense column ranges with equal tiles
-    P8_BALANCED_DGRAD = os.environ.get('GHN3_P8_BALANCED_DGRAD', '0') != '0'    # dgrad: equal tiles per K chunk
     P8_FINE = os.environ.get('GHN3_P8_FINE', '1') != '0'                   # row_tiles on 32-row positions, heights 192 .. 320
 
     @classmethod
@@ -684,16 +671,10 @@ class Program:
                 if not g.get('p8'):
                     continue
                 oc = (g['o'] + 7) // 8
-                if self.P8_BALANCED_DGRAD:                 # chunk 0: every row alive, equal tiles
-                    t_, n_ = self.balanced_tiles(g['rows'])
-                    tiles_ = [(self.P8_COSTN[n_], min(int(g['ext'][min(q * 32 * n_, g['rows'] - 1)]), oc * g['i_ld']))
-                              for q in range(t_) if q * 32 * n_ < g['rows']]
-                else:
-                    tiles_ = [(self.p8_cost(mi), min(int(ext), oc * g['i_ld'])) for (m0, mi, ext) in g['mtiles']]
-                for cost_, ext_ in tiles_:
-                    steps = ext_ / 64.0
+                for (m0, mi, ext) in g['mtiles']:
+                    steps = min(int(ext), oc * g['i_ld']) / 64.0
                     for f in sub:
-                        items += [cost_ * steps * f / sum(sub)] * nt
+                        items += [self.p8_cost(mi) * steps * f / sum(sub)] * nt
             items.sort(reverse=True)
             cu = [0.0] * n_cu
             for it in items:
@@ -877,14 +858,9 @@ class Program:
         w2h = 0
         w2hT = round_up(w2h + n_w2 * 8 * C + 128, 128)
         w0hT = round_up(w2hT + 8 * C * w2hT_ld + 128, 128)
-        # bf16 hi / lo copies of decoder.fc.0.weight, transposed per grid position ([position p][C][4C], k-contiguous), for the
-        # split-bf16 fc dgrad (see _cast_w2)
-        # (off by default since the weight gradient is issued behind the decoder backward: 6.97 ms per step either way, and
-        # the copies are 604 MB at ghn3xlm16; GHN3_FC_DGRAD_T=1 enables them)
-        S2 = int(max_shape[2]) * int(max_shape[3])
-        wfcT = round_up(w0hT + 4 * C * 8 * C + 128, 128)
-        pos = round_up(wfcT + (2 * S2 * C * 4 * C if Program.FC_DGRAD_T else 0) + 128, 128)
-        lay = dict(w2h=w2h, w2hT=w2hT, w2hT_ld=w2hT_ld, w0hT=w0hT, wfcT=wfcT, x3={})
+        # (two 128-element steps: an empty region between W0^T and the Graphormer copies keeps the offsets of existing layouts)
+        pos = round_up(round_up(w0hT + 4 * C * 8 * C + 128, 128) + 128, 128)
+        lay = dict(w2h=w2h, w2hT=w2hT, w2hT_ld=w2hT_ld, w0hT=w0hT, x3={})
         for l in range(layers):
             for name, r, c in Program.X3_WEIGHTS:
                 n = r * C * c * C
@@ -931,41 +907,23 @@ class Program:
                 self.cast16(self.pref('decoder.conv.0.weight'),
                             [dict(src_off=0, rows=8 * C, cols=4 * C, ld_src=4 * C, transposed=(self.w0hT, 8 * C, bct))],
                             flags=self.SIDE, dst_base=shadow)
-        if self.training and self.FC_DGRAD_T and (4 * C) % 64 == 0 and C % 4 == 0:
-            # decoder.fc.0.weight transposed per grid position, as bf16 hi / lo copies (GHN3_GEMM_X3 B operand):
-            # wfcT[p][n][ch] = Wfc[ch * 256 + p][n].  The fc dgrad reduces over ch; on the exact-fp32 small-problem kernel it
-            # was ~50 problems (one per used grid position) of a few dozen rows, 12 column tiles each walking K = 4C in
-            # latency-bound 128-wide chunks: 0.39 ms on the critical path (4 TFLOP/s).  Split-bf16 products against these
-            # copies run the same problems with the whole K slice in LDS.  Written on the side stream when the weights
-            # changed, used by the backward only.
-            S2 = self.S * self.S
-            self.wfcT = lay['wfcT']
-            self.wfcT_lo = S2 * C * 4 * C
-            items = [dict(src_off=p_ * C, rows=4 * C, cols=C, ld_src=S2 * C,
-                          transposed=(self.wfcT + p_ * C * 4 * C, 4 * C, L.CT_BF16), split=self.wfcT_lo) for p_ in range(S2)]
-            self.cast16(self.pref('decoder.fc.0.weight'), items, flags=self.SIDE, dst_base=shadow)
         if self.x3:
             # bf16 hi / lo copies of the Graphormer linears, straight (forward) and transposed (dgrad): ONE launch for all
             # layers (the source base of a cast op is one parameter; every weight is addressed from the first layer's first
             # one -- the flat parameter buffer is contiguous) -- on the main stream: layer 0 needs them at once.
             # (One launch per layer until round 4: 24 dependent launches of ~14 us each in front of every forward of a
-            # TRAINING step, where the weights change every step; GHN3_X3_CAST_PER_LAYER=1 restores that.)
-            per_layer = os.environ.get('GHN3_X3_CAST_PER_LAYER', '0') != '0'
+            # TRAINING step, where the weights change every step.)
             base0 = 'gnn.0.%s' % self.X3_WEIGHTS[0][0]
             items = []
             for l in range(self.Lyr):
-                base = 'gnn.%d.%s' % (l, self.X3_WEIGHTS[0][0]) if per_layer else base0
                 for name, r, c in self.X3_WEIGHTS:
                     e = lay['x3']['gnn.%d.%s' % (l, name)]
-                    it = dict(src_off=self.param_gap(base, 'gnn.%d.%s' % (l, name)), rows=e['rows'], cols=e['cols'],
+                    it = dict(src_off=self.param_gap(base0, 'gnn.%d.%s' % (l, name)), rows=e['rows'], cols=e['cols'],
                               ld_src=e['cols'], straight=(e['hi'], e['cols'], L.CT_BF16), split=e['lo'], frag=self.x3s,
                               f16s=self.x3f16)
                     if self.training:
                         it['transposed'] = (e['hiT'], e['rows'], L.CT_BF16)
                     items.append(it)
-                if per_layer:
-                    self.cast16(self.pref(base), items, dst_base=shadow)
-                    items = []
             if items:
                 self.cast16(self.pref(base0), items, dst_base=shadow)
 
@@ -997,26 +955,18 @@ class Program:
         The kernel is bound by what one CU can pull through L2 -> LDS (~17 B/clk): the bytes per workgroup are
         4 K_slice (BM + BN), so narrow outputs (N <= 512: to_out, ff.net.3, the dgrads of to_qkv / ff.net.0) take 32 x 32
         tiles and -- where the consumer is a LayerNorm op that can sum partial planes -- K slices of 192 (then 128, 64)
-        run by different workgroup sets; wide outputs (to_qkv, ff.net.0, ff.net.3 dgrad) took 32 x 64 tiles over the whole
-        K = C until round 2 (see below).  Measured at ghn3xlm16 (tools/diag/x3_bench.py, us per dependent launch, exact-fp32 kernel in brackets):
+        run by different workgroup sets; wide outputs (to_qkv, ff.net.0, ff.net.3 dgrad) walk K in slices of 192 (see below).
+        Measured at ghn3xlm16 (tools/diag/x3_bench.py, us per dependent launch, exact-fp32 kernel in brackets):
         to_qkv 6.4 (9.9), to_out 4.4 (6.5), ff.net.0 6.4 (10.3), ff.net.3 7.3 (10.0 with its two K halves)."""
         nk = K // 64
         whole = max(d for d in (6, 4, 3, 2, 1) if nk % d == 0)         # k-tiles per slice without a split
-        plan = os.environ.get('GHN3_X3_PLAN', 'A')
         if N > 512:
             # 32 x 32 tiles walking K in slices of 192: 49 KB of LDS per workgroup, so that several of the 288-384 workgroups
             # share a CU -- a workgroup's fetch rate is ~5 B/clk per WAVE (20 B/clk for a lone 4-wave workgroup with its
-            # 147 KB at 32 x 64 / whole K; tools/fetch_rate_probe.hip).  Step 8.35 -> 8.20 ms; GHN3_X3_PLAN=W: the former plan
-            if plan != 'W' and K % 192 == 0:
+            # 147 KB at 32 x 64 / whole K, the plan until round 2; tools/fetch_rate_probe.hip).  Step 8.35 -> 8.20 ms.
+            if K % 192 == 0:
                 return 42, 1, 192
             return 40, 1, 64 * whole
-        if plan == 'B':                                                  # 32 x 64 tiles, slices of up to 384: few planes
-            return 40, (nk // whole if may_split else 1), 64 * whole
-        if plan == 'C':                                                  # 64 x 64 tiles, slices of 192 / 128
-            for d in (3, 2, 4, 1):
-                if nk % d == 0 and (nk // d <= 8 and may_split or nk == d):
-                    return 41, nk // d, 64 * d
-            return 40, (nk // whole if may_split else 1), 64 * whole
         if not may_split:
             return 42, 1, 64 * whole
         for d in (3, 2, 4, 6, 1):
@@ -1120,8 +1070,7 @@ class Program:
             z = self.wsf('z' + sfx, rows * 4 * C)
             f = self.wsf('f' + sfx, rows * 4 * C)
             x_out = self.wsf('x%d' % (l + 1), rows * C)
-            x3_here = l < self.Lyr - self.x3_exact_last
-            if self.x3s and x3_here:
+            if self.x3s:
                 # staged split-bf16 linears: LayerNorm 1 / 2 are row prologues of to_qkv / ff.net.0 (their by-products --
                 # normalised rows, mean, rstd -- are written by the column-tile-0 workgroups when the backward needs them),
                 # the narrow linears split K inside the workgroup: five dependent launches per layer
@@ -1140,7 +1089,7 @@ class Program:
                                 bias=self.pref(pre + 'ff.net.3.bias'), residual=xmid)
                 x_in = x_out
                 continue
-            if self.x3 and x3_here:
+            if self.x3:
                 # split-bf16 linears (GHN3_GEMM_X3); K splits of the linear-epilogue GEMMs go to partial planes that the
                 # next LayerNorm op sums (and writes back) -- x_plane: (number of planes, ref) of the previous ff.net.3
                 self.op(L.OP_LAYERNORM_FWD, refs=(h1, x_in, self.pref(pre + 'ln1.weight'), self.pref(pre + 'ln1.bias'),
@@ -1163,31 +1112,20 @@ class Program:
                 x_plane = (np_, pl) if np_ else None
                 x_in = x_out
                 continue
-            if self.fuse_ln:
-                p0 = self.gemm(x_in, self.pref(pre + 'attn.to_qkv.weight'), qkv, rows, 3 * C, C, C, C, 3 * C,
-                               ln=(1, [self.pref(pre + 'ln1.weight'), self.pref(pre + 'ln1.bias'),
-                                       m1 if train else None, r1 if train else None, h1 if train else None], 1e-5))
-            else:
-                self.op(L.OP_LAYERNORM_FWD, refs=(h1, x_in, self.pref(pre + 'ln1.weight'), self.pref(pre + 'ln1.bias'),
-                                                  m1, r1, x_plane or self.NONE), ints=(rows, C), floats=(1e-5,))
-                x_plane = None
-                p0 = self.gemm(h1, self.pref(pre + 'attn.to_qkv.weight'), qkv, rows, 3 * C, C, C, C, 3 * C)
+            self.op(L.OP_LAYERNORM_FWD, refs=(h1, x_in, self.pref(pre + 'ln1.weight'), self.pref(pre + 'ln1.bias'),
+                                              m1, r1, x_plane or self.NONE), ints=(rows, C), floats=(1e-5,))
+            x_plane = None
+            p0 = self.gemm(h1, self.pref(pre + 'attn.to_qkv.weight'), qkv, rows, 3 * C, C, C, C, 3 * C)
             self.gemm_op(p0)
             self.op(L.OP_ATTN_FWD, refs=(o, qkv, bias, Pm if Pm is not None else self.NONE, r_nn),
                     ints=(B, N, C, H))
             p0 = self.gemm(o, self.pref(pre + 'attn.to_out.0.weight'), xmid, rows, C, C, C, C, C,
                            bias=self.pref(pre + 'attn.to_out.0.bias'), residual=x_in)
             self.gemm_op(p0)
-            if self.fuse_ln:
-                p0 = self.gemm(xmid, self.pref(pre + 'ff.net.0.weight'), f, rows, 4 * C, C, C, C, 4 * C,
-                               bias=self.pref(pre + 'ff.net.0.bias'), act=L.ACT_GELU, aux_out=z if train else None,
-                               ln=(1, [self.pref(pre + 'ln2.weight'), self.pref(pre + 'ln2.bias'),
-                                       m2 if train else None, r2 if train else None, h2 if train else None], 1e-5))
-            else:
-                self.op(L.OP_LAYERNORM_FWD, refs=(h2, xmid, self.pref(pre + 'ln2.weight'), self.pref(pre + 'ln2.bias'),
-                                                  m2, r2), ints=(rows, C), floats=(1e-5,))
-                p0 = self.gemm(h2, self.pref(pre + 'ff.net.0.weight'), f, rows, 4 * C, C, C, C, 4 * C,
-                               bias=self.pref(pre + 'ff.net.0.bias'), act=L.ACT_GELU, aux_out=z if train else None)
+            self.op(L.OP_LAYERNORM_FWD, refs=(h2, xmid, self.pref(pre + 'ln2.weight'), self.pref(pre + 'ln2.bias'),
+                                              m2, r2), ints=(rows, C), floats=(1e-5,))
+            p0 = self.gemm(h2, self.pref(pre + 'ff.net.0.weight'), f, rows, 4 * C, C, C, C, 4 * C,
+                           bias=self.pref(pre + 'ff.net.0.bias'), act=L.ACT_GELU, aux_out=z if train else None)
             self.gemm_op(p0)
             if self.split_small(rows, C, 4 * C) and (self.layernorm or l + 1 < self.Lyr) and not self.x3:
                 # x_out = xmid + f W3^T + b3 in two K halves; the next LayerNorm adds the second one
@@ -1225,7 +1163,7 @@ class Program:
         W0, b0 = 'decoder.conv.0.weight', 'decoder.conv.0.bias'
         W2, b2 = 'decoder.conv.2.weight', 'decoder.conv.2.bias'
         Wc, bc = 'decoder.class_layer_predictor.1.weight', 'decoder.class_layer_predictor.1.bias'
-        def decoder_1d(side):
+        def decoder_1d():
             # 1-D decoder (nn.py:286-295)
             if self.n1 <= 0:
                 return
@@ -1240,7 +1178,7 @@ class Program:
             w1d = self.wsf('w1d', self.n1 * 2 * mc)
             p0 = self.gemm(xe, self.pref(W1), h1d, self.n1, 2 * C, C, C, C, 2 * C, bias=self.pref(b1),
                            act=L.ACT_RELU, a_gather=r_src1)
-            self.gemm_op(p0, side=side)
+            self.gemm_op(p0)
             p0 = len(self._probs)
             if self.n1_plain:
                 self.gemm(h1d, self.pref(W2d), w1d, self.n1_plain, 2 * mc, 2 * C, 2 * C, 2 * C, 2 * mc,
@@ -1249,25 +1187,20 @@ class Program:
                 self.gemm(self.wref('h1d', self.n1_plain * 2 * C), self.pref(W2d),
                           self.wref('w1d', self.n1_plain * 2 * mc), self.n1_clsb, 2 * mc, 2 * C, 2 * C, 2 * C, 2 * mc,
                           bias=self.pref(b2d), act=L.ACT_RELU)
-            self.gemm_op(p0, side=side)
+            self.gemm_op(p0)
             if self.n1_clsb:
                 cbout = self.wsf('cbout', self.n1_clsb * ldK)
                 p0 = self.gemm(self.wref('w1d', self.n1_plain * 2 * mc + mc), self.pref(Wb), cbout, self.n1_clsb, K,
                                mc, 2 * mc, mc, ldK, bias=self.pref(bb))
-                self.gemm_op(p0, side=side)
+                self.gemm_op(p0)
 
-        # The 1-D decoder (bn / bias / norm nodes) depends on the node embeddings only: with two streams it runs on the side
-        # stream beside the W2 GEMMs instead of behind them (~35 us of small launches off the forward chain)
-        # (measured: in a forward-only run the cross-stream hand-off costs 0.13 ms -- more than the 35 us it hides -- so the
-        # forward keeps the 1-D decoder on the chain unless GHN3_EARLY_1D_FWD=1; the backward, whose side stream is busy
-        # anyway, moves it: see _build_backward)
-        early_1d = bool(self.SIDE) and M > 0 and os.environ.get('GHN3_EARLY_1D_FWD', '0') == '1'
+        # The 1-D decoder (bn / bias / norm nodes) depends on the node embeddings only, but the forward keeps it on the chain,
+        # behind the W2 GEMMs: on the side stream the cross-stream hand-off costs 0.13 ms, more than the ~35 us of small
+        # launches it hides.  The backward, whose side stream is busy anyway, moves it: see _build_backward.
         if self.SIDE:
             # An overlapped optimizer step (FusedAdamW.step(overlap=True)) may still be updating the decoder parameters on
             # the side stream: the Graphormer above needed none of them, everything below does (no-op when nothing is pending)
             self.op(L.OP_JOIN)
-        if early_1d:
-            decoder_1d(True)
         if M > 0:
             t = self.wsf('t', M * 4 * C)
             u = self.wsf('u', M * 8 * C)
@@ -1387,10 +1320,7 @@ class Program:
                                   a_mode=L.MODE_COL, bias=self.pref(bc))
                         off += g['i_ld'] * ldK
                 self.gemm_op(p0)
-        if not early_1d:
-            decoder_1d(False)
-        elif self.n1 > 0:
-            self.op(L.OP_JOIN)                          # the side-stream 1-D decoder is complete before the tile kernels read it
+        decoder_1d()
         self._build_tile_descriptors()
 
     @staticmethod
@@ -2112,15 +2042,8 @@ class Program:
                     # the last: the boundaries equalise the WORK (row tiles alive at o' x their cost) instead of the length.
                     if g['p8'] and g['nc'] == 8 and os.environ.get('GHN3_DGRAD_EQ', '1') != '0':
                         dens = np.zeros(g['o'])
-                        if self.P8_BALANCED_DGRAD:              # work alive at o': its equal tiles
-                            lo_ = 0
-                            for hi_ in sorted({sb['o'] for sb in g['subs']}):
-                                t_, n_ = self.balanced_tiles(self.alive_rows(g, lo_))
-                                dens[lo_:hi_] = t_ * self.P8_COSTN[n_]
-                                lo_ = hi_
-                        else:
-                            for (m0_, mi_, ext_) in g['mtiles']:
-                                dens[:min(g['o'], int(ext_) // g['i_ld'])] += self.p8_cost(mi_)
+                        for (m0_, mi_, ext_) in g['mtiles']:
+                            dens[:min(g['o'], int(ext_) // g['i_ld'])] += self.p8_cost(mi_)
                         cw = np.concatenate([[0.0], np.cumsum(dens)])
                         bounds = [0]
                         for j in range(1, g['nc']):
@@ -2148,13 +2071,7 @@ class Program:
                         if g['ragged'] or kc < g['cols']:
                             lim = self.idx(np.clip(g['lim128'] - k0, 0, kc).astype(np.int32))
                         mt = None
-                        if g['p8'] and self.P8_BALANCED_DGRAD:
-                            # equal tiles over the rows alive at the chunk's first W2 row (a prefix); rows dead in this chunk
-                            # write the zeros of their plane rows (K = 0)
-                            alive = self.alive_rows(g, min(o0, g['o'])) if kc > 0 else 0
-                            mt = self.range_tiles(alive, g['rows'], lambda r_: g['ext'][r_], k0, kc)
-                            mt = (self.idx(mt), len(mt))
-                        elif g['p8']:
+                        if g['p8']:
                             mt = g['mtiles'].copy()
                             mt[:, 2] = np.clip(mt[:, 2] - k0, 0, kc)
                             mt = (self.idx(mt), len(mt))
@@ -2350,15 +2267,9 @@ class Program:
             # D1 backward (per used position)
             p0 = len(self._probs)
             for (p, cnt, r_rows, r_src) in self.d1:
-                if hasattr(self, 'wfcT'):             # split-bf16 products against the transposed copies (see _cast_w2)
-                    b_hi = self.wfcT + p * C * 4 * C
-                    self.gemm(d_t, self.sref(b_hi), d_rows, cnt, C, 4 * C, 4 * C, 4 * C, C, a_gather=r_rows,
-                              c_gather=r_rows, x3=(self.sref(b_hi + self.wfcT_lo), 384 if (4 * C) % 384 == 0 else 64))
-                    continue
                 self.gemm(d_t, self.pref(Wfc, p * C), d_rows, cnt, C, 4 * C, 4 * C, S2 * C, C, a_mode=L.MODE_ROW,
                           b_mode=L.MODE_COL, a_gather=r_rows, c_gather=r_rows)
-            self.gemm_op(p0, tag=self.TAG_D1_BWD, ctype=self.d1_bwd_ctype,
-                         tile=42 if hasattr(self, 'wfcT') else int(os.environ.get('GHN3_D1_DGRAD_TILE', '0')))
+            self.gemm_op(p0, tag=self.TAG_D1_BWD, ctype=self.d1_bwd_ctype, tile=int(os.environ.get('GHN3_D1_DGRAD_TILE', '0')))
             p0 = len(self._probs)
             for (p, cnt, r_rows, r_src) in self.d1:
                 self.gemm(d_t, xe, self.gref(Wfc, p * C), 4 * C, C, cnt, 4 * C, C, S2 * C, a_mode=L.MODE_COL,
@@ -2401,7 +2312,7 @@ class Program:
             g_cur = d_xe
         # ---- Graphormer layers, reversed ----------------------------------------------------------------
         bias = self.wref('bias')
-        pending_ln1 = None                  # (dy buffer, prologue refs) of the LayerNorm backward fused into the next GEMM
+        pending_ln1 = None                  # staged route: (dy buffer, prologue refs) of the LayerNorm backward fused into the next GEMM
         # Side-stream ops of `side_group` consecutive layers are issued together: every main -> side hand-off is an event
         # record that stalls the main chain for 6-12 us, and the temporaries the side ops read are per layer anyway.
         side_group = max(1, int(os.environ.get('GHN3_SIDE_GROUP', '4'))) if self.SIDE else 1
@@ -2430,8 +2341,7 @@ class Program:
             g_mid = self.wsf('gmid' + lsfx, rows * C)
             g_out = self.wsf(('gout' + sfx) if self.SIDE else 'gout%d' % (l & 1), rows * C)
             dqkv = self.wsf('dqkv' + lsfx, rows * 3 * C)
-            x3_here = l < self.Lyr - self.x3_exact_last
-            if self.x3s and x3_here:
+            if self.x3s:
                 # staged split-bf16 dgrads against the transposed (fragment-major) weight copies.  The two LayerNorm
                 # backward passes are row prologues: LN2' (+ the residual gradient g_cur) of the to_out dgrad, which writes
                 # g_mid; LN1' (+ g_mid) of the ff.net.3 dgrad of the layer BELOW, which writes g_out = that layer's g_cur.
@@ -2450,7 +2360,7 @@ class Program:
                 else:
                     self.op(L.OP_LAYERNORM_BWD, refs=(g_out, dhB, x_in, self.pref(pre + 'ln1.weight'), m1, r1, g_mid,
                                                       self.NONE), ints=(rows, C))
-            elif self.x3 and x3_here:
+            elif self.x3:
                 # split-bf16 dgrads against the transposed weight copies; K splits -> planes summed by the LayerNorm
                 # backward ops (which write the sums back for the LayerNorm parameter gradients on the side stream)
                 self.x3_linear(g_cur, W3, True, dz, rows, 4 * C, C, C, 4 * C, dact=L.DACT_GELU, aux_in=z)
@@ -2464,12 +2374,9 @@ class Program:
                 self.op(L.OP_LAYERNORM_BWD, refs=(g_out, dhB, x_in, self.pref(pre + 'ln1.weight'), m1, r1, g_mid,
                                                   pl if np_ else self.NONE), ints=(rows, C, np_, rows * C))
             else:
-                # FFN second linear: x_out = xmid + f W3^T + b3.  With fuse_ln the upstream gradient g_cur of every layer
-                # but the last is LN1'(dhB) + g_mid of the layer above, produced by this GEMM's row prologue.
-                p0 = self.gemm(g_cur if pending_ln1 is None else pending_ln1[0], self.pref(W3), dz, rows, 4 * C, C, C,
-                               4 * C, 4 * C, a_mode=L.MODE_ROW, b_mode=L.MODE_COL, dact=L.DACT_GELU, aux_in=z,
-                               ln=None if pending_ln1 is None else (2, pending_ln1[1], 0.0))
-                pending_ln1 = None
+                # FFN second linear: x_out = xmid + f W3^T + b3
+                p0 = self.gemm(g_cur, self.pref(W3), dz, rows, 4 * C, C, C, 4 * C, 4 * C, a_mode=L.MODE_ROW, b_mode=L.MODE_COL,
+                               dact=L.DACT_GELU, aux_in=z)
                 self.gemm_op(p0)
                 # FFN first linear
                 dhA_p = None
@@ -2481,16 +2388,10 @@ class Program:
                                    b_mode=L.MODE_COL)
                 self.gemm_op(p0)
                 # LN2 (+ residual branch gradient g_cur)
-                if self.fuse_ln:
-                    # attention output projection: xmid = x_in + o Wo^T + bo; its A operand g_mid = LN2'(dhA) + g_cur is
-                    # computed (and written for the wgrad / the residual path) by the GEMM's row prologue
-                    p0 = self.gemm(dhA, self.pref(Wo), do, rows, C, C, C, C, C, a_mode=L.MODE_ROW, b_mode=L.MODE_COL,
-                                   ln=(2, [self.pref(pre + 'ln2.weight'), xmid, m2, r2, g_cur, g_mid], 0.0))
-                else:
-                    self.op(L.OP_LAYERNORM_BWD, refs=(g_mid, dhA, xmid, self.pref(pre + 'ln2.weight'), m2, r2, g_cur,
-                                                      dhA_p or self.NONE), ints=(rows, C))
-                    # attention output projection: xmid = x_in + o Wo^T + bo
-                    p0 = self.gemm(g_mid, self.pref(Wo), do, rows, C, C, C, C, C, a_mode=L.MODE_ROW, b_mode=L.MODE_COL)
+                self.op(L.OP_LAYERNORM_BWD, refs=(g_mid, dhA, xmid, self.pref(pre + 'ln2.weight'), m2, r2, g_cur,
+                                                  dhA_p or self.NONE), ints=(rows, C))
+                # attention output projection: xmid = x_in + o Wo^T + bo
+                p0 = self.gemm(g_mid, self.pref(Wo), do, rows, C, C, C, C, C, a_mode=L.MODE_ROW, b_mode=L.MODE_COL)
                 self.gemm_op(p0)
                 self.op(L.OP_ATTN_BWD, refs=(dqkv, do, qkv, Pm, o, hist_amax if l == 0 else self.NONE, dBias, r_nn), ints=(B, N, C, H))
                 dhB_p = None
@@ -2501,11 +2402,8 @@ class Program:
                     p0 = self.gemm(dqkv, self.pref(Wq), dhB, rows, C, 3 * C, 3 * C, C, C, a_mode=L.MODE_ROW,
                                    b_mode=L.MODE_COL)
                 self.gemm_op(p0)
-                if self.fuse_ln and l > 0:
-                    pending_ln1 = (dhB, [self.pref(pre + 'ln1.weight'), x_in, m1, r1, g_mid, g_out])
-                else:
-                    self.op(L.OP_LAYERNORM_BWD, refs=(g_out, dhB, x_in, self.pref(pre + 'ln1.weight'), m1, r1, g_mid,
-                                                      dhB_p or self.NONE), ints=(rows, C))
+                self.op(L.OP_LAYERNORM_BWD, refs=(g_out, dhB, x_in, self.pref(pre + 'ln1.weight'), m1, r1, g_mid,
+                                                  dhB_p or self.NONE), ints=(rows, C))
             # Side-stream work of the layer: four weight gradients (+ fused bias gradients) and the two LayerNorm parameter
             # gradients.  Round 4 (`defer`, side stream only): ALL layers' weight gradients are ONE grouped launch and all
             # LayerNorm parameter gradients ONE batched launch behind the chain -- the 24 x 3 small side launches beside the
@@ -2519,14 +2417,12 @@ class Program:
             if not defer:
                 main_ops, self._ops = self._ops, []
                 self._layer_side_ops([layer_side[-1]], rows)
-                if os.environ.get('GHN3_SKIP_LAYER_SIDE', '0') != '0':   # (timing experiment: wrong gradients)
-                    self._ops = []
                 side_pending, self._ops = side_pending + self._ops, main_ops
                 if (self.Lyr - l) % side_group == 0 or l == 0:
                     self._ops.extend(side_pending)
                     side_pending = []
             g_cur = g_out                   # d x_l
-        if defer and os.environ.get('GHN3_SKIP_LAYER_SIDE', '0') == '0' and side_done < len(layer_side):
+        if defer and side_done < len(layer_side):
             self._layer_side_ops(layer_side[side_done:], rows)
         # ---- node embeddings (side stream: beside the edge-bias backward below, which does not depend on it) --------
         self.op(L.OP_EMBED_BWD,
