@@ -57,6 +57,8 @@ def main():
     ap.add_argument('--workers', type=int, default=8)
     ap.add_argument('--max-nodes', type=int, default=400)
     ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--bn-free-prob', type=float, default=0.0,
+                    help='share of the architecture stream drawn without norm layers (norm=None); 0: the default stream')
     ap.add_argument('--save', default=None)
     ap.add_argument('--native', action='store_true',
                     help='run the target networks on ATen native convolution / batch-norm kernels instead of MIOpen')
@@ -88,7 +90,7 @@ def main():
 
     world = ddp.world_size if ddp.ddp else 1
     per_rank = args.meta_batch_size // world
-    kw = dict(large_images=args.imagenet, seed=args.seed, max_nodes=args.max_nodes)
+    kw = dict(large_images=args.imagenet, seed=args.seed, max_nodes=args.max_nodes, bn_free_prob=args.bn_free_prob)
     total = args.steps * args.epochs
 
     trainer = Trainer(ghn, opt='adamw', opt_args={'lr': args.lr, 'weight_decay': args.wd}, scheduler='cosine',

@@ -27,6 +27,10 @@
 // Limits (checked by the host): C_in, C_out multiples of 4 and <= 512, ks <= 7 (odd or even), N H W C < 2^31.
 // w_dw == nullptr (ks = 1): the same family as ReLU -> 1x1 convolution (stride) -> BatchNorm = `ReLUConvBN` with a 1x1 kernel,
 // the preprocessing layer of every cell and the `conv_1x1` op (ops.py:180-198): the depthwise stage degenerates to the ReLU.
+// Without a norm layer (ghn3_dwpw_plain_fwd / _bwd: the blocks of a network built with norm = None, ops.py:91-96, whose norm slots
+// are Identity layers): the same kernels with NORM = false.  The forward is dwpw_fwd alone -- its accumulators are the output, no
+// z, no statistics --; in the backward dz IS dout, so dwpw_bwd_data and pw_wgrad load it plainly and bn_bwd_partial is not run:
+// one launch forward, six backward, nothing of activation size kept between them but x.
 
 #include <algorithm>
 #include "tnet_common.h"
@@ -147,10 +151,36 @@ __device__ __forceinline__ void dz8(const float* __restrict__ dout, const float*
     }
 }
 
+// 8 consecutive channels c .. c + 7 of row p of dz [P][C]; zeros for p >= P and for channels at or beyond C
+__device__ __forceinline__ void dz_in8(const float* __restrict__ dz, int C, int p, int P, int c, float (&out)[8]) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) out[e] = 0.f;
+    if (p >= P) return;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int cc = c + 4 * h;
+        if (cc >= C) break;
+        const f32x4 g = *reinterpret_cast<const f32x4*>(dz + (int64_t)p * C + cc);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) out[4 * h + e] = g[e];
+    }
+}
+
+// The operand rows of the backward products: NORM = true forms dz from (dout, z, statistics); NORM = false -- the family
+// without a norm layer -- has dz = dout, a plain load (z, stats, gamma, s12 are not touched).
+template <bool NORM>
+__device__ __forceinline__ void dz_operand8(const float* __restrict__ dout, const float* __restrict__ z, const float* __restrict__ stats,
+                                            const float* __restrict__ gamma, const float* __restrict__ s12, int C, int p, int P, int c,
+                                            float (&out)[8]) {
+    if constexpr (NORM) dz8(dout, z, stats, gamma, s12, C, p, P, c, out);
+    else dz_in8(dout, C, p, P, c, out);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
-// forward: z = pw(dw(relu(x))), per-tile channel statistics
+// forward: z = pw(dw(relu(x))), per-tile channel statistics.  NORM = false: z is the op's output and the kernel ends with its
+// store (no statistics, `part` not touched, no `red` section in LDS).
 // ---------------------------------------------------------------------------------------------------------------------
-template <int NT>
+template <int NT, bool NORM = true>
 __global__ __launch_bounds__(256) void tnet_dwpw_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w_dw,
                                                             const float* __restrict__ w_pw, float* __restrict__ z,
                                                             float* __restrict__ part, const Desc d, const int P) {
@@ -160,7 +190,7 @@ __global__ __launch_bounds__(256) void tnet_dwpw_fwd_kernel(const float* __restr
     float* wt = reinterpret_cast<float*>(smem + 3 * TP * 4);                   // [MAXT][KC]
     unsigned short* As = reinterpret_cast<unsigned short*>(smem + 3 * TP * 4 + MAXT * KC * 4);      // [S][TP][LDK]
     unsigned short* Bs = As + S * TP * LDK;                                                          // [S][16 NT][LDK]
-    float* red = reinterpret_cast<float*>(Bs + S * 16 * NT * LDK);             // [5][16 NT]
+    [[maybe_unused]] float* red = reinterpret_cast<float*>(Bs + S * 16 * NT * LDK);   // [5][16 NT] (NORM only)
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r16 = lane & 15, kc = lane >> 4;
     const int tile = blockIdx.x, p0 = tile * TP, taps = d.ks * d.ks;
     if (tid < TP) {
@@ -209,34 +239,36 @@ __global__ __launch_bounds__(256) void tnet_dwpw_fwd_kernel(const float* __restr
     // ---- epilogue: z, then per-tile (mean, M2) of every channel
     const int prow = p0 + 16 * w + r16;
     const bool valid = prow < P;
-    const int cnt = min(TP, P - p0);
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
         const int col = 16 * j + 4 * kc;
         if (valid && col < d.C_out) *reinterpret_cast<f32x4*>(z + (int64_t)prow * d.C_out + col) = acc[j];
     }
-    auto tile_sum = [&](bool centred) {
-        __syncthreads();
+    if constexpr (NORM) {
+        const int cnt = min(TP, P - p0);
+        auto tile_sum = [&](bool centred) {
+            __syncthreads();
 #pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            const int col = 16 * j + 4 * kc;
+            for (int j = 0; j < NT; ++j) {
+                const int col = 16 * j + 4 * kc;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float v = 0.f;
-                if (valid) { v = acc[j][e]; if (centred) { v -= red[4 * 16 * NT + col + e]; v *= v; } }
-                v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64); v += __shfl_xor(v, 8, 64);
-                if (r16 == 0) red[w * 16 * NT + col + e] = v;
+                for (int e = 0; e < 4; ++e) {
+                    float v = 0.f;
+                    if (valid) { v = acc[j][e]; if (centred) { v -= red[4 * 16 * NT + col + e]; v *= v; } }
+                    v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64); v += __shfl_xor(v, 8, 64);
+                    if (r16 == 0) red[w * 16 * NT + col + e] = v;
+                }
             }
+            __syncthreads();
+        };
+        tile_sum(false);
+        for (int c = tid; c < 16 * NT; c += 256)
+            red[4 * 16 * NT + c] = (red[c] + red[16 * NT + c] + red[2 * 16 * NT + c] + red[3 * 16 * NT + c]) / (float)cnt;
+        tile_sum(true);
+        for (int c = tid; c < d.C_out; c += 256) {
+            part[((int64_t)tile * 2) * d.C_out + c] = red[4 * 16 * NT + c];
+            part[((int64_t)tile * 2 + 1) * d.C_out + c] = red[c] + red[16 * NT + c] + red[2 * 16 * NT + c] + red[3 * 16 * NT + c];
         }
-        __syncthreads();
-    };
-    tile_sum(false);
-    for (int c = tid; c < 16 * NT; c += 256)
-        red[4 * 16 * NT + c] = (red[c] + red[16 * NT + c] + red[2 * 16 * NT + c] + red[3 * 16 * NT + c]) / (float)cnt;
-    tile_sum(true);
-    for (int c = tid; c < d.C_out; c += 256) {
-        part[((int64_t)tile * 2) * d.C_out + c] = red[4 * 16 * NT + c];
-        part[((int64_t)tile * 2 + 1) * d.C_out + c] = red[c] + red[16 * NT + c] + red[2 * 16 * NT + c] + red[3 * 16 * NT + c];
     }
 }
 
@@ -347,8 +379,8 @@ __global__ __launch_bounds__(256) void tnet_reduce_rows_kernel(const float* __re
     }
 }
 
-// dy [P][C_in] = dz [P][C_out] W_pw [C_out][C_in]; dz formed on the fly
-template <int NT>
+// dy [P][C_in] = dz [P][C_out] W_pw [C_out][C_in]; dz formed on the fly (NORM = false: dz = dout)
+template <int NT, bool NORM = true>
 __global__ __launch_bounds__(256) void tnet_dwpw_bwd_data_kernel(const float* __restrict__ dout, const float* __restrict__ z,
                                                                  const float* __restrict__ stats, const float* __restrict__ gamma,
                                                                  const float* __restrict__ s12, const float* __restrict__ w_pw,
@@ -367,7 +399,7 @@ __global__ __launch_bounds__(256) void tnet_dwpw_bwd_data_kernel(const float* __
         {   // A[i][k] = dz[p0 + i][c0 + k]
             const int i = tid >> 2, cc = (tid & 3) * 8;
             float v[8];
-            dz8(dout, z, stats, gamma, s12, d.C_out, p0 + i, P, c0 + cc, v);
+            dz_operand8<NORM>(dout, z, stats, gamma, s12, d.C_out, p0 + i, P, c0 + cc, v);
 #pragma unroll
             for (int e = 0; e < 8; ++e) splitS<S>(v[e], As, i * LDK + cc + e, TP * LDK);
         }
@@ -402,6 +434,7 @@ __global__ __launch_bounds__(256) void tnet_dwpw_bwd_data_kernel(const float* __
 }
 
 // part[chunk][co][ci] = sum over the chunk's pixels of dz[p][co] y[p][ci]; workgroup = (chunk, 64 co, 64 ci)
+template <bool NORM = true>
 __global__ __launch_bounds__(256) void tnet_pw_wgrad_kernel(const float* __restrict__ dout, const float* __restrict__ z,
                                                             const float* __restrict__ stats, const float* __restrict__ gamma,
                                                             const float* __restrict__ s12, const float* __restrict__ x,
@@ -425,7 +458,7 @@ __global__ __launch_bounds__(256) void tnet_pw_wgrad_kernel(const float* __restr
         const int k = tid >> 3, m8 = (tid & 7) * 8, p = pk + k;
         {   // A[m = co][k = pixel]
             float v[8];
-            dz8(dout, z, stats, gamma, s12, d.C_out, p < pb ? p : P, P, co0 + m8, v);
+            dz_operand8<NORM>(dout, z, stats, gamma, s12, d.C_out, p < pb ? p : P, P, co0 + m8, v);
 #pragma unroll
             for (int e = 0; e < 8; ++e) splitS<S>(v[e], As, (m8 + e) * LDK + k, 64 * LDK);
         }
@@ -588,21 +621,6 @@ __device__ __forceinline__ void conv_in8(const float* __restrict__ x, const CDes
     }
 }
 
-// 8 consecutive channels c .. c + 7 of row p of dz [P][C]; zeros for p >= P and for channels at or beyond C
-__device__ __forceinline__ void dz_in8(const float* __restrict__ dz, int C, int p, int P, int c, float (&out)[8]) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) out[e] = 0.f;
-    if (p >= P) return;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int cc = c + 4 * h;
-        if (cc >= C) break;
-        const f32x4 g = *reinterpret_cast<const f32x4*>(dz + (int64_t)p * C + cc);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) out[4 * h + e] = g[e];
-    }
-}
-
 // part[chunk][t][co][ci] = sum over the chunk's output pixels of dz[p][co] act(x[tap t of p][ci]); workgroup = (chunk, 64 co, (t, 64 ci))
 __global__ __launch_bounds__(256) void tnet_conv_wgrad_kernel(const float* __restrict__ dz, const float* __restrict__ x,
                                                               float* __restrict__ part, const CDesc d, const int P, const int chunk_px) {
@@ -695,7 +713,7 @@ __global__ __launch_bounds__(256) void tnet_conv_wgrad_kernel(const float* __res
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
 inline int nt_of(int C) { return C <= 64 ? 4 : C <= 128 ? 8 : C <= 256 ? 16 : 32; }
-inline size_t fwd_lds(int NT) { const int S = terms_of(NT); return 3 * TP * 4 + MAXT * KC * 4 + S * TP * LDK * 2 + S * 16 * NT * LDK * 2 + 5 * 16 * NT * 4; }
+inline size_t fwd_lds(int NT, bool norm = true) { const int S = terms_of(NT); return 3 * TP * 4 + MAXT * KC * 4 + S * TP * LDK * 2 + S * 16 * NT * LDK * 2 + (norm ? 5 * 16 * NT * 4 : 0); }
 inline size_t bwd_lds(int NT) { const int S = terms_of(NT); return S * TP * LDK * 2 + S * 16 * NT * LDK * 2; }
 
 struct Plan { int P, n_tiles, pw_chunks, pw_chunk_px, dw_chunks, dw_chunk_px; };
@@ -734,6 +752,53 @@ int check_desc(const ghn3_dwpw_desc* g, Desc& d) {
         (int64_t)d.N * d.Ho * d.Wo * std::max(d.C_in, d.C_out) >= ((int64_t)1 << 31)) {
         ghn3_set_error("dwpw: activation tensors of 2^31 elements or more are not supported");
         return GHN3_E_LIMIT;
+    }
+    return GHN3_OK;
+}
+
+// Steps 2 - 4 of the backward, shared by the with-norm (NORM = true) and the plain family (NORM = false: dz = dout; z, stats, gamma,
+// s12 are null and not read): dy = dz W_pw, dW_pw, dx and dW_dw.
+template <bool NORM>
+int dwpw_bwd_products(const Desc& d, const Plan& pl, const float* dout, const float* z, const float* stats, const float* gamma,
+                      const float* s12, const float* x, const float* w_dw, const float* w_pw, float* dx, float* dw_dw, float* dw_pw,
+                      float* dy, float* part_pw, float* part_dw, hipStream_t s) {
+    const int taps = d.ks * d.ks;
+    // 2. dy = dz W_pw
+    {
+        int rc;
+        const int NT = nt_of(d.C_in);
+        const size_t lds = bwd_lds(NT);
+#define BWD_CASE(n) case n: rc = tnet_raise_lds(tnet_dwpw_bwd_data_kernel<n, NORM>, lds); if (rc) return rc; \
+        hipLaunchKernelGGL((tnet_dwpw_bwd_data_kernel<n, NORM>), dim3(pl.n_tiles), dim3(256), lds, s, dout, z, stats, gamma, s12, w_pw, dy, d, pl.P); break;
+        switch (NT) { BWD_CASE(4) BWD_CASE(8) BWD_CASE(16) BWD_CASE(32) }
+#undef BWD_CASE
+        TNET_LAUNCH_CHECK("dwpw bwd data")
+    }
+    // 3. dW_pw
+    hipLaunchKernelGGL(tnet_pw_wgrad_kernel<NORM>, dim3(pl.pw_chunks, (d.C_out + 63) / 64, (d.C_in + 63) / 64), dim3(256), 0, s, dout, z, stats,
+                       gamma, s12, x, w_dw, part_pw, d, pl.P, pl.pw_chunk_px);
+    TNET_LAUNCH_CHECK("pw wgrad")
+    {
+        const int64_t cols = (int64_t)d.C_out * d.C_in;
+        hipLaunchKernelGGL(tnet_reduce_rows_kernel, dim3((int)((cols / 4 + 15) / 16)), dim3(256), 0, s, part_pw, pl.pw_chunks, cols, dw_pw, 0, 0);
+        TNET_LAUNCH_CHECK("pw wgrad reduce")
+    }
+    // 4. dx and dW_dw
+    {
+        const int64_t total4 = (int64_t)d.N * d.H * d.W * d.C_in / 4;
+        hipLaunchKernelGGL(tnet_dw_bwd_data_kernel, dim3((int)std::min<int64_t>((total4 + 255) / 256, 8192)), dim3(256), 0, s, dy, x, w_dw,
+                           dx, d, total4);
+        TNET_LAUNCH_CHECK("dw bwd data")
+        if (w_dw) {
+            const int nq = d.C_in / 4;
+            hipLaunchKernelGGL(tnet_dw_wgrad_kernel, dim3(pl.dw_chunks), dim3(256), (size_t)std::max(1, 256 / nq) * 16 * nq * 16, s, dy, x,
+                               part_dw, d, pl.P, pl.dw_chunk_px);
+            TNET_LAUNCH_CHECK("dw wgrad")
+            const int64_t cols = (int64_t)taps * d.C_in;
+            hipLaunchKernelGGL(tnet_reduce_rows_kernel, dim3((int)((cols / 4 + 15) / 16)), dim3(256), 0, s, part_dw, pl.dw_chunks, cols,
+                               dw_dw, d.C_in, taps);
+            TNET_LAUNCH_CHECK("dw wgrad reduce")
+        }
     }
     return GHN3_OK;
 }
@@ -788,7 +853,6 @@ extern "C" int ghn3_dwpw_bn_bwd(const ghn3_dwpw_desc* g, const float* dout, cons
     if (!w_dw && (d.ks != 1 || d.pad != 0)) { ghn3_set_error("dwpw: without depthwise weights ks = 1, pad = 0"); return GHN3_E_ARG; }
     hipStream_t s = (hipStream_t)stream_;
     const Plan pl = make_plan(d);
-    const int taps = d.ks * d.ks;
     float* part12 = scratch;
     float* const s12_scratch = part12 + (int64_t)pl.n_tiles * 2 * d.C_out;
     // (dbeta directly followed by dgamma -- how target_ops.py lays them out -- IS the [sum dout | sum dout xhat] pair: no copies)
@@ -811,43 +875,56 @@ extern "C" int ghn3_dwpw_bn_bwd(const ghn3_dwpw_desc* g, const float* dout, cons
             hipMemcpyAsync(dgamma, s12 + d.C_out, (size_t)d.C_out * 4, hipMemcpyDeviceToDevice, s);
         }
     }
-    // 2. dy = dz W_pw
-    {
-        const int NT = nt_of(d.C_in);
-        const size_t lds = bwd_lds(NT);
-#define BWD_CASE(n) case n: rc = tnet_raise_lds(tnet_dwpw_bwd_data_kernel<n>, lds); if (rc) return rc; \
-        hipLaunchKernelGGL((tnet_dwpw_bwd_data_kernel<n>), dim3(pl.n_tiles), dim3(256), lds, s, dout, z, stats, gamma, s12, w_pw, dy, d, pl.P); break;
-        switch (NT) { BWD_CASE(4) BWD_CASE(8) BWD_CASE(16) BWD_CASE(32) }
-#undef BWD_CASE
-        TNET_LAUNCH_CHECK("dwpw bwd data")
-    }
-    // 3. dW_pw
-    hipLaunchKernelGGL(tnet_pw_wgrad_kernel, dim3(pl.pw_chunks, (d.C_out + 63) / 64, (d.C_in + 63) / 64), dim3(256), 0, s, dout, z, stats,
-                       gamma, s12, x, w_dw, part_pw, d, pl.P, pl.pw_chunk_px);
-    TNET_LAUNCH_CHECK("pw wgrad")
-    {
-        const int64_t cols = (int64_t)d.C_out * d.C_in;
-        hipLaunchKernelGGL(tnet_reduce_rows_kernel, dim3((int)((cols / 4 + 15) / 16)), dim3(256), 0, s, part_pw, pl.pw_chunks, cols, dw_pw, 0, 0);
-        TNET_LAUNCH_CHECK("pw wgrad reduce")
-    }
-    // 4. dx and dW_dw
-    {
-        const int64_t total4 = (int64_t)d.N * d.H * d.W * d.C_in / 4;
-        hipLaunchKernelGGL(tnet_dw_bwd_data_kernel, dim3((int)std::min<int64_t>((total4 + 255) / 256, 8192)), dim3(256), 0, s, dy, x, w_dw,
-                           dx, d, total4);
-        TNET_LAUNCH_CHECK("dw bwd data")
-        if (w_dw) {
-            const int nq = d.C_in / 4;
-            hipLaunchKernelGGL(tnet_dw_wgrad_kernel, dim3(pl.dw_chunks), dim3(256), (size_t)std::max(1, 256 / nq) * 16 * nq * 16, s, dy, x,
-                               part_dw, d, pl.P, pl.dw_chunk_px);
-            TNET_LAUNCH_CHECK("dw wgrad")
-            const int64_t cols = (int64_t)taps * d.C_in;
-            hipLaunchKernelGGL(tnet_reduce_rows_kernel, dim3((int)((cols / 4 + 15) / 16)), dim3(256), 0, s, part_dw, pl.dw_chunks, cols,
-                               dw_dw, d.C_in, taps);
-            TNET_LAUNCH_CHECK("dw wgrad reduce")
-        }
-    }
+    return dwpw_bwd_products<true>(d, pl, dout, z, stats, gamma, s12, x, w_dw, w_pw, dx, dw_dw, dw_pw, dy, part_pw, part_dw, s);
+}
+
+// ---- the same family without a norm layer: out = pw(dw(relu(x))) -- the blocks of a norm=None network (ops.py:91-96) -----------
+// Forward: the forward kernel alone, its accumulators stored straight to `out` (no z, no statistics, no scratch).  Backward: dz IS
+// dout, so steps 2 - 4 of the backward above run on dout directly; nothing of activation size but x is kept between the two.
+extern "C" int64_t ghn3_dwpw_plain_scratch_floats(const ghn3_dwpw_desc* g, int backward) {
+    Desc d;
+    if (check_desc(g, d)) return -1;
+    if (!backward) return 0;
+    const Plan pl = make_plan(d);
+    return (int64_t)pl.P * d.C_in + (int64_t)pl.pw_chunks * d.C_out * d.C_in + (int64_t)pl.dw_chunks * d.ks * d.ks * d.C_in + 256;
+}
+
+extern "C" int ghn3_dwpw_plain_fwd(const ghn3_dwpw_desc* g, const float* x, const float* w_dw, const float* w_pw, float* out,
+                                   void* stream_) {
+    Desc d;
+    int rc = check_desc(g, d);
+    if (rc) return rc;
+    if (!x || !w_pw || !out) { ghn3_set_error("dwpw plain fwd: null pointer"); return GHN3_E_ARG; }
+    if (!w_dw && (d.ks != 1 || d.pad != 0)) { ghn3_set_error("dwpw: without depthwise weights the op is ReLU -> 1x1 conv: ks = 1, pad = 0"); return GHN3_E_ARG; }
+    hipStream_t s = (hipStream_t)stream_;
+    const Plan pl = make_plan(d);
+    const int NT = nt_of(d.C_out);
+    const size_t lds = fwd_lds(NT, false);
+    float* const no_part = nullptr;
+#define FWD_CASE(n) case n: rc = tnet_raise_lds(tnet_dwpw_fwd_kernel<n, false>, lds); if (rc) return rc; \
+        hipLaunchKernelGGL((tnet_dwpw_fwd_kernel<n, false>), dim3(pl.n_tiles), dim3(256), lds, s, x, w_dw, w_pw, out, no_part, d, pl.P); break;
+    switch (NT) { FWD_CASE(4) FWD_CASE(8) FWD_CASE(16) FWD_CASE(32) }
+#undef FWD_CASE
+    TNET_LAUNCH_CHECK("dwpw plain fwd")
     return GHN3_OK;
+}
+
+extern "C" int ghn3_dwpw_plain_bwd(const ghn3_dwpw_desc* g, const float* dout, const float* x, const float* w_dw, const float* w_pw,
+                                   float* dx, float* dw_dw, float* dw_pw, float* scratch, void* stream_) {
+    Desc d;
+    int rc = check_desc(g, d);
+    if (rc) return rc;
+    if (!dout || !x || !w_pw || !dx || !dw_pw || !scratch || (w_dw && !dw_dw)) {
+        ghn3_set_error("dwpw plain bwd: null pointer");
+        return GHN3_E_ARG;
+    }
+    if (!w_dw && (d.ks != 1 || d.pad != 0)) { ghn3_set_error("dwpw: without depthwise weights ks = 1, pad = 0"); return GHN3_E_ARG; }
+    const Plan pl = make_plan(d);
+    float* dy = scratch;
+    float* part_pw = dy + (int64_t)pl.P * d.C_in;
+    float* part_dw = part_pw + (int64_t)pl.pw_chunks * d.C_out * d.C_in;
+    return dwpw_bwd_products<false>(d, pl, dout, nullptr, nullptr, nullptr, nullptr, x, w_dw, w_pw, dx, dw_dw, dw_pw, dy, part_pw,
+                                    part_dw, (hipStream_t)stream_);
 }
 
 // ---- dense convolution family: the forward / input-gradient kernel and the host side -------------------------------------------

@@ -59,8 +59,10 @@ def sample_genotype(rng, vit=False, max_steps=4):
     return ops.Genotype(normal=normal, normal_concat=n_cat, reduce=reduce, reduce_concat=r_cat)
 
 
-def sample_net_args(rng, large_images=False):
-    """Network keyword arguments in the ranges the DeepNets-1M loader uses (deepnets1m.py:96-143)."""
+def sample_net_args(rng, large_images=False, bn_free_prob=0.0):
+    """Network keyword arguments in the ranges the DeepNets-1M loader uses (deepnets1m.py:96-143).  With probability
+    `bn_free_prob` the network has no norm layers (norm=None, the BN-Free networks of DeepNets-1M); the draw is the last one and
+    is made only when the probability is positive, so the default stream is the one it always was."""
     vit = rng.rand() < 0.1
     genotype = sample_genotype(rng, vit=vit, max_steps=1 if vit else 4)
     steps = len(genotype.normal_concat)
@@ -75,6 +77,8 @@ def sample_net_args(rng, large_images=False):
         args.update(preproc=False, C_mult=1, stem_pool=False)
     args['is_imagenet_input'] = bool(large_images)
     args['num_classes'] = 1000 if large_images else 10
+    if bn_free_prob > 0 and rng.rand() < bn_free_prob:
+        args['norm'] = None
     return args
 
 
@@ -82,8 +86,9 @@ class SampledNets:
     """A virtual dataset of architectures: ``self[i]`` is a Graph with ``.net`` (a NetworkLight) and ``.net_args``."""
 
     def __init__(self, num_nets=10 ** 6, large_images=False, seed=0, virtual_edges=50, max_nodes=1000, light=True,
-                 verbose=False):
+                 verbose=False, bn_free_prob=0.0):
         self.num_nets, self.large_images, self.seed = int(num_nets), large_images, int(seed)
+        self.bn_free_prob = float(bn_free_prob)
         self.virtual_edges, self.max_nodes, self.light, self.verbose = virtual_edges, max_nodes, light, verbose
 
     def __len__(self):
@@ -93,7 +98,7 @@ class SampledNets:
         idx = int(idx) % self.num_nets
         for attempt in range(64):
             rng = np.random.RandomState((self.seed * 1000003 + idx * 64 + attempt) % (2 ** 31 - 1))
-            args = sample_net_args(rng, self.large_images)
+            args = sample_net_args(rng, self.large_images, self.bn_free_prob)
             try:
                 model = ops.Network(**args)
                 graph = Graph(model, ve_cutoff=self.virtual_edges, verbose=False)
@@ -156,7 +161,8 @@ class DeepNets1MDDP(SampledNets, torch.utils.data.Dataset):
         h5py exist in this image); ``split`` then only selects the stream's seed."""
 
     def __init__(self, split='train', nets_dir=None, virtual_edges=50, num_nets=None, large_images=False, dense=True,
-                 wider_nets=True, debug=False, verbose=False, seed=None, max_nodes=1000, light=True, arch=None, **unused):
+                 wider_nets=True, debug=False, verbose=False, seed=None, max_nodes=1000, light=True, arch=None, bn_free_prob=0.0,
+                 **unused):
         assert dense, 'GHN-3 uses the dense layout'
         self.split, self.is_train, self.dense, self.wider_nets, self.debug = split, split == 'train', dense, wider_nets, debug
         self.store = None
@@ -185,13 +191,14 @@ class DeepNets1MDDP(SampledNets, torch.utils.data.Dataset):
             self.nodes = np.asarray([net['num_nodes'] for net in self.nets], dtype=np.int64)   # (the sampler's node budget)
             self.num_nets, self.large_images, self.virtual_edges = len(self.nets), large_images, virtual_edges
             self.light, self.verbose, self.max_nodes, self.seed = light, verbose, max_nodes, 0
+            self.bn_free_prob = 0.0                             # (the files carry each network's own `norm`)
             return
         if seed is None:                                        # disjoint streams per split
             seed = {'train': 0, 'val': 1, 'test': 2}.get(split, 3)
         if num_nets is None:
             num_nets = 10 ** 6 if self.is_train else 500
         SampledNets.__init__(self, num_nets=num_nets, large_images=large_images, seed=seed, virtual_edges=virtual_edges,
-                             max_nodes=max_nodes, light=light, verbose=verbose)
+                             max_nodes=max_nodes, light=light, verbose=verbose, bn_free_prob=bn_free_prob)
 
     def __len__(self):
         return self.num_nets if self.store is None or self.h5_idx is None else len(self.h5_idx)

@@ -13,6 +13,10 @@ the stock layers the activations are converted (``run_block``): the stock ATen /
 wrong gradients for channels_last inputs, so the layout is not allowed to leak into them.  The weights are the views of the GHN's flat prediction buffer the GHN assigned to the
 layers -- read in place, no copy; their gradients leave as dense tensors for autograd to route back into that buffer.
 
+A network built with norm=None has an Identity in every norm slot (`bn_layer`, ops.py:91-96): its blocks run on the members of
+the families without a norm layer -- ``DwPw`` / ``dwpw`` (ghn3_dwpw_plain_fwd / _bwd) and ``ConvOnly`` / ``conv_only`` --, routed
+by the same runners (``_no_norm``; GHN3_NATIVE_NONORM=0 keeps such blocks on the stock layers).
+
 ``DwPwBn.applicable`` states what the kernels take (fp32 CUDA tensors, batch statistics, C <= 512, ks <= 7); a layer
 outside of it keeps the stock path.  There is no CPU implementation: on a CPU tensor the stock path runs (the target
 networks themselves are torch modules), and ``dwpw_bn`` raises without the library.
@@ -105,6 +109,13 @@ def enabled():
     return os.environ.get('GHN3_NATIVE_OPS', '1') != '0'
 
 
+def _no_norm(bn):
+    """True for the norm slot of a network built with norm=None (`bn_layer`, ops.py:91-96: an Identity layer of either flavour):
+    the block then runs on the no-norm members of the op families (DwPw, ConvOnly).  GHN3_NATIVE_NONORM=0 keeps such blocks on
+    the stock layers (the behaviour before these members existed; A/B measurements)."""
+    return _is_kind(bn, 'Identity') and os.environ.get('GHN3_NATIVE_NONORM', '1') != '0'
+
+
 class DwPwBn(torch.autograd.Function):
     @staticmethod
     def applicable(x, w_dw, w_pw, gamma, beta, ks, training_stats=True):
@@ -170,6 +181,72 @@ class DwPwBn(torch.autograd.Function):
                                       _ptr(dwd) if dwd is not None else None, _ptr(dwp), _ptr(dg), _ptr(db), _ptr(scratch), stream),
                  'ghn3_dwpw_bn_bwd')
         return dx, dwd, dwp, dg, db, None, None, None, None
+
+
+class DwPw(torch.autograd.Function):
+    """ReLU -> depthwise k x k convolution -> pointwise 1 x 1 convolution WITHOUT a norm layer, as ONE autograd node on
+    ghn3_dwpw_plain_fwd / _bwd: `DilConv`, each half of `SepConv` and the 1 x 1 `ReLUConvBN` of a network built with norm=None
+    (ops.py:91-96).  Same conventions as DwPwBn (channels_last storage inside, weights read in place, w_dw None: no depthwise
+    stage); one launch forward, no pre-norm tensor and no statistics: only x and the weights are saved."""
+
+    @staticmethod
+    def applicable(x, w_dw, w_pw, ks):
+        if not (enabled() and torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
+            return False
+        if _autocast_excludes():
+            return False
+        if not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32
+                   for t in (w_pw,) + (() if w_dw is None else (w_dw,))):
+            return False
+        C_in, C_out = x.shape[1], w_pw.shape[0]
+        return C_in % 4 == 0 and C_out % 4 == 0 and C_in <= 512 and C_out <= 512 and ks <= 7 and \
+            x.numel() < 2 ** 31 and (w_dw is None or w_dw.shape[1] == 1) and w_pw.numel() == C_out * C_in
+
+    @staticmethod
+    def forward(ctx, x, w_dw, w_pw, stride, pad, dil):
+        lib = L.load()
+        ks = 1 if w_dw is None else int(w_dw.shape[-1])
+        C_out = int(w_pw.shape[0])
+        xc = x.contiguous(memory_format=torch.channels_last)
+        d = _desc(xc, C_out, ks, stride, pad, dil, 0.0)
+        wd, wp = (None if w_dw is None else w_dw.contiguous()), w_pw.contiguous()
+        out = torch.empty((d.N, C_out, d.Ho, d.Wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+        L._check(lib.ghn3_dwpw_plain_fwd(ctypes.byref(d), _ptr(xc), _ptr(wd) if wd is not None else None, _ptr(wp), _ptr(out),
+                                         _stream()), 'ghn3_dwpw_plain_fwd')
+        ctx.has_dw = wd is not None
+        ctx.save_for_backward(xc, wd if wd is not None else wp, wp)
+        ctx.cfg = (stride, pad, dil)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = L.load()
+        xc, wd, wp = ctx.saved_tensors
+        if not ctx.has_dw:
+            wd = None
+        stride, pad, dil = ctx.cfg
+        C_out, ks = int(wp.shape[0]), (1 if wd is None else int(wd.shape[-1]))
+        d = _desc(xc, C_out, ks, stride, pad, dil, 0.0)
+        do = dout.contiguous(memory_format=torch.channels_last)
+        dx = torch.empty_like(xc)
+        # (one allocation for the parameter gradients and the scratch area, as DwPwBn)
+        n_wd = 0 if wd is None else wd.numel()
+        n_par = (n_wd + wp.numel() + 63) // 64 * 64
+        buf = torch.empty(n_par + _scratch_floats('ghn3_dwpw_plain_scratch_floats', d, 1), dtype=torch.float32, device=xc.device)
+        dwd = None if wd is None else buf[:n_wd].view(wd.shape)
+        dwp = buf[n_wd:n_wd + wp.numel()].view(wp.shape)
+        L._check(lib.ghn3_dwpw_plain_bwd(ctypes.byref(d), _ptr(do), _ptr(xc), _ptr(wd) if wd is not None else None, _ptr(wp),
+                                         _ptr(dx), _ptr(dwd) if dwd is not None else None, _ptr(dwp), _ptr(buf[n_par:]), _stream()),
+                 'ghn3_dwpw_plain_bwd')
+        return dx, dwd, dwp, None, None, None
+
+
+def dwpw(x, w_dw, w_pw, stride=1, padding=0, dilation=1):
+    """out = conv1x1(depthwise_conv(relu(x))), no norm layer; w_dw None: conv1x1(relu(x)) with the stride.  x: (N, C, H, W) fp32
+    CUDA tensor (channels_last preferred), w_dw (C, 1, ks, ks), w_pw (C_out, C, 1, 1) or (C_out, C)."""
+    if not x.is_cuda:
+        raise L.Ghn3Error('dwpw runs on an MI355X only (no CPU implementation: use the stock torch layers)')
+    return DwPw.apply(x, w_dw, w_pw.reshape(w_pw.shape[0], -1), int(stride), int(padding), int(dilation))
 
 
 class _ConvDesc(ctypes.Structure):
@@ -440,10 +517,13 @@ def conv_reference(x, w, gamma, beta, stride=1, padding=0, dilation=1, relu=True
 
 def run_conv_block(layers, x, keep_layout=False):
     """[ReLU, k x k Conv2d, BatchNorm2d] -- `ReLUConvBN` (ops.py:180-198) -- on the fused dense-convolution op where it applies,
-    else layer by layer.  Same layout contract as run_block."""
+    else layer by layer.  Same layout contract as run_block.  An Identity in the norm slot (norm=None): ConvOnly with the ReLU."""
     relu, conv, bn = layers
     gamma, beta, has_run, batch_stats = _norm_inputs(bn)
     w = getattr(conv, 'weight', None)
+    if _no_norm(bn) and _plain_conv(conv) and ConvOnly.applicable(x, w):
+        out = conv_only(x, w, conv.stride, conv.padding, _pair(conv.dilation)[0], relu=True)
+        return _hand_on(out, keep_layout, conv, bn)
     ok = hasattr(bn, 'eps') and _plain_conv(conv) and ConvBn.applicable(x, w, gamma, beta, batch_stats)
     if not ok:
         for m in layers:
@@ -467,6 +547,14 @@ def run_conv_pair_block(layers, x, keep_layout=False):
     (ConvBn without a ReLU); the intermediate stays NHWC.  Else layer by layer."""
     relu, conv_a, conv_b, bn = layers
     gamma, beta, has_run, batch_stats = _norm_inputs(bn)
+    if _no_norm(bn) and _plain_conv(conv_a) and _plain_conv(conv_b) and ConvOnly.applicable(x, conv_a.weight) and \
+            conv_b.weight.shape[1] == conv_a.weight.shape[0]:
+        # (norm=None: two convolution-only nodes; the second one's input is checked on a stand-in, as below)
+        probe = x if conv_a.weight.shape[0] == x.shape[1] else x.new_empty((1, conv_a.weight.shape[0], 1, 1))
+        if ConvOnly.applicable(probe, conv_b.weight):
+            y = conv_only(x, conv_a.weight, conv_a.stride, conv_a.padding, _pair(conv_a.dilation)[0], relu=True)
+            out = conv_only(y, conv_b.weight, conv_b.stride, conv_b.padding, _pair(conv_b.dilation)[0], relu=False)
+            return _hand_on(out, keep_layout, conv_a, conv_b, bn)
     ok = hasattr(bn, 'eps') and _plain_conv(conv_a) and _plain_conv(conv_b) and ConvOnly.applicable(x, conv_a.weight) and \
         conv_b.weight.shape[1] == conv_a.weight.shape[0]
     if ok:
@@ -502,7 +590,8 @@ def _is_kind(m, name):
 
 def run_layer_seq(seq, x):
     """A stem (`nn.Sequential` of Conv2d / BatchNorm2d / ReLU / MaxPool2d / Identity, ops.py:443-463) with every
-    [Conv2d, BatchNorm2d] and [ReLU, Conv2d, BatchNorm2d] window on the fused dense-convolution op and the rest layer by layer.
+    [Conv2d, BatchNorm2d] and [ReLU, Conv2d, BatchNorm2d] window on the fused dense-convolution op and the rest layer by layer
+    (an Identity in the norm slot, norm=None: the same windows on ConvOnly).
     A 3-channel image (the first convolution of every network) is given a zero fourth channel -- and the weight a zero fourth
     input slice, through autograd -- because the kernels read channels in groups of four."""
     layers = list(seq)
@@ -513,7 +602,21 @@ def run_layer_seq(seq, x):
         conv = layers[k + 1] if relu else m
         bn = layers[k + 2] if relu else (layers[k + 1] if k + 1 < n else None)
         done = False
-        if _is_kind(conv, 'Conv2d') and bn is not None and _is_kind(bn, 'BatchNorm2d') and hasattr(bn, 'eps') and \
+        if _is_kind(conv, 'Conv2d') and bn is not None and _no_norm(bn) and _plain_conv(conv) and torch.is_tensor(x) and \
+                x.is_cuda and x.dim() == 4:
+            # the same windows of a norm=None stem, [Conv2d, Identity] and [ReLU, Conv2d, Identity], on the convolution alone
+            w, xin = conv.weight, x
+            if x.shape[1] == 3 and w.shape[1] == 3:
+                xin, w = F.pad(x, (0, 0, 0, 0, 0, 1)), F.pad(w, (0, 0, 0, 0, 0, 1))
+            if ConvOnly.applicable(xin, w):
+                fold = bool(relu)
+                if relu and k == 0 and getattr(m, 'inplace', False):
+                    xin, fold = m(xin), False                  # (the caller's tensor is rewritten, as below: stem1)
+                x = conv_only(xin, w, conv.stride, conv.padding, _pair(conv.dilation)[0], relu=fold)
+                x = _hand_on(x, False, conv, bn)
+                k += 3 if relu else 2
+                done = True
+        elif _is_kind(conv, 'Conv2d') and bn is not None and _is_kind(bn, 'BatchNorm2d') and hasattr(bn, 'eps') and \
                 _plain_conv(conv) and torch.is_tensor(x) and x.is_cuda and x.dim() == 4:
             w = conv.weight
             gamma, beta, has_run, batch_stats = _norm_inputs(bn)
@@ -547,7 +650,8 @@ def run_factorized_reduce(relu, conv_1, conv_2, bn, x, stride=2, keep_layout=Fal
     apply (the caller keeps the stock layers)."""
     w1, w2 = getattr(conv_1, 'weight', None), getattr(conv_2, 'weight', None)
     gamma, beta, has_run, batch_stats = _norm_inputs(bn)
-    if not (stride == 2 and hasattr(bn, 'eps') and torch.is_tensor(w1) and torch.is_tensor(w2) and x.dim() == 4 and
+    plain = _no_norm(bn)
+    if not (stride == 2 and (plain or hasattr(bn, 'eps')) and torch.is_tensor(w1) and torch.is_tensor(w2) and x.dim() == 4 and
             x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0 and getattr(conv_1, 'bias', None) is None and
             getattr(conv_2, 'bias', None) is None and w1.shape == w2.shape and tuple(w1.shape[2:]) == (1, 1)):
         return None
@@ -555,6 +659,10 @@ def run_factorized_reduce(relu, conv_1, conv_2, bn, x, stride=2, keep_layout=Fal
     w = torch.zeros(2 * half, C_in, 2, 2, dtype=w1.dtype, device=w1.device)
     w[:half, :, 0, 0] = w1[:, :, 0, 0]
     w[half:, :, 1, 1] = w2[:, :, 0, 0]
+    if plain:                                              # (norm=None: the same 2 x 2 convolution alone)
+        if not ConvOnly.applicable(x, w):
+            return None
+        return _hand_on(conv_only(x, w, 2, 0, 1, relu=True), keep_layout, conv_1, conv_2, bn)
     if not ConvBn.applicable(x, w, gamma, beta, batch_stats):
         return None
     out, stats = conv_bn(x, w, gamma, beta, 2, 0, 1, True, bn.eps)
@@ -578,10 +686,12 @@ def run_pointwise_block(layers, x, keep_layout=False):
     relu, pw, bn = layers
     w_pw = getattr(pw, 'weight', None)
     gamma, beta, has_run, batch_stats = _norm_inputs(bn)
-    ok = hasattr(bn, 'eps') and getattr(pw, 'bias', None) is None and hasattr(pw, 'kernel_size') and \
+    layer_ok = getattr(pw, 'bias', None) is None and hasattr(pw, 'kernel_size') and \
         tuple(pw.kernel_size) == (1, 1) and pw.stride[0] == pw.stride[1] and not isinstance(pw.padding, str) and \
-        tuple(pw.padding) == (0, 0) and getattr(pw, 'groups', 1) == 1 and torch.is_tensor(w_pw) and \
-        DwPwBn.applicable(x, None, w_pw, gamma, beta, 1, batch_stats)
+        tuple(pw.padding) == (0, 0) and getattr(pw, 'groups', 1) == 1 and torch.is_tensor(w_pw)
+    if _no_norm(bn) and layer_ok and DwPw.applicable(x, None, w_pw, 1):
+        return _hand_on(dwpw(x, None, w_pw, pw.stride[0], 0, 1), keep_layout, pw, bn)
+    ok = hasattr(bn, 'eps') and layer_ok and DwPwBn.applicable(x, None, w_pw, gamma, beta, 1, batch_stats)
     if not ok:
         # (e.g. more than 512 input channels -- the concatenated states of a wide cell: the dense-convolution op takes those)
         return run_conv_block(layers, x, keep_layout)
@@ -627,14 +737,17 @@ def run_block(layers, x, keep_layout=False):
     w_dw, w_pw = getattr(dw, 'weight', None), getattr(pw, 'weight', None)
     gamma, beta, has_run, batch_stats = _norm_inputs(bn)
     ks = dw.kernel_size[0] if hasattr(dw, 'kernel_size') else 0
-    ok = hasattr(bn, 'eps') and getattr(dw, 'bias', None) is None and getattr(pw, 'bias', None) is None and \
+    layers_ok = getattr(dw, 'bias', None) is None and getattr(pw, 'bias', None) is None and \
         hasattr(dw, 'kernel_size') and dw.kernel_size[0] == dw.kernel_size[1] and dw.stride[0] == dw.stride[1] and \
         not isinstance(dw.padding, str) and dw.padding[0] == dw.padding[1] and dw.dilation[0] == dw.dilation[1] and \
         getattr(dw, 'groups', 1) == x.shape[1] and tuple(pw.kernel_size) == (1, 1) and \
         tuple(getattr(pw, 'stride', (1, 1))) == (1, 1) and not isinstance(getattr(pw, 'padding', 0), str) and \
         tuple(getattr(pw, 'padding', (0, 0))) == (0, 0) and getattr(pw, 'groups', 1) == 1 and \
-        tuple(getattr(pw, 'dilation', (1, 1))) == (1, 1) and \
-        DwPwBn.applicable(x, w_dw, w_pw, gamma, beta, ks, batch_stats)
+        tuple(getattr(pw, 'dilation', (1, 1))) == (1, 1)
+    if _no_norm(bn) and layers_ok and DwPw.applicable(x, w_dw, w_pw, ks):
+        # (norm=None: the family's member without a norm layer)
+        return _hand_on(dwpw(x, w_dw, w_pw, dw.stride[0], dw.padding[0], dw.dilation[0]), keep_layout, dw, pw, bn)
+    ok = hasattr(bn, 'eps') and layers_ok and DwPwBn.applicable(x, w_dw, w_pw, gamma, beta, ks, batch_stats)
     if not ok:
         for m in layers:
             x = m(x)

@@ -541,6 +541,18 @@ int ghn3_dwpw_bn_bwd(const ghn3_dwpw_desc* desc, const float* dout, const float*
                      const float* w_dw, const float* w_pw, const float* gamma, float* dx, float* dw_dw, float* dw_pw,
                      float* dgamma, float* dbeta, float* scratch, void* stream);
 
+/* The same family WITHOUT a norm layer -- the blocks of a network built with norm = None, whose norm slots are Identity layers
+ * (ops.py:91-96; the BN-Free split of DeepNets-1M): out = pw(dw(relu(x))), with w_dw == NULL (ks = 1, pad = 0) = conv1x1(relu(x))
+ * with a stride.  Same descriptor (`eps` ignored), limits, NHWC fp32 conventions and in-place weight views; added without an ABI
+ * version step (symbols only).  Forward: ONE launch, the products stored straight to `out` -- no pre-norm tensor, no statistics,
+ * no scratch.  Backward: the gradient of the pre-norm activations IS dout, so the two products and the depthwise kernels run on
+ * it directly (6 launches, 3 without a depthwise stage); nothing of activation size but x is kept between the two directions.
+ * ghn3_dwpw_plain_scratch_floats: 0 for the forward.  Deterministic. */
+int64_t ghn3_dwpw_plain_scratch_floats(const ghn3_dwpw_desc* desc, int backward);
+int ghn3_dwpw_plain_fwd(const ghn3_dwpw_desc* desc, const float* x, const float* w_dw, const float* w_pw, float* out, void* stream);
+int ghn3_dwpw_plain_bwd(const ghn3_dwpw_desc* desc, const float* dout, const float* x, const float* w_dw, const float* w_pw,
+                        float* dx, float* dw_dw, float* dw_pw, float* scratch, void* stream);
+
 
 /* ---- target-network layers, second slice (ABI v19, round 6): [ReLU ->] dense kh x kw convolution -> BatchNorm -------------
  * `ReLUConvBN` with a k x k kernel and its 1 x k / k x 1 halves (/root/reference/ghn3/ops.py:180-198; the `conv_3x3 / 5x5 /

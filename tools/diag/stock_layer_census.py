@@ -1,6 +1,8 @@
 """Diagnostic: which layers of the training loop's target networks still run on stock ATen / MIOpen kernels?
 Runs Trainer.update on the architecture stream of examples/train_ghn_ddp.py and counts, per step, the stock Conv2d / BatchNorm2d /
-Linear / pooling calls and F.cross_entropy calls by configuration and by the module class that issued them."""
+Linear / pooling calls and F.cross_entropy calls by configuration and by the module class that issued them.
+--bn-free-prob P: the share of the stream drawn without norm layers (norm=None), as in examples/train_ghn_ddp.py."""
+import argparse
 import collections
 import inspect
 import os
@@ -15,6 +17,9 @@ from ghn3_amd.deepnets1m import SampledNets
 from ghn3_amd.graph import GraphBatch
 
 STEPS = int(os.environ.get('CENSUS_STEPS', '12'))
+_ap = argparse.ArgumentParser()
+_ap.add_argument('--bn-free-prob', type=float, default=0.0)
+BN_FREE_PROB = _ap.parse_args().bn_free_prob
 counts = collections.Counter()
 host = collections.Counter()
 
@@ -67,7 +72,8 @@ trainer = Trainer(ghn, opt='adamw', opt_args={'lr': 4e-4, 'weight_decay': 1e-2},
 gen = torch.Generator().manual_seed(1)
 images = torch.randn(64, 3, 32, 32, generator=gen).cuda()
 targets = torch.randint(0, 10, (64,), generator=gen).cuda()
-nets = SampledNets(large_images=False, seed=0, max_nodes=400)
+nets = SampledNets(large_images=False, seed=0, max_nodes=400, bn_free_prob=BN_FREE_PROB)
+print('architecture stream: seed 0, max_nodes 400, bn_free_prob %g, %d steps of 8 networks' % (BN_FREE_PROB, STEPS))
 for step in range(STEPS):
     gb = GraphBatch([nets[step * 8 + k] for k in range(8)], dense=True)
     trainer.update(images, targets, graphs=gb)
@@ -81,6 +87,8 @@ print('stock layer calls per step, by (layer, issuing class):')
 for (kind, who), n in by_kind.most_common():
     t = sum(v for (k2, w2, _), v in host.items() if (k2, w2) == (kind, who))
     print('  %-20s %-24s %7.1f calls/step  %7.2f ms host/step (forward only)' % (kind, who, n / STEPS, 1e3 * t / STEPS))
+print('stock Conv2d calls in all: %d, stock BatchNorm2d calls in all: %d' % (
+    sum(n for (k, _), n in by_kind.items() if k == 'Conv2d'), sum(n for (k, _), n in by_kind.items() if k == 'BatchNorm2d')))
 print('top Conv2d configurations:')
 for (kind, who, cfg), n in counts.most_common(400):
     if kind == 'Conv2d':
