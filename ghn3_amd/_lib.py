@@ -72,6 +72,8 @@ EXPORTS = ['ghn3_abi_version', 'ghn3_last_error', 'ghn3_ctx_create', 'ghn3_ctx_d
            'ghn3_event_elapsed_ms', 'ghn3_event_destroy', 'ghn3_profile_enable', 'ghn3_profile_read',
            'ghn3_profile_read_tags', 'ghn3_dwpw_scratch_floats', 'ghn3_dwpw_bn_fwd', 'ghn3_dwpw_bn_bwd',
            'ghn3_dwpw_plain_scratch_floats', 'ghn3_dwpw_plain_fwd', 'ghn3_dwpw_plain_bwd',
+           'ghn3_dwpw_frozen_scratch_floats', 'ghn3_dwpw_frozen_fwd', 'ghn3_dwpw_frozen_bwd',
+           'ghn3_conv_frozen_scratch_floats', 'ghn3_conv_frozen_fwd', 'ghn3_conv_frozen_bwd',
            'ghn3_conv_scratch_floats', 'ghn3_conv_bn_fwd', 'ghn3_conv_bn_bwd', 'ghn3_se_fwd', 'ghn3_se_bwd', 'ghn3_pool_fwd', 'ghn3_pool_bwd',
            'ghn3_msa_scratch_floats', 'ghn3_msa_fwd', 'ghn3_msa_bwd', 'ghn3_head_scratch_floats', 'ghn3_head_fwd',
            'ghn3_head_bwd', 'ghn3_xent_fwd', 'ghn3_xent_bwd', 'ghn3_join_fwd', 'ghn3_join_bwd', 'ghn3_posenc_bwd',
@@ -126,6 +128,14 @@ def load():
         lib.ghn3_dwpw_plain_scratch_floats.restype = ctypes.c_int64
         lib.ghn3_dwpw_plain_fwd.argtypes = [ctypes.c_void_p] * 6
         lib.ghn3_dwpw_plain_bwd.argtypes = [ctypes.c_void_p] * 10
+        lib.ghn3_dwpw_frozen_scratch_floats.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        lib.ghn3_dwpw_frozen_scratch_floats.restype = ctypes.c_int64
+        lib.ghn3_dwpw_frozen_fwd.argtypes = [ctypes.c_void_p] * 11
+        lib.ghn3_dwpw_frozen_bwd.argtypes = [ctypes.c_void_p] * 16
+        lib.ghn3_conv_frozen_scratch_floats.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        lib.ghn3_conv_frozen_scratch_floats.restype = ctypes.c_int64
+        lib.ghn3_conv_frozen_fwd.argtypes = [ctypes.c_void_p] * 11
+        lib.ghn3_conv_frozen_bwd.argtypes = [ctypes.c_void_p] * 14
         lib.ghn3_conv_scratch_floats.argtypes = [ctypes.c_void_p, ctypes.c_int]
         lib.ghn3_conv_scratch_floats.restype = ctypes.c_int64
         lib.ghn3_conv_bn_fwd.argtypes = [ctypes.c_void_p] * 10

@@ -31,6 +31,11 @@
 // are Identity layers): the same kernels with NORM = false.  The forward is dwpw_fwd alone -- its accumulators are the output, no
 // z, no statistics --; in the backward dz IS dout, so dwpw_bwd_data and pw_wgrad load it plainly and bn_bwd_partial is not run:
 // one launch forward, six backward, nothing of activation size kept between them but x.
+// With a norm layer that normalises with RUNNING statistics (ghn3_dwpw_frozen_fwd / _bwd, ghn3_conv_frozen_fwd / _bwd: a
+// BatchNorm in eval mode): the same kernels with NORM = NORM_FROZEN.  The norm is a per-channel affine map whose constants are
+// known before the launch, so the forward applies it to its accumulators in the epilogue -- no statistics, no second pass --
+// and the backward has dz = dout gamma rstd without the two batch-mean terms; dgamma / dbeta come from bn_bwd_partial +
+// reduce_rows on the frozen (mean, rstd).
 
 #include <algorithm>
 #include "tnet_common.h"
@@ -52,6 +57,28 @@ struct Desc {
     int N, H, W, C_in, C_out, ks, stride, pad, dil, Ho, Wo;
     float eps;
 };
+
+// What follows the convolution (the NORM template parameter of the kernels): nothing, a BatchNorm with batch statistics, or a
+// BatchNorm with frozen (running) statistics.
+constexpr int NORM_NONE = 0, NORM_BATCH = 1, NORM_FROZEN = 2;
+
+// The constants of a BatchNorm with frozen statistics, [C_out] each, and where the forward stores its result (NORM_FROZEN
+// only; a zero-filled struct otherwise).
+struct Frozen {
+    const float *gamma, *beta, *mean, *var;
+    float* out;
+};
+
+// (v - mean) rstd gamma + beta of the four consecutive channels col .. col + 3 a lane owns in a fragment: four-float loads of
+// the constants, rstd = 1 / sqrt(var + eps) as tnet_bn_finalize_kernel forms it, the expression of tnet_bn_apply_kernel
+__device__ __forceinline__ f32x4 frozen_affine4(const f32x4 v, const Frozen& fz, int col, float eps) {
+    const f32x4 mu = *reinterpret_cast<const f32x4*>(fz.mean + col), va = *reinterpret_cast<const f32x4*>(fz.var + col);
+    const f32x4 ga = *reinterpret_cast<const f32x4*>(fz.gamma + col), be = *reinterpret_cast<const f32x4*>(fz.beta + col);
+    f32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = (v[e] - mu[e]) * (1.f / sqrtf(va[e] + eps)) * ga[e] + be[e];
+    return o;
+}
 
 // two values at once on the hardware converter (v_cvt_pk_bf16_f32, round to nearest even as bf16_rn): low half = a
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
@@ -166,31 +193,52 @@ __device__ __forceinline__ void dz_in8(const float* __restrict__ dz, int C, int 
     }
 }
 
-// The operand rows of the backward products: NORM = true forms dz from (dout, z, statistics); NORM = false -- the family
-// without a norm layer -- has dz = dout, a plain load (z, stats, gamma, s12 are not touched).
-template <bool NORM>
+// dz of 8 consecutive channels behind a norm layer with frozen statistics: gamma rstd dout (stats = mean | rstd)
+__device__ __forceinline__ void dz_frozen8(const float* __restrict__ dout, const float* __restrict__ stats,
+                                           const float* __restrict__ gamma, int C, int p, int P, int c, float (&out)[8]) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) out[e] = 0.f;
+    if (p >= P) return;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int cc = c + 4 * h;
+        if (cc >= C) break;
+        const f32x4 g = *reinterpret_cast<const f32x4*>(dout + (int64_t)p * C + cc);
+        const f32x4 rs = *reinterpret_cast<const f32x4*>(stats + C + cc), ga = *reinterpret_cast<const f32x4*>(gamma + cc);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) out[4 * h + e] = ga[e] * rs[e] * g[e];
+    }
+}
+
+// The operand rows of the backward products: NORM_BATCH forms dz from (dout, z, statistics); NORM_NONE -- the family without a
+// norm layer -- has dz = dout, a plain load (z, stats, gamma, s12 are not touched); NORM_FROZEN scales dout by gamma rstd (z and
+// s12 are not touched).
+template <int NORM>
 __device__ __forceinline__ void dz_operand8(const float* __restrict__ dout, const float* __restrict__ z, const float* __restrict__ stats,
                                             const float* __restrict__ gamma, const float* __restrict__ s12, int C, int p, int P, int c,
                                             float (&out)[8]) {
-    if constexpr (NORM) dz8(dout, z, stats, gamma, s12, C, p, P, c, out);
+    if constexpr (NORM == NORM_BATCH) dz8(dout, z, stats, gamma, s12, C, p, P, c, out);
+    else if constexpr (NORM == NORM_FROZEN) dz_frozen8(dout, stats, gamma, C, p, P, c, out);
     else dz_in8(dout, C, p, P, c, out);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// forward: z = pw(dw(relu(x))), per-tile channel statistics.  NORM = false: z is the op's output and the kernel ends with its
-// store (no statistics, `part` not touched, no `red` section in LDS).
+// forward: z = pw(dw(relu(x))), per-tile channel statistics.  NORM_NONE: z is the op's output and the kernel ends with its
+// store (no statistics, `part` not touched, no `red` section in LDS).  NORM_FROZEN: the affine map of the frozen norm layer is
+// applied to the accumulators and stored to fz.out; z (the pre-affine result the backward reads) is stored as well when it is
+// non-null; no statistics, `part` and `red` as for NORM_NONE.
 // ---------------------------------------------------------------------------------------------------------------------
-template <int NT, bool NORM = true>
+template <int NT, int NORM = NORM_BATCH>
 __global__ __launch_bounds__(256) void tnet_dwpw_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w_dw,
                                                             const float* __restrict__ w_pw, float* __restrict__ z,
-                                                            float* __restrict__ part, const Desc d, const int P) {
+                                                            float* __restrict__ part, const Desc d, const int P, const Frozen fz) {
     constexpr int S = terms_of(NT);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     int* pix = reinterpret_cast<int*>(smem);                                   // [3][TP]
     float* wt = reinterpret_cast<float*>(smem + 3 * TP * 4);                   // [MAXT][KC]
     unsigned short* As = reinterpret_cast<unsigned short*>(smem + 3 * TP * 4 + MAXT * KC * 4);      // [S][TP][LDK]
     unsigned short* Bs = As + S * TP * LDK;                                                          // [S][16 NT][LDK]
-    [[maybe_unused]] float* red = reinterpret_cast<float*>(Bs + S * 16 * NT * LDK);   // [5][16 NT] (NORM only)
+    [[maybe_unused]] float* red = reinterpret_cast<float*>(Bs + S * 16 * NT * LDK);   // [5][16 NT] (NORM_BATCH only)
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r16 = lane & 15, kc = lane >> 4;
     const int tile = blockIdx.x, p0 = tile * TP, taps = d.ks * d.ks;
     if (tid < TP) {
@@ -239,12 +287,23 @@ __global__ __launch_bounds__(256) void tnet_dwpw_fwd_kernel(const float* __restr
     // ---- epilogue: z, then per-tile (mean, M2) of every channel
     const int prow = p0 + 16 * w + r16;
     const bool valid = prow < P;
+    if constexpr (NORM == NORM_FROZEN) {
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            const int col = 16 * j + 4 * kc;
+            if (valid && col < d.C_out) {
+                if (z) *reinterpret_cast<f32x4*>(z + (int64_t)prow * d.C_out + col) = acc[j];
+                *reinterpret_cast<f32x4*>(fz.out + (int64_t)prow * d.C_out + col) = frozen_affine4(acc[j], fz, col, d.eps);
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
         const int col = 16 * j + 4 * kc;
         if (valid && col < d.C_out) *reinterpret_cast<f32x4*>(z + (int64_t)prow * d.C_out + col) = acc[j];
     }
-    if constexpr (NORM) {
+    if constexpr (NORM == NORM_BATCH) {
         const int cnt = min(TP, P - p0);
         auto tile_sum = [&](bool centred) {
             __syncthreads();
@@ -379,8 +438,8 @@ __global__ __launch_bounds__(256) void tnet_reduce_rows_kernel(const float* __re
     }
 }
 
-// dy [P][C_in] = dz [P][C_out] W_pw [C_out][C_in]; dz formed on the fly (NORM = false: dz = dout)
-template <int NT, bool NORM = true>
+// dy [P][C_in] = dz [P][C_out] W_pw [C_out][C_in]; dz formed on the fly (dz_operand8)
+template <int NT, int NORM = NORM_BATCH>
 __global__ __launch_bounds__(256) void tnet_dwpw_bwd_data_kernel(const float* __restrict__ dout, const float* __restrict__ z,
                                                                  const float* __restrict__ stats, const float* __restrict__ gamma,
                                                                  const float* __restrict__ s12, const float* __restrict__ w_pw,
@@ -434,7 +493,7 @@ __global__ __launch_bounds__(256) void tnet_dwpw_bwd_data_kernel(const float* __
 }
 
 // part[chunk][co][ci] = sum over the chunk's pixels of dz[p][co] y[p][ci]; workgroup = (chunk, 64 co, 64 ci)
-template <bool NORM = true>
+template <int NORM = NORM_BATCH>
 __global__ __launch_bounds__(256) void tnet_pw_wgrad_kernel(const float* __restrict__ dout, const float* __restrict__ z,
                                                             const float* __restrict__ stats, const float* __restrict__ gamma,
                                                             const float* __restrict__ s12, const float* __restrict__ x,
@@ -756,9 +815,40 @@ int check_desc(const ghn3_dwpw_desc* g, Desc& d) {
     return GHN3_OK;
 }
 
-// Steps 2 - 4 of the backward, shared by the with-norm (NORM = true) and the plain family (NORM = false: dz = dout; z, stats, gamma,
-// s12 are null and not read): dy = dz W_pw, dW_pw, dx and dW_dw.
-template <bool NORM>
+// (mean, var) of a frozen norm layer -> stats[0..C) = mean, stats[C..2C) = 1 / sqrt(var + eps): what tnet_bn_bwd_partial_kernel,
+// dz_frozen8 and tnet_dz_kernel read
+__global__ __launch_bounds__(256) void tnet_bn_frozen_stats_kernel(const float* __restrict__ mean, const float* __restrict__ var,
+                                                                   float eps, int C, float* __restrict__ stats) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c < C) {
+        stats[c] = mean[c];
+        stats[C + c] = 1.f / sqrtf(var[c] + eps);
+    }
+}
+
+// Step 1 of the backward of a norm layer: dbeta = sum dout, dgamma = sum dout xhat over the P pixels (per-tile partials, then a
+// fixed-order reduction).  *s12_out = where the reduced pair [sum dout | sum dout xhat] lies: dbeta directly followed by dgamma --
+// how target_ops.py lays them out -- IS that pair (no copies); otherwise it is reduced into s12_scratch and copied out.
+int bn_param_grads(const float* dout, const float* z, const float* stats, float* part12, float* s12_scratch, float* dgamma,
+                   float* dbeta, int n_tiles, int P, int C, hipStream_t s, const float** s12_out) {
+    const bool in_place = dgamma == dbeta + C;
+    float* s12 = in_place ? dbeta : s12_scratch;
+    const int nq = C / 4, ng = std::max(1, 256 / nq);
+    hipLaunchKernelGGL(tnet_bn_bwd_partial_kernel, dim3(n_tiles), dim3(256), (size_t)ng * 2 * C * 4, s, dout, z, stats, part12, P, C);
+    TNET_LAUNCH_CHECK("bn bwd partial")
+    hipLaunchKernelGGL(tnet_reduce_rows_kernel, dim3((2 * C / 4 + 15) / 16), dim3(256), 0, s, part12, n_tiles, (int64_t)2 * C, s12, 0, 0);
+    TNET_LAUNCH_CHECK("bn bwd reduce")
+    if (!in_place) {
+        (void)hipMemcpyAsync(dbeta, s12, (size_t)C * 4, hipMemcpyDeviceToDevice, s);
+        (void)hipMemcpyAsync(dgamma, s12 + C, (size_t)C * 4, hipMemcpyDeviceToDevice, s);
+    }
+    *s12_out = s12;
+    return GHN3_OK;
+}
+
+// Steps 2 - 4 of the backward, shared by the family's three members (NORM_NONE: dz = dout; z, stats, gamma, s12 are null and not
+// read.  NORM_FROZEN: z and s12 are null and not read): dy = dz W_pw, dW_pw, dx and dW_dw.
+template <int NORM>
 int dwpw_bwd_products(const Desc& d, const Plan& pl, const float* dout, const float* z, const float* stats, const float* gamma,
                       const float* s12, const float* x, const float* w_dw, const float* w_pw, float* dx, float* dw_dw, float* dw_pw,
                       float* dy, float* part_pw, float* part_dw, hipStream_t s) {
@@ -827,7 +917,7 @@ extern "C" int ghn3_dwpw_bn_fwd(const ghn3_dwpw_desc* g, const float* x, const f
     const int NT = nt_of(d.C_out);
     const size_t lds = fwd_lds(NT);
 #define FWD_CASE(n) case n: rc = tnet_raise_lds(tnet_dwpw_fwd_kernel<n>, lds); if (rc) return rc; \
-        hipLaunchKernelGGL((tnet_dwpw_fwd_kernel<n>), dim3(pl.n_tiles), dim3(256), lds, s, x, w_dw, w_pw, z, scratch, d, pl.P); break;
+        hipLaunchKernelGGL((tnet_dwpw_fwd_kernel<n>), dim3(pl.n_tiles), dim3(256), lds, s, x, w_dw, w_pw, z, scratch, d, pl.P, Frozen{}); break;
     switch (NT) { FWD_CASE(4) FWD_CASE(8) FWD_CASE(16) FWD_CASE(32) }
 #undef FWD_CASE
     TNET_LAUNCH_CHECK("dwpw fwd")
@@ -855,27 +945,14 @@ extern "C" int ghn3_dwpw_bn_bwd(const ghn3_dwpw_desc* g, const float* dout, cons
     const Plan pl = make_plan(d);
     float* part12 = scratch;
     float* const s12_scratch = part12 + (int64_t)pl.n_tiles * 2 * d.C_out;
-    // (dbeta directly followed by dgamma -- how target_ops.py lays them out -- IS the [sum dout | sum dout xhat] pair: no copies)
-    const bool s12_in_place = dbeta && dgamma == dbeta + d.C_out;
-    float* s12 = s12_in_place ? dbeta : s12_scratch;
     float* dy = s12_scratch + 2 * d.C_out;
     float* part_pw = dy + (int64_t)pl.P * d.C_in;
     float* part_dw = part_pw + (int64_t)pl.pw_chunks * d.C_out * d.C_in;
     // 1. dgamma / dbeta
-    {
-        const int nq = d.C_out / 4, ng = std::max(1, 256 / nq);
-        hipLaunchKernelGGL(tnet_bn_bwd_partial_kernel, dim3(pl.n_tiles), dim3(256), (size_t)ng * 2 * d.C_out * 4, s, dout, z, stats, part12,
-                           pl.P, d.C_out);
-        TNET_LAUNCH_CHECK("bn bwd partial")
-        hipLaunchKernelGGL(tnet_reduce_rows_kernel, dim3((2 * d.C_out / 4 + 15) / 16), dim3(256), 0, s, part12, pl.n_tiles,
-                           (int64_t)2 * d.C_out, s12, 0, 0);
-        TNET_LAUNCH_CHECK("bn bwd reduce")
-        if (!s12_in_place) {
-            hipMemcpyAsync(dbeta, s12, (size_t)d.C_out * 4, hipMemcpyDeviceToDevice, s);
-            hipMemcpyAsync(dgamma, s12 + d.C_out, (size_t)d.C_out * 4, hipMemcpyDeviceToDevice, s);
-        }
-    }
-    return dwpw_bwd_products<true>(d, pl, dout, z, stats, gamma, s12, x, w_dw, w_pw, dx, dw_dw, dw_pw, dy, part_pw, part_dw, s);
+    const float* s12;
+    rc = bn_param_grads(dout, z, stats, part12, s12_scratch, dgamma, dbeta, pl.n_tiles, pl.P, d.C_out, s, &s12);
+    if (rc) return rc;
+    return dwpw_bwd_products<NORM_BATCH>(d, pl, dout, z, stats, gamma, s12, x, w_dw, w_pw, dx, dw_dw, dw_pw, dy, part_pw, part_dw, s);
 }
 
 // ---- the same family without a norm layer: out = pw(dw(relu(x))) -- the blocks of a norm=None network (ops.py:91-96) -----------
@@ -901,8 +978,8 @@ extern "C" int ghn3_dwpw_plain_fwd(const ghn3_dwpw_desc* g, const float* x, cons
     const int NT = nt_of(d.C_out);
     const size_t lds = fwd_lds(NT, false);
     float* const no_part = nullptr;
-#define FWD_CASE(n) case n: rc = tnet_raise_lds(tnet_dwpw_fwd_kernel<n, false>, lds); if (rc) return rc; \
-        hipLaunchKernelGGL((tnet_dwpw_fwd_kernel<n, false>), dim3(pl.n_tiles), dim3(256), lds, s, x, w_dw, w_pw, out, no_part, d, pl.P); break;
+#define FWD_CASE(n) case n: rc = tnet_raise_lds(tnet_dwpw_fwd_kernel<n, NORM_NONE>, lds); if (rc) return rc; \
+        hipLaunchKernelGGL((tnet_dwpw_fwd_kernel<n, NORM_NONE>), dim3(pl.n_tiles), dim3(256), lds, s, x, w_dw, w_pw, out, no_part, d, pl.P, Frozen{}); break;
     switch (NT) { FWD_CASE(4) FWD_CASE(8) FWD_CASE(16) FWD_CASE(32) }
 #undef FWD_CASE
     TNET_LAUNCH_CHECK("dwpw plain fwd")
@@ -923,8 +1000,72 @@ extern "C" int ghn3_dwpw_plain_bwd(const ghn3_dwpw_desc* g, const float* dout, c
     float* dy = scratch;
     float* part_pw = dy + (int64_t)pl.P * d.C_in;
     float* part_dw = part_pw + (int64_t)pl.pw_chunks * d.C_out * d.C_in;
-    return dwpw_bwd_products<false>(d, pl, dout, nullptr, nullptr, nullptr, nullptr, x, w_dw, w_pw, dx, dw_dw, dw_pw, dy, part_pw,
+    return dwpw_bwd_products<NORM_NONE>(d, pl, dout, nullptr, nullptr, nullptr, nullptr, x, w_dw, w_pw, dx, dw_dw, dw_pw, dy, part_pw,
                                     part_dw, (hipStream_t)stream_);
+}
+
+// ---- the same family behind a norm layer with FROZEN statistics: out = (pw(dw(relu(x))) - mean) rstd gamma + beta, rstd = 1 /
+// sqrt(var + eps) -- the blocks of a network whose BatchNorm layers normalise with their running statistics (eval mode) ----------
+// Forward: the forward kernel alone (NORM_FROZEN): the affine map in its epilogue, z stored beside out only when the caller
+// wants a backward.  Backward: (mean, var) -> (mean, rstd) once, dgamma / dbeta as with batch statistics, then steps 2 - 4 on
+// dz = dout gamma rstd formed on the fly.  The statistics are read only.
+extern "C" int64_t ghn3_dwpw_frozen_scratch_floats(const ghn3_dwpw_desc* g, int backward) {
+    Desc d;
+    if (check_desc(g, d)) return -1;
+    if (!backward) return 0;
+    const Plan pl = make_plan(d);
+    return (int64_t)pl.n_tiles * 2 * d.C_out + 4 * d.C_out + (int64_t)pl.P * d.C_in + (int64_t)pl.pw_chunks * d.C_out * d.C_in +
+           (int64_t)pl.dw_chunks * d.ks * d.ks * d.C_in + 256;
+}
+
+extern "C" int ghn3_dwpw_frozen_fwd(const ghn3_dwpw_desc* g, const float* x, const float* w_dw, const float* w_pw, const float* gamma,
+                                    const float* beta, const float* mean, const float* var, float* z, float* out, void* stream_) {
+    Desc d;
+    int rc = check_desc(g, d);
+    if (rc) return rc;
+    if (!x || !w_pw || !gamma || !beta || !mean || !var || !out) { ghn3_set_error("dwpw frozen fwd: null pointer"); return GHN3_E_ARG; }
+    if (!w_dw && (d.ks != 1 || d.pad != 0)) { ghn3_set_error("dwpw: without depthwise weights the op is ReLU -> 1x1 conv -> norm: ks = 1, pad = 0"); return GHN3_E_ARG; }
+    hipStream_t s = (hipStream_t)stream_;
+    const Plan pl = make_plan(d);
+    const int NT = nt_of(d.C_out);
+    const size_t lds = fwd_lds(NT, false);
+    float* const no_part = nullptr;
+    const Frozen fz = {gamma, beta, mean, var, out};
+#define FWD_CASE(n) case n: rc = tnet_raise_lds(tnet_dwpw_fwd_kernel<n, NORM_FROZEN>, lds); if (rc) return rc; \
+        hipLaunchKernelGGL((tnet_dwpw_fwd_kernel<n, NORM_FROZEN>), dim3(pl.n_tiles), dim3(256), lds, s, x, w_dw, w_pw, z, no_part, d, pl.P, fz); break;
+    switch (NT) { FWD_CASE(4) FWD_CASE(8) FWD_CASE(16) FWD_CASE(32) }
+#undef FWD_CASE
+    TNET_LAUNCH_CHECK("dwpw frozen fwd")
+    return GHN3_OK;
+}
+
+extern "C" int ghn3_dwpw_frozen_bwd(const ghn3_dwpw_desc* g, const float* dout, const float* x, const float* z, const float* w_dw,
+                                    const float* w_pw, const float* gamma, const float* mean, const float* var, float* dx, float* dw_dw,
+                                    float* dw_pw, float* dgamma, float* dbeta, float* scratch, void* stream_) {
+    Desc d;
+    int rc = check_desc(g, d);
+    if (rc) return rc;
+    if (!dout || !x || !z || !w_pw || !gamma || !mean || !var || !dx || !dw_pw || !dgamma || !dbeta || !scratch || (w_dw && !dw_dw)) {
+        ghn3_set_error("dwpw frozen bwd: null pointer");
+        return GHN3_E_ARG;
+    }
+    if (!w_dw && (d.ks != 1 || d.pad != 0)) { ghn3_set_error("dwpw: without depthwise weights ks = 1, pad = 0"); return GHN3_E_ARG; }
+    hipStream_t s = (hipStream_t)stream_;
+    const Plan pl = make_plan(d);
+    float* part12 = scratch;
+    float* const s12_scratch = part12 + (int64_t)pl.n_tiles * 2 * d.C_out;
+    float* stats = s12_scratch + 2 * d.C_out;
+    float* dy = stats + 2 * d.C_out;
+    float* part_pw = dy + (int64_t)pl.P * d.C_in;
+    float* part_dw = part_pw + (int64_t)pl.pw_chunks * d.C_out * d.C_in;
+    hipLaunchKernelGGL(tnet_bn_frozen_stats_kernel, dim3((d.C_out + 255) / 256), dim3(256), 0, s, mean, var, d.eps, d.C_out, stats);
+    TNET_LAUNCH_CHECK("bn frozen stats")
+    // 1. dgamma / dbeta
+    const float* s12;
+    rc = bn_param_grads(dout, z, stats, part12, s12_scratch, dgamma, dbeta, pl.n_tiles, pl.P, d.C_out, s, &s12);
+    if (rc) return rc;
+    return dwpw_bwd_products<NORM_FROZEN>(d, pl, dout, nullptr, stats, gamma, nullptr, x, w_dw, w_pw, dx, dw_dw, dw_pw, dy, part_pw,
+                                          part_dw, s);
 }
 
 // ---- dense convolution family: the forward / input-gradient kernel and the host side -------------------------------------------
@@ -940,6 +1081,8 @@ namespace {
 //    barrier per chunk), the A pieces are stored as 16-byte vectors;
 //  * the backward reads dz from a buffer written once (tnet_dz_kernel).
 // BWD = false: dst = z[P_dst = output pixels][R = C_out] from src = x;  BWD = true: dst = dx[input pixels][R = C_in] from src = dz.
+// FROZEN (forward only): the norm layer behind the convolution has frozen statistics: its affine map is applied to the
+// accumulators and stored to fz.out, dst = z is stored as well when it is non-null, and the kernel ends there (no statistics).
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void tnet_conv_w_pack_kernel(const float* __restrict__ w, unsigned short* __restrict__ wp, int C_out,
                                                                int C_in, int taps, int transposed) {
@@ -963,30 +1106,39 @@ __global__ __launch_bounds__(256) void tnet_conv_w_pack_kernel(const float* __re
     }
 }
 
+// dz [P][C] of a norm layer, written once.  BATCH = false: frozen statistics, dz = gamma rstd dout (z and s12 are not touched).
+template <bool BATCH = true>
 __global__ __launch_bounds__(256) void tnet_dz_kernel(const float* __restrict__ dout, const float* __restrict__ z,
                                                       const float* __restrict__ stats, const float* __restrict__ gamma,
                                                       const float* __restrict__ s12, float* __restrict__ dz, int64_t total4, int C, int P) {
     const float invP = 1.f / (float)P;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (int64_t)gridDim.x * 256) {
         const int c = (int)((i * 4) % C);
-        const f32x4 g = *reinterpret_cast<const f32x4*>(dout + 4 * i), zz = *reinterpret_cast<const f32x4*>(z + 4 * i);
-        const f32x4 mu = *reinterpret_cast<const f32x4*>(stats + c), rs = *reinterpret_cast<const f32x4*>(stats + C + c);
-        const f32x4 ga = *reinterpret_cast<const f32x4*>(gamma + c);
-        const f32x4 a1 = *reinterpret_cast<const f32x4*>(s12 + c), a2 = *reinterpret_cast<const f32x4*>(s12 + C + c);
+        const f32x4 g = *reinterpret_cast<const f32x4*>(dout + 4 * i);
+        const f32x4 rs = *reinterpret_cast<const f32x4*>(stats + C + c), ga = *reinterpret_cast<const f32x4*>(gamma + c);
         f32x4 o;
+        if constexpr (BATCH) {
+            const f32x4 zz = *reinterpret_cast<const f32x4*>(z + 4 * i), mu = *reinterpret_cast<const f32x4*>(stats + c);
+            const f32x4 a1 = *reinterpret_cast<const f32x4*>(s12 + c), a2 = *reinterpret_cast<const f32x4*>(s12 + C + c);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float xh = (zz[e] - mu[e]) * rs[e];
-            o[e] = ga[e] * rs[e] * (g[e] - a1[e] * invP - xh * a2[e] * invP);
+            for (int e = 0; e < 4; ++e) {
+                const float xh = (zz[e] - mu[e]) * rs[e];
+                o[e] = ga[e] * rs[e] * (g[e] - a1[e] * invP - xh * a2[e] * invP);
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = ga[e] * rs[e] * g[e];
         }
         *reinterpret_cast<f32x4*>(dz + 4 * i) = o;
     }
 }
 
-template <int NT, bool BWD>
+template <int NT, bool BWD, bool FROZEN = false>
 __global__ __launch_bounds__(256) void tnet_conv2_kernel(const float* __restrict__ src, const unsigned short* __restrict__ wp,
                                                          float* __restrict__ dst, float* __restrict__ part,
-                                                         const float* __restrict__ xmask, const CDesc d, const int P_dst, const int P_src) {
+                                                         const float* __restrict__ xmask, const CDesc d, const int P_dst, const int P_src,
+                                                         const Frozen fz) {
+    static_assert(!(BWD && FROZEN), "the frozen norm layer is an epilogue of the forward");
     constexpr int S = 3;
     constexpr int A_BUF = S * TP * LDK, B_BUF = S * 16 * NT * LDK;             // 16-bit elements per stage
     constexpr int NB = (S * 16 * NT * 4 + 255) / 256;                          // 16-byte units of the B tile per thread
@@ -1110,6 +1262,17 @@ __global__ __launch_bounds__(256) void tnet_conv2_kernel(const float* __restrict
     }
     const int prow = p0 + 16 * w + r16;
     const bool valid = prow < P_dst;
+    if constexpr (FROZEN) {
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            const int col = col0 + 16 * j + 4 * kc;
+            if (valid && col < R) {
+                if (dst) *reinterpret_cast<f32x4*>(dst + (int64_t)prow * R + col) = acc[j];
+                *reinterpret_cast<f32x4*>(fz.out + (int64_t)prow * R + col) = frozen_affine4(acc[j], fz, col, d.eps);
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
         const int col = col0 + 16 * j + 4 * kc;
@@ -1230,6 +1393,37 @@ CScratch conv_scratch(const CDesc& d, const CPlan& pl, bool backward) {
     return sc;
 }
 
+// Steps 3 and 4 of the backward, shared by every member of the family: dx by the transposed implicit GEMM and dW, both from a
+// plain dz [P][C_out] buffer.
+int conv_bwd_products(const CDesc& d, const CPlan& pl, const CScratch& sc, const float* dz, const float* x, const float* w, float* dx,
+                      float* dw, float* scratch, hipStream_t s) {
+    int rc;
+    const int64_t wr = (int64_t)pl.taps * d.C_out * d.C_in;
+    // 3. dx
+    unsigned short* wp = reinterpret_cast<unsigned short*>(scratch + sc.wp);
+    const int64_t plane = (int64_t)pl.taps * d.C_in * ((d.C_out + KC - 1) / KC * KC);
+    hipLaunchKernelGGL(tnet_conv_w_pack_kernel, dim3((int)std::min<int64_t>((plane + 255) / 256, 2048)), dim3(256), 0, s, w, wp, d.C_out,
+                       d.C_in, pl.taps, 1);
+    TNET_LAUNCH_CHECK("conv weight pack (transposed)")
+    const int NT = conv2_nt(pl.n_tiles_in, d.C_in);
+    const dim3 grid(pl.n_tiles_in, (d.C_in + 16 * NT - 1) / (16 * NT));
+    const size_t lds = conv2_lds(NT);
+#define C2B_CASE(n) case n: rc = tnet_raise_lds(tnet_conv2_kernel<n, true>, lds); if (rc) return rc; \
+    hipLaunchKernelGGL((tnet_conv2_kernel<n, true>), grid, dim3(256), lds, s, dz, wp, dx, (float*)nullptr, x, d, pl.P_in, pl.P, Frozen{}); break;
+    switch (NT) { C2B_CASE(2) C2B_CASE(4) C2B_CASE(8) }
+#undef C2B_CASE
+    TNET_LAUNCH_CHECK("conv bwd data")
+    // 4. dW (in the parameter's own [C_out][C_in][kh][kw] order)
+    float* part_w = scratch + sc.part_w;
+    hipLaunchKernelGGL(tnet_conv_wgrad_kernel, dim3(pl.w_chunks, (d.C_out + 63) / 64, ((d.C_in + 63) / 64) * pl.taps), dim3(256), 0, s, dz, x,
+                       part_w, d, pl.P, pl.w_chunk_px);
+    TNET_LAUNCH_CHECK("conv wgrad")
+    hipLaunchKernelGGL(tnet_reduce_rows_kernel, dim3((int)((wr / 4 + 15) / 16)), dim3(256), 0, s, part_w, pl.w_chunks, wr, dw,
+                       d.C_out * d.C_in, pl.taps);
+    TNET_LAUNCH_CHECK("conv wgrad reduce")
+    return GHN3_OK;
+}
+
 }  // namespace
 
 extern "C" int64_t ghn3_conv_scratch_floats(const ghn3_conv_desc* g, int backward) {
@@ -1261,7 +1455,7 @@ extern "C" int ghn3_conv_bn_fwd(const ghn3_conv_desc* g, const float* x, const f
     const dim3 grid(pl.n_tiles, (d.C_out + 16 * NT - 1) / (16 * NT));
     const size_t lds = conv2_lds(NT);
 #define C2F_CASE(n) case n: rc = tnet_raise_lds(tnet_conv2_kernel<n, false>, lds); if (rc) return rc; \
-    hipLaunchKernelGGL((tnet_conv2_kernel<n, false>), grid, dim3(256), lds, s, x, wp, z, part, (const float*)nullptr, d, pl.P, pl.P_in); break;
+    hipLaunchKernelGGL((tnet_conv2_kernel<n, false>), grid, dim3(256), lds, s, x, wp, z, part, (const float*)nullptr, d, pl.P, pl.P_in, Frozen{}); break;
     switch (NT) { C2F_CASE(2) C2F_CASE(4) C2F_CASE(8) }
 #undef C2F_CASE
     TNET_LAUNCH_CHECK("conv fwd")
@@ -1289,55 +1483,88 @@ extern "C" int ghn3_conv_bn_bwd(const ghn3_conv_desc* g, const float* dout, cons
     hipStream_t s = (hipStream_t)stream_;
     const CPlan pl = make_cplan(d);
     const CScratch sc = conv_scratch(d, pl, true);
-    const int64_t wr = (int64_t)pl.taps * d.C_out * d.C_in;
     const float* dz = dout;
     if (!no_norm) {
         // 1. dgamma / dbeta
-        float* part12 = scratch + sc.part;
-        // (dbeta directly followed by dgamma -- how target_ops.py lays them out -- IS the [sum dout | sum dout xhat] pair: no copies)
-        const bool s12_in_place = dgamma == dbeta + d.C_out;
-        float* s12 = s12_in_place ? dbeta : scratch + sc.s12;
-        const int nq = d.C_out / 4, ng = std::max(1, 256 / nq);
-        hipLaunchKernelGGL(tnet_bn_bwd_partial_kernel, dim3(pl.n_tiles), dim3(256), (size_t)ng * 2 * d.C_out * 4, s, dout, z, stats, part12,
-                           pl.P, d.C_out);
-        TNET_LAUNCH_CHECK("bn bwd partial")
-        hipLaunchKernelGGL(tnet_reduce_rows_kernel, dim3((2 * d.C_out / 4 + 15) / 16), dim3(256), 0, s, part12, pl.n_tiles,
-                           (int64_t)2 * d.C_out, s12, 0, 0);
-        TNET_LAUNCH_CHECK("bn bwd reduce")
-        if (!s12_in_place) {
-            hipMemcpyAsync(dbeta, s12, (size_t)d.C_out * 4, hipMemcpyDeviceToDevice, s);
-            hipMemcpyAsync(dgamma, s12 + d.C_out, (size_t)d.C_out * 4, hipMemcpyDeviceToDevice, s);
-        }
+        const float* s12;
+        rc = bn_param_grads(dout, z, stats, scratch + sc.part, scratch + sc.s12, dgamma, dbeta, pl.n_tiles, pl.P, d.C_out, s, &s12);
+        if (rc) return rc;
         // 2. dz [P][C_out], written once for the two kernels that read it
         const int64_t total4 = (int64_t)pl.P * d.C_out / 4;
-        hipLaunchKernelGGL(tnet_dz_kernel, dim3((int)std::min<int64_t>((total4 + 255) / 256, 4096)), dim3(256), 0, s, dout, z, stats, gamma,
-                           s12, scratch + sc.dz, total4, d.C_out, pl.P);
+        hipLaunchKernelGGL(tnet_dz_kernel<true>, dim3((int)std::min<int64_t>((total4 + 255) / 256, 4096)), dim3(256), 0, s, dout, z, stats,
+                           gamma, s12, scratch + sc.dz, total4, d.C_out, pl.P);
         TNET_LAUNCH_CHECK("conv bwd dz")
         dz = scratch + sc.dz;
     }
-    // 3. dx
-    unsigned short* wp = reinterpret_cast<unsigned short*>(scratch + sc.wp);
-    const int64_t plane = (int64_t)pl.taps * d.C_in * ((d.C_out + KC - 1) / KC * KC);
+    return conv_bwd_products(d, pl, sc, dz, x, w, dx, dw, scratch, s);
+}
+
+// ---- the same family behind a norm layer with FROZEN statistics (a BatchNorm in eval mode; see ghn3_dwpw_frozen_fwd) ------------
+// Forward: weight pack + the convolution kernel with the affine map in its epilogue (FROZEN), z stored beside out only when the
+// caller wants a backward.  Backward: (mean, var) -> (mean, rstd), dgamma / dbeta as with batch statistics, dz = dout gamma rstd
+// written once (tnet_dz_kernel<false>: the two kernels that read it take a plain buffer), then dx and dW unchanged.
+// Scratch: forward = the weight pack; backward = that of ghn3_conv_bn_bwd followed by the (mean, rstd) pair.
+extern "C" int64_t ghn3_conv_frozen_scratch_floats(const ghn3_conv_desc* g, int backward) {
+    CDesc d;
+    if (check_cdesc(g, d)) return -1;
+    const CPlan pl = make_cplan(d);
+    if (!backward) return pack_floats(pl.taps, d.C_out, d.C_in) + 64;
+    return conv_scratch(d, pl, true).total + 2 * d.C_out;
+}
+
+extern "C" int ghn3_conv_frozen_fwd(const ghn3_conv_desc* g, const float* x, const float* w, const float* gamma, const float* beta,
+                                    const float* mean, const float* var, float* z, float* out, float* scratch, void* stream_) {
+    CDesc d;
+    int rc = check_cdesc(g, d);
+    if (rc) return rc;
+    if (g->relu & GHN3_CONV_NO_NORM) { ghn3_set_error("conv frozen: GHN3_CONV_NO_NORM has no meaning here"); return GHN3_E_ARG; }
+    if (!x || !w || !gamma || !beta || !mean || !var || !out || !scratch) { ghn3_set_error("conv frozen fwd: null pointer"); return GHN3_E_ARG; }
+    hipStream_t s = (hipStream_t)stream_;
+    const CPlan pl = make_cplan(d);
+    unsigned short* wp = reinterpret_cast<unsigned short*>(scratch);
+    const int64_t plane = (int64_t)pl.taps * d.C_out * ((d.C_in + KC - 1) / KC * KC);
     hipLaunchKernelGGL(tnet_conv_w_pack_kernel, dim3((int)std::min<int64_t>((plane + 255) / 256, 2048)), dim3(256), 0, s, w, wp, d.C_out,
-                       d.C_in, pl.taps, 1);
-    TNET_LAUNCH_CHECK("conv weight pack (transposed)")
-    const int NT = conv2_nt(pl.n_tiles_in, d.C_in);
-    const dim3 grid(pl.n_tiles_in, (d.C_in + 16 * NT - 1) / (16 * NT));
+                       d.C_in, pl.taps, 0);
+    TNET_LAUNCH_CHECK("conv weight pack")
+    const int NT = conv2_nt(pl.n_tiles, d.C_out);
+    const dim3 grid(pl.n_tiles, (d.C_out + 16 * NT - 1) / (16 * NT));
     const size_t lds = conv2_lds(NT);
-#define C2B_CASE(n) case n: rc = tnet_raise_lds(tnet_conv2_kernel<n, true>, lds); if (rc) return rc; \
-    hipLaunchKernelGGL((tnet_conv2_kernel<n, true>), grid, dim3(256), lds, s, dz, wp, dx, (float*)nullptr, x, d, pl.P_in, pl.P); break;
-    switch (NT) { C2B_CASE(2) C2B_CASE(4) C2B_CASE(8) }
-#undef C2B_CASE
-    TNET_LAUNCH_CHECK("conv bwd data")
-    // 4. dW (in the parameter's own [C_out][C_in][kh][kw] order)
-    float* part_w = scratch + sc.part_w;
-    hipLaunchKernelGGL(tnet_conv_wgrad_kernel, dim3(pl.w_chunks, (d.C_out + 63) / 64, ((d.C_in + 63) / 64) * pl.taps), dim3(256), 0, s, dz, x,
-                       part_w, d, pl.P, pl.w_chunk_px);
-    TNET_LAUNCH_CHECK("conv wgrad")
-    hipLaunchKernelGGL(tnet_reduce_rows_kernel, dim3((int)((wr / 4 + 15) / 16)), dim3(256), 0, s, part_w, pl.w_chunks, wr, dw,
-                       d.C_out * d.C_in, pl.taps);
-    TNET_LAUNCH_CHECK("conv wgrad reduce")
+    const Frozen fz = {gamma, beta, mean, var, out};
+#define C2F_CASE(n) case n: rc = tnet_raise_lds(tnet_conv2_kernel<n, false, true>, lds); if (rc) return rc; \
+    hipLaunchKernelGGL((tnet_conv2_kernel<n, false, true>), grid, dim3(256), lds, s, x, wp, z, (float*)nullptr, (const float*)nullptr, d, pl.P, pl.P_in, fz); break;
+    switch (NT) { C2F_CASE(2) C2F_CASE(4) C2F_CASE(8) }
+#undef C2F_CASE
+    TNET_LAUNCH_CHECK("conv frozen fwd")
     return GHN3_OK;
+}
+
+extern "C" int ghn3_conv_frozen_bwd(const ghn3_conv_desc* g, const float* dout, const float* x, const float* z, const float* w,
+                                    const float* gamma, const float* mean, const float* var, float* dx, float* dw, float* dgamma,
+                                    float* dbeta, float* scratch, void* stream_) {
+    CDesc d;
+    int rc = check_cdesc(g, d);
+    if (rc) return rc;
+    if (g->relu & GHN3_CONV_NO_NORM) { ghn3_set_error("conv frozen: GHN3_CONV_NO_NORM has no meaning here"); return GHN3_E_ARG; }
+    if (!dout || !x || !z || !w || !gamma || !mean || !var || !dx || !dw || !dgamma || !dbeta || !scratch) {
+        ghn3_set_error("conv frozen bwd: null pointer");
+        return GHN3_E_ARG;
+    }
+    hipStream_t s = (hipStream_t)stream_;
+    const CPlan pl = make_cplan(d);
+    const CScratch sc = conv_scratch(d, pl, true);
+    float* stats = scratch + sc.total;
+    hipLaunchKernelGGL(tnet_bn_frozen_stats_kernel, dim3((d.C_out + 255) / 256), dim3(256), 0, s, mean, var, d.eps, d.C_out, stats);
+    TNET_LAUNCH_CHECK("bn frozen stats")
+    // 1. dgamma / dbeta
+    const float* s12;
+    rc = bn_param_grads(dout, z, stats, scratch + sc.part, scratch + sc.s12, dgamma, dbeta, pl.n_tiles, pl.P, d.C_out, s, &s12);
+    if (rc) return rc;
+    // 2. dz [P][C_out] = dout gamma rstd
+    const int64_t total4 = (int64_t)pl.P * d.C_out / 4;
+    hipLaunchKernelGGL(tnet_dz_kernel<false>, dim3((int)std::min<int64_t>((total4 + 255) / 256, 4096)), dim3(256), 0, s, dout,
+                       (const float*)nullptr, stats, gamma, (const float*)nullptr, scratch + sc.dz, total4, d.C_out, pl.P);
+    TNET_LAUNCH_CHECK("conv frozen bwd dz")
+    return conv_bwd_products(d, pl, sc, scratch + sc.dz, x, w, dx, dw, scratch, s);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

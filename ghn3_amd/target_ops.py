@@ -17,6 +17,12 @@ A network built with norm=None has an Identity in every norm slot (`bn_layer`, o
 the families without a norm layer -- ``DwPw`` / ``dwpw`` (ghn3_dwpw_plain_fwd / _bwd) and ``ConvOnly`` / ``conv_only`` --, routed
 by the same runners (``_no_norm``; GHN3_NATIVE_NONORM=0 keeps such blocks on the stock layers).
 
+A BatchNorm that carries running statistics and is not in training mode (``net.eval()`` on a network built with the default
+norm='bn-track') is a per-channel affine map with constants known before the launch: its blocks run on ``DwPwBnEval`` /
+``dwpw_bn_eval`` (ghn3_dwpw_frozen_fwd / _bwd) and ``ConvBnEval`` / ``conv_bn_eval`` (ghn3_conv_frozen_fwd / _bwd), routed by the
+same runners (``_frozen_norm``; GHN3_NATIVE_EVALBN=0 keeps such blocks on the stock layers).  The running statistics are read
+only: they take no gradient and are never written.
+
 ``DwPwBn.applicable`` states what the kernels take (fp32 CUDA tensors, batch statistics, C <= 512, ks <= 7); a layer
 outside of it keeps the stock path.  There is no CPU implementation: on a CPU tensor the stock path runs (the target
 networks themselves are torch modules), and ``dwpw_bn`` raises without the library.
@@ -114,6 +120,25 @@ def _no_norm(bn):
     the block then runs on the no-norm members of the op families (DwPw, ConvOnly).  GHN3_NATIVE_NONORM=0 keeps such blocks on
     the stock layers (the behaviour before these members existed; A/B measurements)."""
     return _is_kind(bn, 'Identity') and os.environ.get('GHN3_NATIVE_NONORM', '1') != '0'
+
+
+def _frozen_norm(batch_stats):
+    """True for a norm layer that normalises with its running statistics in this call (`_norm_inputs`' batch_stats is False:
+    the layer carries them and is not in training mode): the block then runs on the frozen-statistics members of the op families
+    (DwPwBnEval, ConvBnEval).  GHN3_NATIVE_EVALBN=0 keeps such blocks on the stock layers (the behaviour before these members
+    existed; A/B measurements)."""
+    return not batch_stats and os.environ.get('GHN3_NATIVE_EVALBN', '1') != '0'
+
+
+def _frozen_stats_ok(running_mean, running_var, C_out):
+    return all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.numel() == C_out
+               for t in (running_mean, running_var))
+
+
+def _wants_grad(*tensors):
+    """Whether a node's backward can ever run: grad mode is on and some input requires a gradient (asked BEFORE Function.apply,
+    which switches grad mode off for its forward)."""
+    return torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in tensors)
 
 
 class DwPwBn(torch.autograd.Function):
@@ -249,6 +274,73 @@ def dwpw(x, w_dw, w_pw, stride=1, padding=0, dilation=1):
     return DwPw.apply(x, w_dw, w_pw.reshape(w_pw.shape[0], -1), int(stride), int(padding), int(dilation))
 
 
+class DwPwBnEval(torch.autograd.Function):
+    """ReLU -> depthwise k x k convolution -> pointwise 1 x 1 convolution -> BatchNorm with RUNNING statistics (eval mode) as ONE
+    autograd node on ghn3_dwpw_frozen_fwd / _bwd.  Same conventions as DwPwBn.  One launch forward: the norm is applied to the
+    product's accumulators; the pre-norm tensor z is allocated, written and saved only when `keep_z` (a backward can follow),
+    which does not change the arithmetic of the output.  The statistics are constants: no gradient, never written."""
+
+    @staticmethod
+    def applicable(x, w_dw, w_pw, gamma, beta, running_mean, running_var, ks):
+        return DwPwBn.applicable(x, w_dw, w_pw, gamma, beta, ks) and gamma.numel() == w_pw.shape[0] and \
+            beta.numel() == w_pw.shape[0] and _frozen_stats_ok(running_mean, running_var, w_pw.shape[0])
+
+    @staticmethod
+    def forward(ctx, x, w_dw, w_pw, gamma, beta, running_mean, running_var, stride, pad, dil, eps, keep_z):
+        lib = L.load()
+        ks = 1 if w_dw is None else int(w_dw.shape[-1])
+        C_out = int(w_pw.shape[0])
+        xc = x.contiguous(memory_format=torch.channels_last)
+        d = _desc(xc, C_out, ks, stride, pad, dil, eps)
+        wd, wp = (None if w_dw is None else w_dw.contiguous()), w_pw.contiguous()
+        g, b, rm, rv = gamma.contiguous(), beta.contiguous(), running_mean.contiguous(), running_var.contiguous()
+        out = torch.empty((d.N, C_out, d.Ho, d.Wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+        z = torch.empty_like(out) if keep_z else None
+        L._check(lib.ghn3_dwpw_frozen_fwd(ctypes.byref(d), _ptr(xc), _ptr(wd) if wd is not None else None, _ptr(wp), _ptr(g), _ptr(b),
+                                          _ptr(rm), _ptr(rv), _ptr(z) if keep_z else None, _ptr(out), _stream()),
+                 'ghn3_dwpw_frozen_fwd')
+        if keep_z:
+            ctx.has_dw = wd is not None
+            ctx.save_for_backward(xc, z, wd if wd is not None else wp, wp, g, rm, rv)
+            ctx.cfg = (stride, pad, dil, eps)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = L.load()
+        xc, z, wd, wp, g, rm, rv = ctx.saved_tensors
+        if not ctx.has_dw:
+            wd = None
+        stride, pad, dil, eps = ctx.cfg
+        C_out, ks = int(wp.shape[0]), (1 if wd is None else int(wd.shape[-1]))
+        d = _desc(xc, C_out, ks, stride, pad, dil, eps)
+        do = dout.contiguous(memory_format=torch.channels_last)
+        dx = torch.empty_like(xc)
+        # (one allocation for the four parameter gradients and the scratch area, as DwPwBn)
+        n_wd = 0 if wd is None else wd.numel()
+        n_par = n_wd + wp.numel() + 2 * C_out
+        buf = torch.empty(n_par + 64 + _scratch_floats('ghn3_dwpw_frozen_scratch_floats', d, 1), dtype=torch.float32, device=xc.device)
+        dwd = None if wd is None else buf[:n_wd].view(wd.shape)
+        dwp = buf[n_wd:n_wd + wp.numel()].view(wp.shape)
+        db = buf[n_par - 2 * C_out:n_par - C_out]            # (dbeta directly followed by dgamma: the kernels' own pair of sums)
+        dg = buf[n_par - C_out:n_par]
+        scratch = buf[(n_par + 63) // 64 * 64:]
+        L._check(lib.ghn3_dwpw_frozen_bwd(ctypes.byref(d), _ptr(do), _ptr(xc), _ptr(z), _ptr(wd) if wd is not None else None, _ptr(wp),
+                                          _ptr(g), _ptr(rm), _ptr(rv), _ptr(dx), _ptr(dwd) if dwd is not None else None, _ptr(dwp),
+                                          _ptr(dg), _ptr(db), _ptr(scratch), _stream()), 'ghn3_dwpw_frozen_bwd')
+        return dx, dwd, dwp, dg, db, None, None, None, None, None, None, None
+
+
+def dwpw_bn_eval(x, w_dw, w_pw, gamma, beta, running_mean, running_var, stride=1, padding=0, dilation=1, eps=1e-5):
+    """out = batch_norm(conv1x1(depthwise_conv(relu(x)))) with the given running statistics (a BatchNorm in eval mode); w_dw None:
+    no depthwise stage.  Tensors as for dwpw_bn, running_mean / running_var (C_out) fp32.  Under torch.no_grad(), or when no
+    input requires a gradient, nothing is saved and only the output is written."""
+    if not x.is_cuda:
+        raise L.Ghn3Error('dwpw_bn_eval runs on an MI355X only (no CPU implementation: use the stock torch layers)')
+    return DwPwBnEval.apply(x, w_dw, w_pw.reshape(w_pw.shape[0], -1), gamma, beta, running_mean, running_var, int(stride),
+                            int(padding), int(dilation), float(eps), _wants_grad(x, w_dw, w_pw, gamma, beta))
+
+
 class _ConvDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ('N', 'H', 'W', 'C_in', 'C_out', 'kh', 'kw', 'stride_h', 'stride_w', 'pad_h', 'pad_w',
                                               'dil', 'Ho', 'Wo', 'relu')] + [('eps', ctypes.c_float)]
@@ -283,6 +375,13 @@ def _conv_desc(x, w, stride, pad, dil, relu, eps, no_norm=False):
     Wo = (W + 2 * pw - dil * (kw - 1) - 1) // sw + 1
     return _ConvDesc(N, H, W, C, C_out, kh, kw, sh, sw, ph, pw, int(dil), Ho, Wo,
                      int(bool(relu)) | (CONV_NO_NORM if no_norm else 0), float(eps))
+
+
+def conv_desc_fits(d):
+    """The two 2^31 rules of the C side (check_cdesc: input pixels and output pixels, each times the wider channel count) on a
+    _ConvDesc: a refusal there would come as an error in the middle of a network, not as a return to the stock layers."""
+    widest = max(d.C_in, d.C_out)
+    return d.Ho > 0 and d.Wo > 0 and d.N * d.H * d.W * widest < 2 ** 31 and d.N * d.Ho * d.Wo * widest < 2 ** 31
 
 
 class ConvBn(torch.autograd.Function):
@@ -374,6 +473,66 @@ class ConvOnly(torch.autograd.Function):
         L._check(lib.ghn3_conv_bn_bwd(ctypes.byref(d), _ptr(do), _ptr(xc), None, None, _ptr(wc), None, _ptr(dx), _ptr(dw), None,
                                       None, _ptr(buf[n_par:]), stream), 'ghn3_conv_bn_bwd')
         return dx, dw, None, None, None, None
+
+
+class ConvBnEval(torch.autograd.Function):
+    """[ReLU ->] dense kh x kw convolution -> BatchNorm with RUNNING statistics (eval mode) as ONE autograd node on
+    ghn3_conv_frozen_fwd / _bwd.  Same conventions as ConvBn; z and `keep_z` as for DwPwBnEval."""
+
+    @staticmethod
+    def applicable(x, w, gamma, beta, running_mean, running_var, stride=1, padding=0, dilation=1):
+        if not (ConvBn.applicable(x, w, gamma, beta) and beta.numel() == w.shape[0] and
+                _frozen_stats_ok(running_mean, running_var, w.shape[0])):
+            return False
+        return conv_desc_fits(_conv_desc(x, w, stride, padding, dilation, False, 0.0))
+
+    @staticmethod
+    def forward(ctx, x, w, gamma, beta, running_mean, running_var, stride, pad, dil, relu, eps, keep_z):
+        lib = L.load()
+        xc = x.contiguous(memory_format=torch.channels_last)
+        wc, g, b = w.contiguous(), gamma.contiguous(), beta.contiguous()
+        rm, rv = running_mean.contiguous(), running_var.contiguous()
+        d = _conv_desc(xc, wc, stride, pad, dil, relu, eps)
+        dev, C_out = x.device, int(wc.shape[0])
+        out = torch.empty((d.N, C_out, d.Ho, d.Wo), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
+        z = torch.empty_like(out) if keep_z else None
+        scratch = torch.empty(_scratch_floats('ghn3_conv_frozen_scratch_floats', d, 0), dtype=torch.float32, device=dev)
+        L._check(lib.ghn3_conv_frozen_fwd(ctypes.byref(d), _ptr(xc), _ptr(wc), _ptr(g), _ptr(b), _ptr(rm), _ptr(rv),
+                                          _ptr(z) if keep_z else None, _ptr(out), _ptr(scratch), _stream()), 'ghn3_conv_frozen_fwd')
+        if keep_z:
+            ctx.save_for_backward(xc, z, wc, g, rm, rv)
+            ctx.cfg = (stride, pad, dil, relu, eps)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = L.load()
+        xc, z, wc, g, rm, rv = ctx.saved_tensors
+        stride, pad, dil, relu, eps = ctx.cfg
+        d = _conv_desc(xc, wc, stride, pad, dil, relu, eps)
+        dev, C_out = xc.device, int(wc.shape[0])
+        do = dout.contiguous(memory_format=torch.channels_last)
+        dx = torch.empty_like(xc)
+        n_par = wc.numel() + 2 * C_out
+        buf = torch.empty((n_par + 63) // 64 * 64 + _scratch_floats('ghn3_conv_frozen_scratch_floats', d, 1), dtype=torch.float32,
+                          device=dev)
+        dw = buf[:wc.numel()].view(wc.shape)
+        db = buf[wc.numel():wc.numel() + C_out]              # (dbeta directly followed by dgamma: the kernels' own pair of sums)
+        dg = buf[wc.numel() + C_out:n_par]
+        scratch = buf[(n_par + 63) // 64 * 64:]
+        L._check(lib.ghn3_conv_frozen_bwd(ctypes.byref(d), _ptr(do), _ptr(xc), _ptr(z), _ptr(wc), _ptr(g), _ptr(rm), _ptr(rv), _ptr(dx),
+                                          _ptr(dw), _ptr(dg), _ptr(db), _ptr(scratch), _stream()), 'ghn3_conv_frozen_bwd')
+        return dx, dw, dg, db, None, None, None, None, None, None, None, None
+
+
+def conv_bn_eval(x, w, gamma, beta, running_mean, running_var, stride=1, padding=0, dilation=1, relu=True, eps=1e-5):
+    """out = batch_norm(conv2d(relu(x) if relu else x, w)) with the given running statistics (a BatchNorm in eval mode).  Tensors
+    as for conv_bn, running_mean / running_var (C_out) fp32.  Under torch.no_grad(), or when no input requires a gradient, nothing
+    is saved and only the output is written."""
+    if not x.is_cuda:
+        raise L.Ghn3Error('conv_bn_eval runs on an MI355X only (no CPU implementation: use the stock torch layers)')
+    return ConvBnEval.apply(x, w, gamma, beta, running_mean, running_var, _pair(stride), _pair(padding), int(dilation), bool(relu),
+                            float(eps), _wants_grad(x, w, gamma, beta))
 
 
 def conv_only(x, w, stride=1, padding=0, dilation=1, relu=False):
@@ -524,6 +683,13 @@ def run_conv_block(layers, x, keep_layout=False):
     if _no_norm(bn) and _plain_conv(conv) and ConvOnly.applicable(x, w):
         out = conv_only(x, w, conv.stride, conv.padding, _pair(conv.dilation)[0], relu=True)
         return _hand_on(out, keep_layout, conv, bn)
+    if _frozen_norm(batch_stats) and hasattr(bn, 'eps') and _plain_conv(conv) and \
+            ConvBnEval.applicable(x, w, gamma, beta, bn.running_mean, bn.running_var, conv.stride, conv.padding,
+                                  _pair(conv.dilation)[0]):
+        # (running statistics in eval mode: the family's member with a frozen norm; the statistics are not touched)
+        out = conv_bn_eval(x, w, gamma, beta, bn.running_mean, bn.running_var, conv.stride, conv.padding,
+                           _pair(conv.dilation)[0], True, bn.eps)
+        return _hand_on(out, keep_layout, conv, bn)
     ok = hasattr(bn, 'eps') and _plain_conv(conv) and ConvBn.applicable(x, w, gamma, beta, batch_stats)
     if not ok:
         for m in layers:
@@ -557,6 +723,18 @@ def run_conv_pair_block(layers, x, keep_layout=False):
             return _hand_on(out, keep_layout, conv_a, conv_b, bn)
     ok = hasattr(bn, 'eps') and _plain_conv(conv_a) and _plain_conv(conv_b) and ConvOnly.applicable(x, conv_a.weight) and \
         conv_b.weight.shape[1] == conv_a.weight.shape[0]
+    if ok and _frozen_norm(batch_stats):
+        # (running statistics in eval mode: ConvOnly, then the second convolution with the frozen norm.  The second node's input
+        # has conv_a's channel count, x's type and the first convolution's output size: checked on a stand-in of that shape)
+        da = _conv_desc(x, conv_a.weight, conv_a.stride, conv_a.padding, _pair(conv_a.dilation)[0], True, 0.0)
+        if conv_desc_fits(da):
+            probe = x.new_empty(1).expand(da.N, da.C_out, da.Ho, da.Wo)        # (one element, no storage of that size)
+            if ConvBnEval.applicable(probe, conv_b.weight, gamma, beta, bn.running_mean, bn.running_var, conv_b.stride,
+                                     conv_b.padding, _pair(conv_b.dilation)[0]):
+                y = conv_only(x, conv_a.weight, conv_a.stride, conv_a.padding, _pair(conv_a.dilation)[0], relu=True)
+                out = conv_bn_eval(y, conv_b.weight, gamma, beta, bn.running_mean, bn.running_var, conv_b.stride, conv_b.padding,
+                                   _pair(conv_b.dilation)[0], False, bn.eps)
+                return _hand_on(out, keep_layout, conv_a, conv_b, bn)
     if ok:
         # (the second node's input has conv_a's channel count and x's type: checked on a stand-in of that shape)
         probe = x if conv_a.weight.shape[0] == x.shape[1] else x.new_empty((1, conv_a.weight.shape[0], 1, 1))
@@ -624,7 +802,20 @@ def run_layer_seq(seq, x):
             if x.shape[1] == 3 and w.shape[1] == 3:
                 xin = F.pad(x, (0, 0, 0, 0, 0, 1))
                 w = F.pad(w, (0, 0, 0, 0, 0, 1))
-            if ConvBn.applicable(xin, w, gamma, beta, batch_stats):
+            frozen = _frozen_norm(batch_stats) and ConvBnEval.applicable(xin, w, gamma, beta, bn.running_mean, bn.running_var,
+                                                                         conv.stride, conv.padding, _pair(conv.dilation)[0])
+            if frozen:
+                # (running statistics in eval mode: the same windows on the member with a frozen norm, the same rules for the
+                # padded image and an in-place ReLU at the head)
+                fold = bool(relu)
+                if relu and k == 0 and getattr(m, 'inplace', False):
+                    xin, fold = m(xin), False
+                x = conv_bn_eval(xin, w, gamma, beta, bn.running_mean, bn.running_var, conv.stride, conv.padding,
+                                 _pair(conv.dilation)[0], fold, bn.eps)
+                x = _hand_on(x, False, conv, bn)
+                k += 3 if relu else 2
+                done = True
+            elif ConvBn.applicable(xin, w, gamma, beta, batch_stats):
                 fold = bool(relu)
                 if relu and k == 0 and getattr(m, 'inplace', False):
                     # an in-place ReLU at the head of the sequence rewrites the CALLER's tensor (stem1 of the two-stem networks:
@@ -663,6 +854,10 @@ def run_factorized_reduce(relu, conv_1, conv_2, bn, x, stride=2, keep_layout=Fal
         if not ConvOnly.applicable(x, w):
             return None
         return _hand_on(conv_only(x, w, 2, 0, 1, relu=True), keep_layout, conv_1, conv_2, bn)
+    if _frozen_norm(batch_stats) and ConvBnEval.applicable(x, w, gamma, beta, bn.running_mean, bn.running_var, 2, 0, 1):
+        # (running statistics in eval mode: the same 2 x 2 convolution with the frozen norm)
+        out = conv_bn_eval(x, w, gamma, beta, bn.running_mean, bn.running_var, 2, 0, 1, True, bn.eps)
+        return _hand_on(out, keep_layout, conv_1, conv_2, bn)
     if not ConvBn.applicable(x, w, gamma, beta, batch_stats):
         return None
     out, stats = conv_bn(x, w, gamma, beta, 2, 0, 1, True, bn.eps)
@@ -691,6 +886,11 @@ def run_pointwise_block(layers, x, keep_layout=False):
         tuple(pw.padding) == (0, 0) and getattr(pw, 'groups', 1) == 1 and torch.is_tensor(w_pw)
     if _no_norm(bn) and layer_ok and DwPw.applicable(x, None, w_pw, 1):
         return _hand_on(dwpw(x, None, w_pw, pw.stride[0], 0, 1), keep_layout, pw, bn)
+    if _frozen_norm(batch_stats) and hasattr(bn, 'eps') and layer_ok and \
+            DwPwBnEval.applicable(x, None, w_pw, gamma, beta, bn.running_mean, bn.running_var, 1):
+        # (running statistics in eval mode: the family's member with a frozen norm; the statistics are not touched)
+        out = dwpw_bn_eval(x, None, w_pw, gamma, beta, bn.running_mean, bn.running_var, pw.stride[0], 0, 1, bn.eps)
+        return _hand_on(out, keep_layout, pw, bn)
     ok = hasattr(bn, 'eps') and layer_ok and DwPwBn.applicable(x, None, w_pw, gamma, beta, 1, batch_stats)
     if not ok:
         # (e.g. more than 512 input channels -- the concatenated states of a wide cell: the dense-convolution op takes those)
@@ -747,6 +947,12 @@ def run_block(layers, x, keep_layout=False):
     if _no_norm(bn) and layers_ok and DwPw.applicable(x, w_dw, w_pw, ks):
         # (norm=None: the family's member without a norm layer)
         return _hand_on(dwpw(x, w_dw, w_pw, dw.stride[0], dw.padding[0], dw.dilation[0]), keep_layout, dw, pw, bn)
+    if _frozen_norm(batch_stats) and hasattr(bn, 'eps') and layers_ok and \
+            DwPwBnEval.applicable(x, w_dw, w_pw, gamma, beta, bn.running_mean, bn.running_var, ks):
+        # (running statistics in eval mode: the family's member with a frozen norm; the statistics are not touched)
+        out = dwpw_bn_eval(x, w_dw, w_pw, gamma, beta, bn.running_mean, bn.running_var, dw.stride[0], dw.padding[0],
+                           dw.dilation[0], bn.eps)
+        return _hand_on(out, keep_layout, dw, pw, bn)
     ok = hasattr(bn, 'eps') and layers_ok and DwPwBn.applicable(x, w_dw, w_pw, gamma, beta, ks, batch_stats)
     if not ok:
         for m in layers:

@@ -553,6 +553,24 @@ int ghn3_dwpw_plain_fwd(const ghn3_dwpw_desc* desc, const float* x, const float*
 int ghn3_dwpw_plain_bwd(const ghn3_dwpw_desc* desc, const float* dout, const float* x, const float* w_dw, const float* w_pw,
                         float* dx, float* dw_dw, float* dw_pw, float* scratch, void* stream);
 
+/* The same family behind a BatchNorm that normalises with its RUNNING statistics (a tracking BatchNorm in eval mode):
+ *   out = (z - mean) rstd gamma + beta,  z = pw(dw(relu(x))),  rstd = 1 / sqrt(var + desc->eps),
+ * mean / var [C_out] fp32, read only: they take no gradient and are never written.  Same descriptor, limits, error codes, NHWC
+ * fp32 conventions and in-place weight views as ghn3_dwpw_bn_fwd / _bwd; added without an ABI version step (symbols only).
+ * Forward: ONE launch -- the affine map is applied to the accumulators in the kernel's epilogue: no statistics, no second pass
+ * over the activations, no scratch.  z != NULL: the pre-affine result is stored as well, for the backward; z == NULL (inference):
+ * nothing of activation size is written but `out`.  The value of `out` does not depend on which.
+ * Backward: dz = dout gamma rstd (no batch-mean terms), formed on the fly as the operand of the two products; dbeta = sum dout,
+ * dgamma = sum dout (z - mean) rstd.  9 launches (6 without a depthwise stage): (mean, var) -> (mean, rstd), two for dgamma /
+ * dbeta, then the six (three) of ghn3_dwpw_plain_bwd.  dgamma == dbeta + C_out saves two small copies.
+ * ghn3_dwpw_frozen_scratch_floats: 0 for the forward.  No allocation, no synchronisation inside.  Deterministic. */
+int64_t ghn3_dwpw_frozen_scratch_floats(const ghn3_dwpw_desc* desc, int backward);
+int ghn3_dwpw_frozen_fwd(const ghn3_dwpw_desc* desc, const float* x, const float* w_dw, const float* w_pw, const float* gamma,
+                         const float* beta, const float* mean, const float* var, float* z, float* out, void* stream);
+int ghn3_dwpw_frozen_bwd(const ghn3_dwpw_desc* desc, const float* dout, const float* x, const float* z, const float* w_dw,
+                         const float* w_pw, const float* gamma, const float* mean, const float* var, float* dx, float* dw_dw,
+                         float* dw_pw, float* dgamma, float* dbeta, float* scratch, void* stream);
+
 
 /* ---- target-network layers, second slice (ABI v19, round 6): [ReLU ->] dense kh x kw convolution -> BatchNorm -------------
  * `ReLUConvBN` with a k x k kernel and its 1 x k / k x 1 halves (/root/reference/ghn3/ops.py:180-198; the `conv_3x3 / 5x5 /
@@ -575,6 +593,21 @@ int ghn3_conv_bn_fwd(const ghn3_conv_desc* desc, const float* x, const float* w,
 int ghn3_conv_bn_bwd(const ghn3_conv_desc* desc, const float* dout, const float* x, const float* z, const float* stats,
                      const float* w, const float* gamma, float* dx, float* dw, float* dgamma, float* dbeta, float* scratch,
                      void* stream);
+
+/* The dense convolution behind a BatchNorm that normalises with its RUNNING statistics (see ghn3_dwpw_frozen_fwd):
+ *   out = (z - mean) rstd gamma + beta,  z = conv(relu(x) if desc->relu else x, w),  rstd = 1 / sqrt(var + desc->eps).
+ * Same descriptor, limits and error codes as ghn3_conv_bn_fwd / _bwd (the two 2^31 rules included); GHN3_CONV_NO_NORM in
+ * desc->relu is GHN3_E_ARG.  Added without an ABI version step (symbols only).  mean / var [C_out] are read only.
+ * Forward: 2 launches (weight pack + the convolution with the affine map in its epilogue); z != NULL: the pre-affine result is
+ * stored as well, for the backward; z == NULL: only `out` is written.  Backward: 8 launches -- (mean, var) -> (mean, rstd), two
+ * for dgamma / dbeta, dz = dout gamma rstd written once, then weight pack, dx, dW and its reduction as ghn3_conv_bn_bwd.
+ * `scratch` = ghn3_conv_frozen_scratch_floats(desc, backward) floats.  No allocation, no synchronisation inside.  Deterministic. */
+int64_t ghn3_conv_frozen_scratch_floats(const ghn3_conv_desc* desc, int backward);  /* < 0: bad descriptor (ghn3_last_error) */
+int ghn3_conv_frozen_fwd(const ghn3_conv_desc* desc, const float* x, const float* w, const float* gamma, const float* beta,
+                         const float* mean, const float* var, float* z, float* out, float* scratch, void* stream);
+int ghn3_conv_frozen_bwd(const ghn3_conv_desc* desc, const float* dout, const float* x, const float* z, const float* w,
+                         const float* gamma, const float* mean, const float* var, float* dx, float* dw, float* dgamma, float* dbeta,
+                         float* scratch, void* stream);
 
 /* ---- target-network layers, third slice (ABI v19, round 6): squeeze-and-excitation with a hard-swish gate -----------------
  * Replaces `ChannelSELayer.forward` (/root/reference/ghn3/ops.py:239-274) executed at trainer.py:308-319 and torch autograd of it:
