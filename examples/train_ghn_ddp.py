@@ -59,6 +59,8 @@ def main():
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--bn-free-prob', type=float, default=0.0,
                     help='share of the architecture stream drawn without norm layers (norm=None); 0: the default stream')
+    ap.add_argument('--opt-state', choices=('fp32', 'bf16'), default='fp32',
+                    help='type of the AdamW moments; bf16: half the optimizer state, stored by stochastic rounding')
     ap.add_argument('--save', default=None)
     ap.add_argument('--native', action='store_true',
                     help='run the target networks on ATen native convolution / batch-norm kernels instead of MIOpen')
@@ -93,7 +95,8 @@ def main():
     kw = dict(large_images=args.imagenet, seed=args.seed, max_nodes=args.max_nodes, bn_free_prob=args.bn_free_prob)
     total = args.steps * args.epochs
 
-    trainer = Trainer(ghn, opt='adamw', opt_args={'lr': args.lr, 'weight_decay': args.wd}, scheduler='cosine',
+    trainer = Trainer(ghn, opt='adamw', opt_args={'lr': args.lr, 'weight_decay': args.wd, 'state_dtype': args.opt_state,
+                                                'state_seed': args.seed % (1 << 24)}, scheduler='cosine',
                       n_batches=args.steps, grad_clip=5, device=ddp.device, log_interval=10, amp=args.amp,
                       amp_min_scale=1024, predparam_wd=3e-5, label_smoothing=0.1 if args.imagenet else 0.0,
                       save_dir=args.save, epochs=args.epochs, verbose=ddp.rank == 0)

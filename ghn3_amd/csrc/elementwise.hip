@@ -1760,8 +1760,68 @@ static int adamw_nt_env() {
     static const int v = getenv("GHN3_ADAMW_NT") ? atoi(getenv("GHN3_ADAMW_NT")) != 0 : 1;
     return v;
 }
-// gradient / moment buffers congruent to the source of a cast (same float offsets): GHN3_OP_ADAMW_CAST16
-struct AdamWSrc { const float* g; float* m; float* v; const float* sumsq; AdamWArgs a; };
+// gradient / moment buffers congruent to the source of a cast (same element offsets): GHN3_OP_ADAMW_CAST16.  MT = float, or
+// unsigned short for bf16 moments (GHN3_OP_ADAMW_S16_CAST16)
+template <typename MT> struct AdamWSrcT { const float* g; MT* m; MT* v; const float* sumsq; AdamWArgs a; };
+typedef AdamWSrcT<float> AdamWSrc;
+
+// bf16 moments (GHN3_OP_ADAMW_S16 / _S16_CAST16): the update runs in fp32 on the widened moments, the parameter takes the
+// unrounded new moments, and only what is carried to the next step is rounded -- stochastically: 16 random bits are added to
+// the low half of the fp32 pattern, which is then truncated, so the stored magnitude is the upper neighbour with probability
+// (discarded bits) / 2^16: unbiased for either sign.  (Round-to-nearest would freeze exp_avg_sq: with beta2 = 0.999 a step
+// moves it by 0.1 %, less than half a bf16 ulp.)  The bits are a pure function of (seed, step, flat element index, which
+// moment) -- never of the grid, the launch partition, the stream or an address -- so reruns and every split of the flat
+// buffer into launches give the same bits.  key = adamw_rng_key(seed, step) once per launch, one hash per element:
+// low half -> exp_avg, high half -> exp_avg_sq.
+struct AdamWRng { unsigned key; unsigned base; };      // base: flat index (mod 2^32) of the element the moment pointers address
+__host__ __device__ __forceinline__ unsigned adamw_mix32(unsigned x) {
+    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+    return x;
+}
+static unsigned adamw_rng_key(unsigned seed, unsigned step) { return adamw_mix32(seed * 0x9e3779b9u + step); }
+__device__ __forceinline__ unsigned short bf16_stochastic(float x, unsigned r16) {
+    return (unsigned short)((__builtin_bit_cast(unsigned, x) + r16) >> 16);
+}
+typedef unsigned u32x2_nt __attribute__((ext_vector_type(2)));
+// four consecutive moments, widened to fp32 (exact) / stored back; `idx` = flat index of the first of the four.
+// NT: the cache policy of the bf16 accesses as a compile-time constant (1 = non-temporal) -- two branches on a run-time flag
+// that load the same 8 bytes are folded into one plain load before this function is inlined
+template <int NT> __device__ __forceinline__ float4 ld_m4(const float* p, bool nt) { return ld4(p, nt); }
+template <int NT> __device__ __forceinline__ float4 ld_m4(const unsigned short* p, bool) {
+    u32x2_nt w;
+    if constexpr (NT > 0) w = __builtin_nontemporal_load(reinterpret_cast<const u32x2_nt*>(p));
+    else w = *reinterpret_cast<const u32x2_nt*>(p);
+    return make_float4(__builtin_bit_cast(float, w[0] << 16), __builtin_bit_cast(float, w[0] & 0xffff0000u),
+                       __builtin_bit_cast(float, w[1] << 16), __builtin_bit_cast(float, w[1] & 0xffff0000u));
+}
+template <int NT>
+__device__ __forceinline__ void st_mv4(float* m, float* v, const float4& mv, const float4& vv, bool nt, const AdamWRng&, unsigned) {
+    st4(m, mv, nt); st4(v, vv, nt);
+}
+template <int NT>
+__device__ __forceinline__ void st_mv4(unsigned short* m, unsigned short* v, const float4& mv, const float4& vv, bool,
+                                       const AdamWRng& rng, unsigned idx) {
+    const unsigned h0 = adamw_mix32(idx ^ rng.key), h1 = adamw_mix32((idx + 1u) ^ rng.key),
+                   h2 = adamw_mix32((idx + 2u) ^ rng.key), h3 = adamw_mix32((idx + 3u) ^ rng.key);
+    const u32x2_nt wm = {(unsigned)bf16_stochastic(mv.x, h0 & 0xffffu) | ((unsigned)bf16_stochastic(mv.y, h1 & 0xffffu) << 16),
+                         (unsigned)bf16_stochastic(mv.z, h2 & 0xffffu) | ((unsigned)bf16_stochastic(mv.w, h3 & 0xffffu) << 16)};
+    const u32x2_nt wv = {(unsigned)bf16_stochastic(vv.x, h0 >> 16) | ((unsigned)bf16_stochastic(vv.y, h1 >> 16) << 16),
+                         (unsigned)bf16_stochastic(vv.z, h2 >> 16) | ((unsigned)bf16_stochastic(vv.w, h3 >> 16) << 16)};
+    if constexpr (NT > 0) {
+        __builtin_nontemporal_store(wm, reinterpret_cast<u32x2_nt*>(m));
+        __builtin_nontemporal_store(wv, reinterpret_cast<u32x2_nt*>(v));
+    } else {
+        *reinterpret_cast<u32x2_nt*>(m) = wm;
+        *reinterpret_cast<u32x2_nt*>(v) = wv;
+    }
+}
+__device__ __forceinline__ float ld_m1(const float* p) { return *p; }
+__device__ __forceinline__ float ld_m1(const unsigned short* p) { return bf16_back(*p); }
+__device__ __forceinline__ void st_mv1(float* m, float* v, float mi, float vi, const AdamWRng&, unsigned) { *m = mi; *v = vi; }
+__device__ __forceinline__ void st_mv1(unsigned short* m, unsigned short* v, float mi, float vi, const AdamWRng& rng, unsigned idx) {
+    const unsigned h = adamw_mix32(idx ^ rng.key);
+    *m = bf16_stochastic(mi, h & 0xffffu); *v = bf16_stochastic(vi, h >> 16);
+}
 
 __device__ __forceinline__ float nofuse(float x) { asm volatile("" : "+v"(x)); return x; }   // the value exists in a register: no FMA across it
 // per-launch scalars of the update, explicitly rounded like adamw_element: the two kernels that share them must not differ by a
@@ -1793,11 +1853,14 @@ __device__ __forceinline__ void adamw_element(float& p, float g, float& m, float
 // offsets in aw.g / aw.m / aw.v; written back in place) and are then cast -- the 16-bit copies of a weight follow its
 // update without a second pass over it (host contract: fp32 source, cols % 4 == 0, no column map, every source element
 // in exactly one work tile)
-template <bool ADAMW>
+// NT (bf16-state kernels): the cache policy as a compile-time constant, 1 = non-temporal.  Behind the run-time flag of the
+// fp32-state kernels (NT = -1) the compiler folds the two branches of an access into one plain access where it can.
+template <bool ADAMW, typename MT = float, int NT = -1>
 __device__ __forceinline__ void cast16_body(const float* __restrict__ src, unsigned short* __restrict__ dst,
                                             const ghn3_cast_desc* __restrict__ descs, int n_desc,
                                             float* __restrict__ dbias, int total_items,
-                                            const float* __restrict__ amax, const AdamWSrc& aw) {
+                                            const float* __restrict__ amax, const AdamWSrcT<MT>& aw,
+                                            const AdamWRng& rng = AdamWRng{}) {
     __shared__ unsigned short tr[64][66];          // transposed-copy staging (already converted)
     __shared__ float csum[16][64];
     float aw_clip = 1.f, aw_step = 0.f, aw_decay = 1.f;
@@ -1895,16 +1958,15 @@ __device__ __forceinline__ void cast16_body(const float* __restrict__ src, unsig
                 if (c + 3 < D.cols) {
                     const int64_t o = D.src_off + (int64_t)r * D.ld_src + c;
                     float* pp = const_cast<float*>(src) + o;
-                    const bool nt = aw.a.nt != 0;
+                    const bool nt = NT < 0 ? aw.a.nt != 0 : NT != 0;
                     x = ld4(pp, nt);
                     const float4 gv = ld4(aw.g + o, nt);
-                    float4 mv = ld4(aw.m + o, nt), vv = ld4(aw.v + o, nt);
+                    float4 mv = ld_m4<NT>(aw.m + o, nt), vv = ld_m4<NT>(aw.v + o, nt);
                     adamw_element(x.x, gv.x, mv.x, vv.x, aw.a, aw_clip, aw_step, aw_decay);
                     adamw_element(x.y, gv.y, mv.y, vv.y, aw.a, aw_clip, aw_step, aw_decay);
                     adamw_element(x.z, gv.z, mv.z, vv.z, aw.a, aw_clip, aw_step, aw_decay);
                     adamw_element(x.w, gv.w, mv.w, vv.w, aw.a, aw_clip, aw_step, aw_decay);
-                    st4(aw.m + o, mv, nt);
-                    st4(aw.v + o, vv, nt);
+                    st_mv4<NT>(aw.m + o, aw.v + o, mv, vv, nt, rng, rng.base + (unsigned)o);
                     st4(pp, x, nt);
                 }
             } else {
@@ -2049,6 +2111,12 @@ __global__ __launch_bounds__(256) void adamw_cast16_kernel(float* __restrict__ p
                                                            int total_items, AdamWSrc aw) {
     cast16_body<true>(p, dst, descs, n_desc, nullptr, total_items, nullptr, aw);
 }
+template <int NT>
+__global__ __launch_bounds__(256) void adamw_s16_cast16_kernel(float* __restrict__ p, unsigned short* __restrict__ dst,
+                                                               const ghn3_cast_desc* __restrict__ descs, int n_desc,
+                                                               int total_items, AdamWSrcT<unsigned short> aw, AdamWRng rng) {
+    cast16_body<true, unsigned short, NT>(p, dst, descs, n_desc, nullptr, total_items, nullptr, aw, rng);
+}
 
 int ghn3_cast16(const float* src, void* dst, const ghn3_cast_desc* d_desc, int n_desc, int total_blocks, float* dbias,
                 const float* amax, int grid_cap, hipStream_t s) {
@@ -2153,9 +2221,12 @@ int ghn3_sumsq(float* out, const float* x, int64_t n, float* parts, int64_t skip
 
 // torch.optim.AdamW (decoupled weight decay) with the gradient scaled by clip_grad_norm_'s coefficient
 // min(1, max_norm / (||g|| + 1e-6)); `sumsq` holds ||g||^2 (absent: no clipping)
-__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                    float* __restrict__ m, float* __restrict__ v, int64_t n,
-                                                    const float* __restrict__ sumsq, AdamWArgs a) {
+// MT = float: GHN3_OP_ADAMW.  MT = unsigned short: bf16 moments, stored by stochastic rounding (GHN3_OP_ADAMW_S16; 20 bytes
+// per parameter instead of 28: 16-byte accesses for p and g, 8-byte ones for four moments)
+template <typename MT, int NT = -1>
+__device__ __forceinline__ void adamw_body(float* __restrict__ p, const float* __restrict__ g,
+                                           MT* __restrict__ m, MT* __restrict__ v, int64_t n,
+                                           const float* __restrict__ sumsq, const AdamWArgs& a, const AdamWRng& rng) {
     // Non-finite gradient norm (a NaN / inf anywhere in the -- already rank-averaged -- flat gradient): the update is
     // skipped on every rank alike, like GradScaler's found_inf and the reference trainer's NaN-loss skip
     // (trainer.py:240-257), without a host round trip.
@@ -2165,23 +2236,35 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
     // 16 bytes per lane (the pass streams 28 bytes per parameter: 4 loads + 3 stores -- HBM-bound); same arithmetic per
     // element as the scalar tail, so results do not depend on the path
     int64_t n4 = 0;
-    if (((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
-          reinterpret_cast<uintptr_t>(v)) & 15) == 0) {
+    constexpr uintptr_t MA = 4 * sizeof(MT) - 1;       // four moments per access
+    if (((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g)) & 15) == 0 &&
+        ((reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v)) & MA) == 0) {
         n4 = n >> 2;
-        const bool nt = a.nt != 0;
+        const bool nt = NT < 0 ? a.nt != 0 : NT != 0;
         for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
-            float4 pv = ld4(p + 4 * i, nt), gv = ld4(g + 4 * i, nt), mv = ld4(m + 4 * i, nt), vv = ld4(v + 4 * i, nt);
+            float4 pv = ld4(p + 4 * i, nt), gv = ld4(g + 4 * i, nt), mv = ld_m4<NT>(m + 4 * i, nt), vv = ld_m4<NT>(v + 4 * i, nt);
             float* pe = &pv.x; float* ge = &gv.x; float* me = &mv.x; float* ve = &vv.x;
 #pragma unroll
             for (int e = 0; e < 4; ++e) adamw_element(pe[e], ge[e], me[e], ve[e], a, clip, step, decay);
-            st4(m + 4 * i, mv, nt); st4(v + 4 * i, vv, nt); st4(p + 4 * i, pv, nt);
+            st_mv4<NT>(m + 4 * i, v + 4 * i, mv, vv, nt, rng, rng.base + (unsigned)(4 * i)); st4(p + 4 * i, pv, nt);
         }
     }
     for (int64_t i = 4 * n4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        float pi = p[i], mi = m[i], vi = v[i];
+        float pi = p[i], mi = ld_m1(m + i), vi = ld_m1(v + i);
         adamw_element(pi, g[i], mi, vi, a, clip, step, decay);
-        m[i] = mi; v[i] = vi; p[i] = pi;
+        st_mv1(m + i, v + i, mi, vi, rng, rng.base + (unsigned)i); p[i] = pi;
     }
+}
+__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                    float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                                    const float* __restrict__ sumsq, AdamWArgs a) {
+    adamw_body<float>(p, g, m, v, n, sumsq, a, AdamWRng{});
+}
+template <int NT>
+__global__ __launch_bounds__(256) void adamw_s16_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                        unsigned short* __restrict__ m, unsigned short* __restrict__ v,
+                                                        int64_t n, const float* __restrict__ sumsq, AdamWArgs a, AdamWRng rng) {
+    adamw_body<unsigned short, NT>(p, g, m, v, n, sumsq, a, rng);
 }
 int ghn3_adamw_cast16(float* p, const float* g, float* m, float* v, void* dst, const ghn3_cast_desc* d_desc, int n_desc,
                       int total_blocks, const float* sumsq, float lr, float beta1, float beta2, float eps, float weight_decay,
@@ -2209,4 +2292,58 @@ int ghn3_adamw(float* p, const float* g, float* m, float* v, int64_t n, const fl
     if (blocks > 16384) blocks = 16384;
     hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p, g, m, v, n, sumsq, a);
     return launch_ok("adamw");
+}
+
+// step and seed of the bf16-state kinds travel in the op's f2 / f3: integers a float holds exactly
+static int adamw_rng_of(float step, float seed, int64_t base, AdamWRng* rng, const char* what) {
+    if (!(step >= 0.f) || !(seed >= 0.f) || step != floorf(step) || seed != floorf(seed) || base < 0) {
+        ghn3_set_error("%s: step (f2) and seed (f3) must be non-negative integers", what);
+        return GHN3_E_ARG;
+    }
+    if (step >= 16777216.f || seed >= 16777216.f) {
+        ghn3_set_error("%s: step %.0f / seed %.0f: 2^24 or more is not exact in the op's float fields", what, step, seed);
+        return GHN3_E_LIMIT;
+    }
+    rng->key = adamw_rng_key((unsigned)seed, (unsigned)step);
+    rng->base = (unsigned)(uint64_t)base;
+    return GHN3_OK;
+}
+
+int ghn3_adamw_s16_cast16(float* p, const float* g, void* m, void* v, void* dst, const ghn3_cast_desc* d_desc, int n_desc,
+                          int total_blocks, const float* sumsq, float lr, float beta1, float beta2, float eps,
+                          float weight_decay, float bias_corr1, float bias_corr2, float max_norm, float inv_scale, float step,
+                          float seed, int64_t base, hipStream_t s) {
+    if (n_desc <= 0 || total_blocks <= 0) return GHN3_OK;
+    if (((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g)) & 15) ||
+        ((reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v)) & 7)) {
+        ghn3_set_error("adamw_s16_cast16: parameters / gradients must be 16-byte, bf16 moments 8-byte aligned");
+        return GHN3_E_ARG;
+    }
+    AdamWRng rng;
+    if (int rc = adamw_rng_of(step, seed, base, &rng, "adamw_s16_cast16")) return rc;
+    AdamWSrcT<unsigned short> aw{g, (unsigned short*)m, (unsigned short*)v, sumsq,
+                                 AdamWArgs{lr, beta1, beta2, eps, weight_decay, bias_corr1, sqrtf(bias_corr2), max_norm,
+                                           inv_scale > 0.f ? inv_scale : 1.f, adamw_nt_env()}};
+    hipLaunchKernelGGL(aw.a.nt ? adamw_s16_cast16_kernel<1> : adamw_s16_cast16_kernel<0>, dim3(total_blocks), dim3(256), 0, s, p,
+                       (unsigned short*)dst, d_desc, n_desc, total_blocks, aw, rng);
+    return launch_ok("adamw_s16_cast16");
+}
+
+int ghn3_adamw_s16(float* p, const float* g, void* m, void* v, int64_t n, const float* sumsq, float lr, float beta1,
+                   float beta2, float eps, float weight_decay, float bias_corr1, float bias_corr2, float max_norm,
+                   float inv_scale, float step, float seed, int64_t base, hipStream_t s) {
+    if (n <= 0) return GHN3_OK;
+    if ((reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v)) & 1) {
+        ghn3_set_error("adamw_s16: bf16 moments must be 2-byte aligned");
+        return GHN3_E_ARG;
+    }
+    AdamWRng rng;
+    if (int rc = adamw_rng_of(step, seed, base, &rng, "adamw_s16")) return rc;
+    AdamWArgs a{lr, beta1, beta2, eps, weight_decay, bias_corr1, sqrtf(bias_corr2), max_norm,
+                inv_scale > 0.f ? inv_scale : 1.f, adamw_nt_env()};
+    int64_t blocks = (n / 4 + 255) / 256 + 1;
+    if (blocks > 16384) blocks = 16384;
+    hipLaunchKernelGGL(a.nt ? adamw_s16_kernel<1> : adamw_s16_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, s, p, g,
+                       (unsigned short*)m, (unsigned short*)v, n, sumsq, a, rng);
+    return launch_ok("adamw_s16");
 }

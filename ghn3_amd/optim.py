@@ -20,10 +20,21 @@ def _dbits(x):
 
 
 class FusedAdamW:
-    """AdamW + gradient-norm clipping for a ghn3_amd.GHN3 (same update rule and defaults as torch.optim.AdamW)."""
+    """AdamW + gradient-norm clipping for a ghn3_amd.GHN3 (same update rule and defaults as torch.optim.AdamW).
+
+    state_dtype: 'fp32' (default: the moments are fp32, the update is torch.optim.AdamW's) or 'bf16': exp_avg and exp_avg_sq
+    are kept in bf16 -- half the optimizer state, 20 instead of 28 bytes per parameter through the pass.  Parameters,
+    gradients and the arithmetic of the update stay fp32; only what is carried to the next step is rounded, stochastically
+    (GHN3_OP_ADAMW_S16; round-to-nearest would freeze exp_avg_sq).  The random bits are a function of `state_seed`, the step
+    number and the element's index in the flat buffer: a rerun repeats them bit for bit, whatever form the step takes."""
 
     def __init__(self, ghn, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=0.0,
-                 nan_guard=True):
+                 nan_guard=True, state_dtype='fp32', state_seed=0):
+        if state_dtype not in ('fp32', 'bf16'):
+            raise ValueError("state_dtype must be 'fp32' or 'bf16', got %r" % (state_dtype,))
+        if int(state_seed) != state_seed or not 0 <= state_seed < STATE16_LIMIT:
+            raise ValueError('state_seed must be an integer in [0, 2^24), got %r' % (state_seed,))
+        self.state_dtype, self.state_seed = state_dtype, int(state_seed)
         self.ghn = ghn
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.max_grad_norm = max_grad_norm
@@ -34,8 +45,9 @@ class FusedAdamW:
         flat = ghn._flat
         if not flat.is_cuda:
             raise L.Ghn3Error('FusedAdamW runs on an MI355X only (no CPU path)')
-        self.exp_avg = torch.zeros_like(flat)
-        self.exp_avg_sq = torch.zeros_like(flat)
+        mdt = torch.bfloat16 if state_dtype == 'bf16' else flat.dtype
+        self.exp_avg = torch.zeros_like(flat, dtype=mdt)
+        self.exp_avg_sq = torch.zeros_like(flat, dtype=mdt)
         self.scal = torch.zeros(16 + 8192, dtype=torch.float32, device=flat.device)   # [norm^2 ...| partial sums]
         self.steps = 0
         self._w2_descs = {}
@@ -126,10 +138,20 @@ class FusedAdamW:
         hyper = (self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay,
                  1.0 - self.betas[0] ** self.steps, 1.0 - self.betas[1] ** self.steps)
 
+        s16 = self.state_dtype == 'bf16'
+        if s16 and self.steps >= STATE16_LIMIT:
+            raise L.Ghn3Error('bf16 optimizer state: step %d does not fit the op (limit 2^24)' % self.steps)
+
         def adamw(op, kind, lo, count):
             op['kind'] = kind
             op['r']['buf'][:5] = (0, 1, 2, 3, 4 if guard else -1)
             op['r']['off'][:4] = 4 * lo
+            if s16:
+                # (bf16 moments: same element offset, 2 bytes each -- the kernel takes the flat index of its first element,
+                # which the random bits of the rounding depend on, from this offset; step and seed ride in f2 / f3)
+                op['kind'] = {L.OP_ADAMW: L.OP_ADAMW_S16, L.OP_ADAMW_CAST16: L.OP_ADAMW_S16_CAST16}[kind]
+                op['r']['off'][2:4] = 2 * lo
+                op['f'][2], op['f'][3] = float(self.steps), float(self.state_seed)
             op['i'][0] = count
             for k, h in enumerate(hyper):
                 op['i'][1 + k] = _dbits(h)
@@ -180,7 +202,9 @@ class FusedAdamW:
     def state_dict(self):
         """State in the layout of ``torch.optim.AdamW.state_dict()`` over ``ghn.parameters()`` (the order the reference's
         trainer hands to its optimizer, trainer.py:165-175), so that ``{'state_dict', 'optimizer', 'epoch', 'step'}``
-        checkpoints written by either trainer resume in the other.  The moment tensors are views of the flat buffers."""
+        checkpoints written by either trainer resume in the other.  With fp32 state the moment tensors are views of the flat
+        buffers; with bf16 state they are fp32 COPIES (exact: every bf16 value is an fp32 value), so the file stays
+        interchangeable with torch.optim.AdamW and with the fp32-state optimizer, which resumes from it exactly."""
         ghn = self.ghn
         self.wait()                               # (an overlapped step may still be writing the moments)
         slot_of = {id(p): k for k, p in enumerate(ghn._slot_params())}
@@ -191,15 +215,17 @@ class FusedAdamW:
             order.append(i)
             if self.steps > 0:
                 state[i] = {'step': torch.tensor(float(self.steps)),
-                            'exp_avg': self.exp_avg[o:o + n].view(p.shape),
-                            'exp_avg_sq': self.exp_avg_sq[o:o + n].view(p.shape)}
+                            'exp_avg': self.exp_avg[o:o + n].view(p.shape).float(),
+                            'exp_avg_sq': self.exp_avg_sq[o:o + n].view(p.shape).float()}
         group = {'lr': self.lr, 'betas': tuple(self.betas), 'eps': self.eps, 'weight_decay': self.weight_decay,
                  'amsgrad': False, 'maximize': False, 'foreach': None, 'capturable': False, 'differentiable': False,
                  'fused': None, 'params': order}
         return {'state': state, 'param_groups': [group]}
 
     def load_state_dict(self, sd):
-        """Accepts a ``torch.optim.AdamW`` (or FusedAdamW) state dict over ``ghn.parameters()``."""
+        """Accepts a ``torch.optim.AdamW`` (or FusedAdamW, of either state type) state dict over ``ghn.parameters()``.  With
+        bf16 state the fp32 moments of the file are rounded to nearest even (moments a bf16-state optimizer wrote are bf16
+        values already: unchanged)."""
         ghn = self.ghn
         self.wait()
         groups = sd['param_groups']
@@ -240,6 +266,72 @@ def adamw_reference_(p, g, m, v, sumsq, step, lr, betas, eps, weight_decay, max_
     v.mul_(betas[1]).addcmul_(gg, gg, value=1.0 - betas[1])
     denom = (v / (1.0 - betas[1] ** step)).sqrt_().add_(eps)
     p.addcdiv_(m / (1.0 - betas[0] ** step), denom, value=-lr)
+
+
+STATE16_LIMIT = 1 << 24        # step numbers and seeds of the bf16-state ops travel in floats: exact below 2^24
+
+
+def _mix32(x):
+    """The 32-bit integer hash of the bf16-state kernels (include/ghn3_hip.h, GHN3_OP_ADAMW_S16) on a uint32 array."""
+    x = np.array(x, dtype=np.uint32)
+    x ^= x >> np.uint32(16)
+    x *= np.uint32(0x7feb352d)
+    x ^= x >> np.uint32(15)
+    x *= np.uint32(0x846ca68b)
+    x ^= x >> np.uint32(16)
+    return x
+
+
+def state16_random_bits(seed, step, base, n):
+    """One hash per element of the flat range [base, base + n): the low half rounds exp_avg, the high half exp_avg_sq.  A
+    function of seed, step and flat index alone."""
+    key = _mix32([(int(seed) * 0x9e3779b9 + int(step)) & 0xffffffff])[0]
+    idx = ((np.arange(n, dtype=np.int64) + int(base)) & 0xffffffff).astype(np.uint32)
+    return _mix32(idx ^ key)
+
+
+def bf16_stochastic_round(x, r16):
+    """bf16 bit patterns (uint16) of the fp32 array x: 16 random bits added to the low half of the pattern, then truncated."""
+    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32) + r16.astype(np.uint32)
+    return (u >> np.uint32(16)).astype(np.uint16)
+
+
+def adamw_state16_reference_(p, g, m, v, sumsq, step, lr, betas, eps, weight_decay, max_norm, inv_scale, seed=0, base=0):
+    """Host restatement of one GHN3_OP_ADAMW_S16 launch, operation for operation (numpy, in place): p, g are fp32 CPU tensors,
+    m, v torch.bfloat16 ones, all views of flat buffers starting at flat element `base`.  The stored moments are widened
+    (exact), the update runs in fp32 with the kernel's roundings (adamw_element: the two moment updates are fused
+    multiply-adds, every other product is rounded on its own), p takes the unrounded moments, and each moment is stored by
+    stochastic rounding with the bits of state16_random_bits.  A non-finite norm leaves everything untouched.  This is the
+    rule the CPU tests check (unbiased, no stall, independent of the partition) and the GPU tests compare bits against."""
+    f = np.float32
+    if not 0 <= int(step) < STATE16_LIMIT:
+        raise ValueError('step %r outside [0, 2^24)' % (step,))
+    ss = f(float(sumsq)) if sumsq is not None else None
+    if ss is not None and not np.isfinite(ss):
+        return
+    inv = f(inv_scale) if inv_scale > 0 else f(1)
+    clip = inv
+    if ss is not None and max_norm > 0:
+        clip = f(inv * min(f(1), f(max_norm) / f(f(np.sqrt(ss) * inv) + f(1e-6))))
+    b1, b2 = f(betas[0]), f(betas[1])
+    bc1, bc2s = f(1.0 - betas[0] ** step), np.sqrt(f(1.0 - betas[1] ** step))
+    stepsz = f(f(lr) / bc1)
+    decay = f(f(1) - f(f(lr) * f(weight_decay)))
+    pn, gn = p.numpy(), g.numpy()
+    mb, vb = m.view(torch.int16).numpy().view(np.uint16), v.view(torch.int16).numpy().view(np.uint16)
+    mf = (mb.astype(np.uint32) << np.uint32(16)).view(np.float32)
+    vf = (vb.astype(np.uint32) << np.uint32(16)).view(np.float32)
+
+    def fma(a, x, y):            # one rounding (the product of two fp32 values is exact in float64)
+        return (np.float64(a) * x.astype(np.float64) + y.astype(np.float64)).astype(np.float32)
+    gi = gn * clip
+    mi = fma(b1, mf, (f(1) - b1) * gi)
+    vi = fma(b2, vf, ((f(1) - b2) * gi) * gi)
+    den = np.sqrt(vi) / bc2s + f(eps)
+    pn[...] = pn * decay - (stepsz * mi) / den
+    h = state16_random_bits(seed, step, base, pn.size).reshape(pn.shape)
+    mb[...] = bf16_stochastic_round(mi, h & np.uint32(0xffff))
+    vb[...] = bf16_stochastic_round(vi, h >> np.uint32(16))
 
 
 class ShardedAdamW:

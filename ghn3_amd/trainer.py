@@ -145,7 +145,7 @@ class Trainer:
             sync_parameters(model)                       # what DistributedDataParallel's constructor does
             model.grad_reducer = FlatGradReducer(compress=grad_compress)
         self.base_lr = float(opt_args['lr'])
-        kw = {k: v for k, v in opt_args.items() if k in ('betas', 'eps', 'weight_decay')}
+        kw = {k: v for k, v in opt_args.items() if k in ('betas', 'eps', 'weight_decay', 'state_dtype', 'state_seed')}
         self._optimizer = FusedAdamW(model, lr=self.base_lr, max_grad_norm=float(grad_clip or 0.0), **kw)
         self._lr_mult = _schedule(scheduler, epochs or 1, self.base_lr, scheduler_args)
         self._epoch = self.start_epoch

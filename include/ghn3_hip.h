@@ -438,6 +438,25 @@ enum ghn3_op_kind {
      * belongs to exactly one descriptor.  A non-finite r4 leaves parameters, moments and copies untouched.  Same arithmetic
      * per element as GHN3_OP_ADAMW (bit-identical parameters).  (ABI v16) */
     GHN3_OP_ADAMW_CAST16 = 35,
+    /* GHN3_OP_ADAMW / GHN3_OP_ADAMW_CAST16 with the two moments kept in bf16: r2 / r3 point into buffers of 2 bytes per
+     * element, congruent to the parameter buffer by element index (their byte offsets are half of r0's); 20 bytes per
+     * parameter stream through the pass instead of 28.  Everything else -- r0, r1, r4 (r5, r6), i0..i7, f0, f1, the NaN guard
+     * (parameters, moments and 16-bit copies untouched), the non-temporal policy -- is as in the fp32-state kind.
+     * Per element: the stored moments are widened to fp32 (exact), the fp32-state update runs unchanged, the parameter takes
+     * the UNROUNDED new moments (bit-identical to the fp32-state kind from the same widened state), and each new moment is
+     * stored by stochastic rounding: u = fp32 bit pattern + 16 random bits, stored = u >> 16 (the magnitude goes to the upper
+     * bf16 neighbour with probability (discarded bits) / 2^16: unbiased for either sign; round-to-nearest would freeze
+     * exp_avg_sq, whose step of 0.1 % at beta2 = 0.999 is below half a bf16 ulp).
+     * Random bits: h = mix32(e ^ mix32(seed * 0x9e3779b9 + step)) with mix32(x) = { x ^= x >> 16; x *= 0x7feb352d;
+     * x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16 } in 32-bit arithmetic and e = the element's index in the flat buffer
+     * (mod 2^32): (byte offset of r2) / 2 + index inside the launch (CAST16 form: + the descriptor's src_off + row * ld_src +
+     * column); exp_avg takes h & 0xffff, exp_avg_sq takes h >> 16.  They depend on the seed, the step, the flat index and
+     * the moment only -- not on the grid, on how the flat buffer is split into launches, on the stream or on an address:
+     * reruns and every partition give the same bits, and the two kinds agree bit for bit.
+     * f2 = step number, f3 = seed: non-negative integers below 2^24 (exact in a float; GHN3_E_LIMIT from 2^24 on).
+     * The 16-byte path needs r0 / r1 16-byte and r2 / r3 8-byte aligned (CAST16 form: required). */
+    GHN3_OP_ADAMW_S16 = 36,
+    GHN3_OP_ADAMW_S16_CAST16 = 37,
     GHN3_OP_KIND_COUNT
 };
 

@@ -20,7 +20,7 @@ ctx = L.context(0)
 stream = torch.cuda.current_stream().cuda_stream
 fin = prog.norm_fin_ops()
 one = torch.ones(1, dtype=torch.float32, device=dev)
-opt = FusedAdamW(ghn, lr=1e-6, max_grad_norm=5.0)
+opt = FusedAdamW(ghn, lr=1e-6, max_grad_norm=5.0, state_dtype=os.environ.get('DIAG_OPT_STATE', 'fp32'))   # fp32 | bf16
 fused = os.environ.get('DIAG_FUSED', '1') != '0'       # FusedAdamW.step with the plan: the W2 update writes its 16-bit copies
 
 
