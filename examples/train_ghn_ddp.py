@@ -59,6 +59,9 @@ def main():
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--bn-free-prob', type=float, default=0.0,
                     help='share of the architecture stream drawn without norm layers (norm=None); 0: the default stream')
+    ap.add_argument('--width-mult', type=int, default=1,
+                    help='multiplies the drawn width C of every architecture (4: the widths of the `wide` evaluation split); '
+                         '1: the default stream')
     ap.add_argument('--opt-state', choices=('fp32', 'bf16'), default='fp32',
                     help='type of the AdamW moments; bf16: half the optimizer state, stored by stochastic rounding')
     ap.add_argument('--save', default=None)
@@ -92,7 +95,8 @@ def main():
 
     world = ddp.world_size if ddp.ddp else 1
     per_rank = args.meta_batch_size // world
-    kw = dict(large_images=args.imagenet, seed=args.seed, max_nodes=args.max_nodes, bn_free_prob=args.bn_free_prob)
+    kw = dict(large_images=args.imagenet, seed=args.seed, max_nodes=args.max_nodes, bn_free_prob=args.bn_free_prob,
+              width_mult=args.width_mult)
     total = args.steps * args.epochs
 
     trainer = Trainer(ghn, opt='adamw', opt_args={'lr': args.lr, 'weight_decay': args.wd, 'state_dtype': args.opt_state,

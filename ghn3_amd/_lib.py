@@ -79,7 +79,8 @@ EXPORTS = ['ghn3_abi_version', 'ghn3_last_error', 'ghn3_ctx_create', 'ghn3_ctx_d
            'ghn3_conv_scratch_floats', 'ghn3_conv_bn_fwd', 'ghn3_conv_bn_bwd', 'ghn3_se_fwd', 'ghn3_se_bwd', 'ghn3_pool_fwd', 'ghn3_pool_bwd',
            'ghn3_msa_scratch_floats', 'ghn3_msa_fwd', 'ghn3_msa_bwd', 'ghn3_head_scratch_floats', 'ghn3_head_fwd',
            'ghn3_head_bwd', 'ghn3_xent_fwd', 'ghn3_xent_bwd', 'ghn3_join_fwd', 'ghn3_join_bwd', 'ghn3_posenc_bwd',
-           'ghn3_attn_lean_fwd', 'ghn3_attn_lean_bwd', 'ghn3_msa_lean_scratch_floats', 'ghn3_msa_lean_fwd', 'ghn3_msa_lean_bwd']
+           'ghn3_attn_lean_fwd', 'ghn3_attn_lean_bwd', 'ghn3_msa_lean_scratch_floats', 'ghn3_msa_lean_fwd', 'ghn3_msa_lean_bwd',
+           'ghn3_dw_scratch_floats', 'ghn3_dw_fwd', 'ghn3_dw_bwd']
 OPFLAG_TIMED = 0x100
 OPFLAG_SIDE = 0x200
 
@@ -134,6 +135,10 @@ def load():
         lib.ghn3_dwpw_frozen_scratch_floats.restype = ctypes.c_int64
         lib.ghn3_dwpw_frozen_fwd.argtypes = [ctypes.c_void_p] * 11
         lib.ghn3_dwpw_frozen_bwd.argtypes = [ctypes.c_void_p] * 16
+        lib.ghn3_dw_scratch_floats.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        lib.ghn3_dw_scratch_floats.restype = ctypes.c_int64
+        lib.ghn3_dw_fwd.argtypes = [ctypes.c_void_p] * 5
+        lib.ghn3_dw_bwd.argtypes = [ctypes.c_void_p] * 8
         lib.ghn3_conv_frozen_scratch_floats.argtypes = [ctypes.c_void_p, ctypes.c_int]
         lib.ghn3_conv_frozen_scratch_floats.restype = ctypes.c_int64
         lib.ghn3_conv_frozen_fwd.argtypes = [ctypes.c_void_p] * 11

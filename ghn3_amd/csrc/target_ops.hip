@@ -25,6 +25,12 @@
 // (fixed-order partial slots).  Weights are read IN PLACE: w_dw [C_in][ks][ks], w_pw [C_out][C_in], gamma / beta [C_out] are
 // views of the GHN's flat prediction buffer; their gradients are written densely for autograd to route back into it.
 // Limits (checked by the host): C_in, C_out multiples of 4 and <= 512, ks <= 7 (odd or even), N H W C < 2^31.
+// WIDE networks (the `wide` evaluation split of DeepNets-1M: up to 2048 channels in the last stage, 8192 into a cell's 1 x 1
+// preprocessing layer): a chain with max(C_in, C_out) > 512 runs as two nodes -- the depthwise stage alone (ghn3_dw_fwd / _bwd:
+// tnet_dw_fwd_kernel, C <= 16384) and the pointwise convolution + norm on the dense-convolution family, which takes C_out <= 4096,
+// C_in <= 16384 (its kernels split the columns over the grid and walk the reduction in chunks; tnet_bn_bwd_partial_kernel loops
+// over the channel quads above 1024 channels).  Squeeze-and-excitation takes C, J <= 4096 (se_pixel_sum loops above 1024).  At or
+// below the former widths (512 / 1024) every kernel takes the code path, launch geometry and summation order it had.
 // w_dw == nullptr (ks = 1): the same family as ReLU -> 1x1 convolution (stride) -> BatchNorm = `ReLUConvBN` with a 1x1 kernel,
 // the preprocessing layer of every cell and the `conv_1x1` op (ops.py:180-198): the depthwise stage degenerates to the ReLU.
 // Without a norm layer (ghn3_dwpw_plain_fwd / _bwd: the blocks of a network built with norm = None, ops.py:91-96, whose norm slots
@@ -383,7 +389,9 @@ __global__ __launch_bounds__(256) void tnet_bn_apply_kernel(const float* __restr
 // ---------------------------------------------------------------------------------------------------------------------
 // backward
 // ---------------------------------------------------------------------------------------------------------------------
-// per 64-pixel tile: part[tile][0][c] = sum dout, part[tile][1][c] = sum dout xhat        (C <= 1024)
+// per 64-pixel tile: part[tile][0][c] = sum dout, part[tile][1][c] = sum dout xhat.  Up to 256 channel quads (C <= 1024) the
+// threads are (quad) x (pixel group) and the groups are added through LDS; wider layers (launched without LDS) give every thread
+// the quads tid, tid + 256, ... over the tile's pixels in sequence and write the sums directly.
 __global__ __launch_bounds__(256) void tnet_bn_bwd_partial_kernel(const float* __restrict__ dout, const float* __restrict__ z,
                                                                   const float* __restrict__ stats, float* __restrict__ part,
                                                                   int P, int C) {
@@ -392,6 +400,21 @@ __global__ __launch_bounds__(256) void tnet_bn_bwd_partial_kernel(const float* _
     const int nq = C / 4, ng = max(1, 256 / nq);
     const int g = threadIdx.x / nq, q = threadIdx.x % nq, c = 4 * q;
     const int p0 = blockIdx.x * TP, p1 = min(P, p0 + TP);
+    if (nq > 256) {
+        for (int cw = 4 * threadIdx.x; cw < C; cw += 1024) {
+            f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = s1;
+            const f32x4 mu = *reinterpret_cast<const f32x4*>(stats + cw), rs = *reinterpret_cast<const f32x4*>(stats + C + cw);
+            for (int p = p0; p < p1; ++p) {
+                const f32x4 gd = *reinterpret_cast<const f32x4*>(dout + (int64_t)p * C + cw);
+                const f32x4 zz = *reinterpret_cast<const f32x4*>(z + (int64_t)p * C + cw);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { s1[e] += gd[e]; s2[e] += gd[e] * (zz[e] - mu[e]) * rs[e]; }
+            }
+            *reinterpret_cast<f32x4*>(part + (int64_t)blockIdx.x * 2 * C + cw) = s1;
+            *reinterpret_cast<f32x4*>(part + (int64_t)blockIdx.x * 2 * C + C + cw) = s2;
+        }
+        return;
+    }
     if (g < ng) {
         f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = s1;
         const f32x4 mu = *reinterpret_cast<const f32x4*>(stats + c), rs = *reinterpret_cast<const f32x4*>(stats + C + c);
@@ -591,13 +614,15 @@ __global__ __launch_bounds__(256) void tnet_dw_wgrad_kernel(const float* __restr
     // Threads = (channel quad) x (pixel lane): a thread sums its channels over every PL-th pixel of the chunk for up to TG taps at
     // a time (registers), the pixel lanes are then added through LDS.  (One (tap, channel quad) per
     // thread, walking the chunk's 128 pixels in sequence, keeps taps x C / 4 of the 256 threads busy: 108 us per call, 9 ms of
-    // the training loop's 75 ms of GPU time per step.)
+    // the training loop's 75 ms of GPU time per step.)  More than 256 channel quads (the stand-alone depthwise op of wide
+    // networks): slices of 256 quads on blockIdx.y, each of them the same scheme; one slice = the grid and the sums as before.
     constexpr int TG = 16;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     f32x4* red = reinterpret_cast<f32x4*>(smem);                               // [PL][TG][nq]
-    const int nq = d.C_in / 4, taps = d.ks * d.ks, PL = max(1, 256 / nq);
+    const int q0 = blockIdx.y * 256, nq = min(256, d.C_in / 4 - q0), taps = d.ks * d.ks, PL = max(1, 256 / nq);
     const int cq = threadIdx.x % nq, pl = threadIdx.x / nq;
     const bool live = pl < PL;
+    dy += 4 * q0; x += 4 * q0; part += 4 * q0;                                 // (this slice's first channel)
     const int pa = blockIdx.x * chunk_px, pb = min(P, pa + chunk_px);
     const int hw = d.Ho * d.Wo;
     for (int t0 = 0; t0 < taps; t0 += TG) {
@@ -834,7 +859,8 @@ int bn_param_grads(const float* dout, const float* z, const float* stats, float*
     const bool in_place = dgamma == dbeta + C;
     float* s12 = in_place ? dbeta : s12_scratch;
     const int nq = C / 4, ng = std::max(1, 256 / nq);
-    hipLaunchKernelGGL(tnet_bn_bwd_partial_kernel, dim3(n_tiles), dim3(256), (size_t)ng * 2 * C * 4, s, dout, z, stats, part12, P, C);
+    hipLaunchKernelGGL(tnet_bn_bwd_partial_kernel, dim3(n_tiles), dim3(256), nq > 256 ? 0 : (size_t)ng * 2 * C * 4, s, dout, z, stats,
+                       part12, P, C);
     TNET_LAUNCH_CHECK("bn bwd partial")
     hipLaunchKernelGGL(tnet_reduce_rows_kernel, dim3((2 * C / 4 + 15) / 16), dim3(256), 0, s, part12, n_tiles, (int64_t)2 * C, s12, 0, 0);
     TNET_LAUNCH_CHECK("bn bwd reduce")
@@ -846,16 +872,30 @@ int bn_param_grads(const float* dout, const float* z, const float* stats, float*
     return GHN3_OK;
 }
 
+// dW_dw [C_in][ks][ks] = sum over the output pixels of dy relu(x at the tap): per-chunk partials, then the fixed-order reduction
+// that also transposes (tap, channel) to the parameter's order.  LDS = [pixel lanes][16 taps][quads of a slice] float4.
+int dw_wgrad(const Desc& d, const Plan& pl, const float* dy, const float* x, float* part_dw, float* dw_dw, hipStream_t s) {
+    const int nq = d.C_in / 4, taps = d.ks * d.ks;
+    const size_t lds = nq > 256 ? (size_t)65536 : (size_t)std::max(1, 256 / nq) * 16 * nq * 16;
+    hipLaunchKernelGGL(tnet_dw_wgrad_kernel, dim3(pl.dw_chunks, (nq + 255) / 256), dim3(256), lds, s, dy, x, part_dw, d, pl.P,
+                       pl.dw_chunk_px);
+    TNET_LAUNCH_CHECK("dw wgrad")
+    const int64_t cols = (int64_t)taps * d.C_in;
+    hipLaunchKernelGGL(tnet_reduce_rows_kernel, dim3((int)((cols / 4 + 15) / 16)), dim3(256), 0, s, part_dw, pl.dw_chunks, cols, dw_dw,
+                       d.C_in, taps);
+    TNET_LAUNCH_CHECK("dw wgrad reduce")
+    return GHN3_OK;
+}
+
 // Steps 2 - 4 of the backward, shared by the family's three members (NORM_NONE: dz = dout; z, stats, gamma, s12 are null and not
 // read.  NORM_FROZEN: z and s12 are null and not read): dy = dz W_pw, dW_pw, dx and dW_dw.
 template <int NORM>
 int dwpw_bwd_products(const Desc& d, const Plan& pl, const float* dout, const float* z, const float* stats, const float* gamma,
                       const float* s12, const float* x, const float* w_dw, const float* w_pw, float* dx, float* dw_dw, float* dw_pw,
                       float* dy, float* part_pw, float* part_dw, hipStream_t s) {
-    const int taps = d.ks * d.ks;
+    int rc;
     // 2. dy = dz W_pw
     {
-        int rc;
         const int NT = nt_of(d.C_in);
         const size_t lds = bwd_lds(NT);
 #define BWD_CASE(n) case n: rc = tnet_raise_lds(tnet_dwpw_bwd_data_kernel<n, NORM>, lds); if (rc) return rc; \
@@ -880,14 +920,8 @@ int dwpw_bwd_products(const Desc& d, const Plan& pl, const float* dout, const fl
                            dx, d, total4);
         TNET_LAUNCH_CHECK("dw bwd data")
         if (w_dw) {
-            const int nq = d.C_in / 4;
-            hipLaunchKernelGGL(tnet_dw_wgrad_kernel, dim3(pl.dw_chunks), dim3(256), (size_t)std::max(1, 256 / nq) * 16 * nq * 16, s, dy, x,
-                               part_dw, d, pl.P, pl.dw_chunk_px);
-            TNET_LAUNCH_CHECK("dw wgrad")
-            const int64_t cols = (int64_t)taps * d.C_in;
-            hipLaunchKernelGGL(tnet_reduce_rows_kernel, dim3((int)((cols / 4 + 15) / 16)), dim3(256), 0, s, part_dw, pl.dw_chunks, cols,
-                               dw_dw, d.C_in, taps);
-            TNET_LAUNCH_CHECK("dw wgrad reduce")
+            rc = dw_wgrad(d, pl, dy, x, part_dw, dw_dw, s);
+            if (rc) return rc;
         }
     }
     return GHN3_OK;
@@ -1066,6 +1100,115 @@ extern "C" int ghn3_dwpw_frozen_bwd(const ghn3_dwpw_desc* g, const float* dout, 
     if (rc) return rc;
     return dwpw_bwd_products<NORM_FROZEN>(d, pl, dout, nullptr, stats, gamma, nullptr, x, w_dw, w_pw, dx, dw_dw, dw_pw, dy, part_pw,
                                           part_dw, s);
+}
+
+// ---- the depthwise stage ALONE: y = depthwise(relu(x)) -- the first of the two nodes a ReLU -> depthwise -> pointwise -> norm
+// chain runs as when it is wider than the fused kernels take (max(C_in, C_out) > 512: tnet_dwpw_fwd_kernel keeps all output columns
+// of a pixel tile in one workgroup's accumulators); the pointwise convolution and the norm then run on the dense-convolution
+// family, whose kernels split the columns over the grid.  Same descriptor with C_out == C_in; C a multiple of 4, C <= 16384.
+// Forward: one launch, no scratch.  Backward: dx (tnet_dw_bwd_data_kernel) and dW_dw (tnet_dw_wgrad_kernel + reduction) from
+// dout directly: 3 launches; scratch = the weight gradient's partials.
+namespace {
+
+constexpr int DW_MAX_C = 16384;
+constexpr int DW_CS = 128;       // channels per workgroup of the forward (32 quads x 8 pixel lanes)
+constexpr int DW_PX = 32;        // output pixels per workgroup
+
+// workgroup = (DW_PX output pixels, DW_CS channels): the slice's taps in LDS ([tap][channel], read as four floats), thread =
+// (channel quad, pixel lane): 16-byte loads, a wave reads 512 consecutive bytes of two pixels per tap; taps in (kh, kw) order.
+__global__ __launch_bounds__(256) void tnet_dw_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w_dw,
+                                                          float* __restrict__ y, const Desc d, const int P) {
+    __shared__ __attribute__((aligned(16))) float wt[MAXT * DW_CS];
+    const int c0 = blockIdx.y * DW_CS, nc = min(DW_CS, d.C_in - c0), taps = d.ks * d.ks;
+    for (int i = threadIdx.x; i < taps * DW_CS; i += 256) {
+        const int t = i / DW_CS, cc = i - t * DW_CS;
+        wt[i] = cc < nc ? w_dw[(int64_t)(c0 + cc) * taps + t] : 0.f;
+    }
+    __syncthreads();
+    const int cq = threadIdx.x & 31, pl = threadIdx.x >> 5;
+    if (4 * cq >= nc) return;
+    const int c = c0 + 4 * cq, hw = d.Ho * d.Wo;
+    const int pa = blockIdx.x * DW_PX, pb = min(P, pa + DW_PX);
+    for (int p = pa + pl; p < pb; p += 8) {
+        const int n = p / hw, r = p - n * hw, oh = r / d.Wo, ow = r - oh * d.Wo;
+        const int ih0 = oh * d.stride - d.pad, iw0 = ow * d.stride - d.pad;
+        const float* xn = x + (int64_t)n * d.H * d.W * d.C_in + c;
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        int t = 0;
+        for (int kh = 0; kh < d.ks; ++kh) {
+            const int ih = ih0 + kh * d.dil;
+            for (int kw = 0; kw < d.ks; ++kw, ++t) {
+                const int iw = iw0 + kw * d.dil;
+                if (ih < 0 || ih >= d.H || iw < 0 || iw >= d.W) continue;
+                const f32x4 v = *reinterpret_cast<const f32x4*>(xn + ((int64_t)ih * d.W + iw) * d.C_in);
+                const f32x4 wv = *reinterpret_cast<const f32x4*>(wt + t * DW_CS + 4 * cq);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[e] = fmaf(fmaxf(v[e], 0.f), wv[e], acc[e]);
+            }
+        }
+        *reinterpret_cast<f32x4*>(y + (int64_t)p * d.C_in + c) = acc;
+    }
+}
+
+// check_desc's rules with the width limit of the stand-alone op
+int check_dw_desc(const ghn3_dwpw_desc* g, Desc& d) {
+    if (!g) { ghn3_set_error("dw: null descriptor"); return GHN3_E_ARG; }
+    d = Desc{g->N, g->H, g->W, g->C_in, g->C_out, g->ks, g->stride, g->pad, g->dil, g->Ho, g->Wo, g->eps};
+    if (d.N <= 0 || d.H <= 0 || d.W <= 0 || d.C_in <= 0 || d.C_out != d.C_in || d.ks <= 0 || d.stride <= 0 || d.dil <= 0 || d.pad < 0) {
+        ghn3_set_error("dw: non-positive size in the descriptor, or C_out != C_in");
+        return GHN3_E_ARG;
+    }
+    if ((d.C_in & 3) || d.C_in > DW_MAX_C || d.ks > 7) {
+        ghn3_set_error("dw: needs C a multiple of 4 and <= %d, ks <= 7 (got %d, ks %d)", DW_MAX_C, d.C_in, d.ks);
+        return GHN3_E_LIMIT;
+    }
+    const int ho = (d.H + 2 * d.pad - d.dil * (d.ks - 1) - 1) / d.stride + 1, wo = (d.W + 2 * d.pad - d.dil * (d.ks - 1) - 1) / d.stride + 1;
+    if (ho != d.Ho || wo != d.Wo || ho <= 0 || wo <= 0) {
+        ghn3_set_error("dw: output size %d x %d does not match the convolution arithmetic (%d x %d)", d.Ho, d.Wo, ho, wo);
+        return GHN3_E_ARG;
+    }
+    if ((int64_t)d.N * d.H * d.W * d.C_in >= ((int64_t)1 << 31) || (int64_t)d.N * d.Ho * d.Wo * d.C_in >= ((int64_t)1 << 31)) {
+        ghn3_set_error("dw: activation tensors of 2^31 elements or more are not supported");
+        return GHN3_E_LIMIT;
+    }
+    return GHN3_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t ghn3_dw_scratch_floats(const ghn3_dwpw_desc* g, int backward) {
+    Desc d;
+    const int rc = check_dw_desc(g, d);
+    if (rc) return rc;
+    if (!backward) return 0;
+    return (int64_t)make_plan(d).dw_chunks * d.ks * d.ks * d.C_in + 256;
+}
+
+extern "C" int ghn3_dw_fwd(const ghn3_dwpw_desc* g, const float* x, const float* w_dw, float* y, void* stream_) {
+    Desc d;
+    const int rc = check_dw_desc(g, d);
+    if (rc) return rc;
+    if (!x || !w_dw || !y) { ghn3_set_error("dw fwd: null pointer"); return GHN3_E_ARG; }
+    const int P = d.N * d.Ho * d.Wo;
+    hipLaunchKernelGGL(tnet_dw_fwd_kernel, dim3((P + DW_PX - 1) / DW_PX, (d.C_in + DW_CS - 1) / DW_CS), dim3(256), 0, (hipStream_t)stream_,
+                       x, w_dw, y, d, P);
+    TNET_LAUNCH_CHECK("dw fwd")
+    return GHN3_OK;
+}
+
+extern "C" int ghn3_dw_bwd(const ghn3_dwpw_desc* g, const float* dout, const float* x, const float* w_dw, float* dx, float* dw_dw,
+                           float* scratch, void* stream_) {
+    Desc d;
+    const int rc = check_dw_desc(g, d);
+    if (rc) return rc;
+    if (!dout || !x || !w_dw || !dx || !dw_dw || !scratch) { ghn3_set_error("dw bwd: null pointer"); return GHN3_E_ARG; }
+    hipStream_t s = (hipStream_t)stream_;
+    const Plan pl = make_plan(d);
+    const int64_t total4 = (int64_t)d.N * d.H * d.W * d.C_in / 4;
+    hipLaunchKernelGGL(tnet_dw_bwd_data_kernel, dim3((int)std::min<int64_t>((total4 + 255) / 256, 8192)), dim3(256), 0, s, dout, x, w_dw, dx,
+                       d, total4);
+    TNET_LAUNCH_CHECK("dw bwd data")
+    return dw_wgrad(d, pl, dout, x, scratch, dw_dw, s);
 }
 
 // ---- dense convolution family: the forward / input-gradient kernel and the host side -------------------------------------------
@@ -1316,6 +1459,8 @@ __global__ __launch_bounds__(256) void tnet_conv2_kernel(const float* __restrict
     }
 }
 
+constexpr int CONV_MAX_IN = 16384, CONV_MAX_OUT = 4096;
+
 struct CPlan { int P, P_in, n_tiles, n_tiles_in, w_chunks, w_chunk_px, taps; };
 
 CPlan make_cplan(const CDesc& d) {
@@ -1342,10 +1487,16 @@ int check_cdesc(const ghn3_conv_desc* g, CDesc& d) {
         ghn3_set_error("conv: non-positive size in the descriptor");
         return GHN3_E_ARG;
     }
-    // (tnet_conv2_kernel walks C_in in chunks and splits it over blockIdx.y in the backward: wide inputs are fine)
-    if ((d.C_in & 3) || (d.C_out & 3) || d.C_in > 4096 || d.C_out > 512 || d.kh > 7 || d.kw > 7) {
-        ghn3_set_error("conv: needs C_in, C_out multiples of 4, C_out <= 512, C_in <= 4096, kernel <= 7 x 7 (got %d -> %d, %d x %d)",
-                       d.C_in, d.C_out, d.kh, d.kw);
+    // (tnet_conv2_kernel walks the reduction in chunks and splits the columns over blockIdx.y in both directions, the weight
+    // gradient tiles both sides over the grid, the norm kernels loop over the channels: wide layers are fine)
+    if ((d.C_in & 3) || (d.C_out & 3) || d.C_in > CONV_MAX_IN || d.C_out > CONV_MAX_OUT || d.kh > 7 || d.kw > 7) {
+        ghn3_set_error("conv: needs C_in, C_out multiples of 4, C_out <= %d, C_in <= %d, kernel <= 7 x 7 (got %d -> %d, %d x %d)",
+                       CONV_MAX_OUT, CONV_MAX_IN, d.C_in, d.C_out, d.kh, d.kw);
+        return GHN3_E_LIMIT;
+    }
+    // (the weight gradient's reduction runs four threads per weight on a one-dimensional grid)
+    if ((int64_t)d.kh * d.kw * d.C_out * d.C_in >= ((int64_t)1 << 30)) {
+        ghn3_set_error("conv: weight tensors of 2^30 elements or more are not supported");
         return GHN3_E_LIMIT;
     }
     const int ho = (d.H + 2 * d.ph - d.dil * (d.kh - 1) - 1) / d.sh + 1, wo = (d.W + 2 * d.pw - d.dil * (d.kw - 1) - 1) / d.sw + 1;
@@ -1428,7 +1579,8 @@ int conv_bwd_products(const CDesc& d, const CPlan& pl, const CScratch& sc, const
 
 extern "C" int64_t ghn3_conv_scratch_floats(const ghn3_conv_desc* g, int backward) {
     CDesc d;
-    if (check_cdesc(g, d)) return -1;
+    const int rc = check_cdesc(g, d);
+    if (rc) return rc;                                            // GHN3_E_ARG / GHN3_E_LIMIT
     return conv_scratch(d, make_cplan(d), backward != 0).total;
 }
 
@@ -1506,7 +1658,8 @@ extern "C" int ghn3_conv_bn_bwd(const ghn3_conv_desc* g, const float* dout, cons
 // Scratch: forward = the weight pack; backward = that of ghn3_conv_bn_bwd followed by the (mean, rstd) pair.
 extern "C" int64_t ghn3_conv_frozen_scratch_floats(const ghn3_conv_desc* g, int backward) {
     CDesc d;
-    if (check_cdesc(g, d)) return -1;
+    const int rc = check_cdesc(g, d);
+    if (rc) return rc;
     const CPlan pl = make_cplan(d);
     if (!backward) return pack_floats(pl.taps, d.C_out, d.C_in) + 64;
     return conv_scratch(d, pl, true).total + 2 * d.C_out;
@@ -1584,6 +1737,27 @@ __device__ __forceinline__ float hswish_grad(float a) { return a < -3.f ? 0.f : 
 __device__ __forceinline__ void se_pixel_sum(const float* __restrict__ a, const float* __restrict__ b, int HW, int C, f32x4* red,
                                              float* out, float scale) {
     const int nq = C / 4, PL = max(1, 256 / nq), cq = threadIdx.x % nq, pl = threadIdx.x / nq;
+    if (nq > 256) {
+        // more quads than threads (C > 1024): a thread takes the quads tid, tid + 256, ... over the pixels in sequence; `red` unused
+        for (int q = threadIdx.x; q < nq; q += 256) {
+            f32x4 sum = {0.f, 0.f, 0.f, 0.f};
+            for (int p = 0; p < HW; ++p) {
+                const f32x4 u = *reinterpret_cast<const f32x4*>(a + (int64_t)p * C + 4 * q);
+                if (b) {
+                    const f32x4 v = *reinterpret_cast<const f32x4*>(b + (int64_t)p * C + 4 * q);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) sum[e] = fmaf(u[e], v[e], sum[e]);
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) sum[e] += u[e];
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) out[4 * q + e] = sum[e] * scale;
+        }
+        __syncthreads();
+        return;
+    }
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     if (pl < PL) {
         for (int p = pl; p < HW; p += PL) {
@@ -1739,8 +1913,8 @@ __global__ __launch_bounds__(256) void tnet_se_wgrad_kernel(const float* __restr
 
 int check_se(int N, int HW, int C, int J) {
     if (N <= 0 || HW <= 0 || C <= 0 || J <= 0) { ghn3_set_error("se: non-positive size"); return GHN3_E_ARG; }
-    if ((C & 3) || C > 1024 || J > 1024 || (int64_t)N * HW * C >= ((int64_t)1 << 31)) {
-        ghn3_set_error("se: needs C a multiple of 4, C, J <= 1024 and fewer than 2^31 activations (got C = %d, J = %d)", C, J);
+    if ((C & 3) || C > 4096 || J > 4096 || (int64_t)N * HW * C >= ((int64_t)1 << 31)) {
+        ghn3_set_error("se: needs C a multiple of 4, C, J <= 4096 and fewer than 2^31 activations (got C = %d, J = %d)", C, J);
         return GHN3_E_LIMIT;
     }
     return GHN3_OK;
@@ -1753,8 +1927,10 @@ extern "C" int ghn3_se_fwd(int N, int HW, int C, int J, const float* x, const fl
     int rc = check_se(N, HW, C, J);
     if (rc) return rc;
     if (!x || !w1 || !b1 || !w2 || !b2 || !y || !save) { ghn3_set_error("se fwd: null pointer"); return GHN3_E_ARG; }
-    hipLaunchKernelGGL(tnet_se_fwd_kernel, dim3(N), dim3(256), (size_t)4096 + (2 * C + J) * 4, (hipStream_t)stream_, x, w1, b1, w2, b2, y, save,
-                       HW, C, J);
+    const size_t lds = (size_t)4096 + (size_t)(2 * C + J) * 4;    // (52 KB at the widest layer)
+    rc = tnet_raise_lds(tnet_se_fwd_kernel, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL(tnet_se_fwd_kernel, dim3(N), dim3(256), lds, (hipStream_t)stream_, x, w1, b1, w2, b2, y, save, HW, C, J);
     TNET_LAUNCH_CHECK("se fwd")
     return GHN3_OK;
 }
@@ -1768,7 +1944,10 @@ extern "C" int ghn3_se_bwd(int N, int HW, int C, int J, const float* dy, const f
         return GHN3_E_ARG;
     }
     hipStream_t s = (hipStream_t)stream_;
-    hipLaunchKernelGGL(tnet_se_bwd_kernel, dim3(N), dim3(256), (size_t)4096 + (2 * C + J) * 4, s, dy, x, w1, w2, save, dx, scratch, HW, C, J);
+    const size_t lds = (size_t)4096 + (size_t)(2 * C + J) * 4;
+    rc = tnet_raise_lds(tnet_se_bwd_kernel, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL(tnet_se_bwd_kernel, dim3(N), dim3(256), lds, s, dy, x, w1, w2, save, dx, scratch, HW, C, J);
     TNET_LAUNCH_CHECK("se bwd")
     const int64_t total = (int64_t)2 * C * J + C + J;
     hipLaunchKernelGGL(tnet_se_wgrad_kernel, dim3((int)std::min<int64_t>((total + 255) / 256, 4096)), dim3(256), 0, s, scratch, save, dw1, db1, dw2,

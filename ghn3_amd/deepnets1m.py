@@ -59,10 +59,12 @@ def sample_genotype(rng, vit=False, max_steps=4):
     return ops.Genotype(normal=normal, normal_concat=n_cat, reduce=reduce, reduce_concat=r_cat)
 
 
-def sample_net_args(rng, large_images=False, bn_free_prob=0.0):
+def sample_net_args(rng, large_images=False, bn_free_prob=0.0, width_mult=1):
     """Network keyword arguments in the ranges the DeepNets-1M loader uses (deepnets1m.py:96-143).  With probability
     `bn_free_prob` the network has no norm layers (norm=None, the BN-Free networks of DeepNets-1M); the draw is the last one and
-    is made only when the probability is positive, so the default stream is the one it always was."""
+    is made only when the probability is positive, so the default stream is the one it always was.  `width_mult` multiplies the
+    drawn `C` (4 on CIFAR-sized and 2 on ImageNet-sized inputs is what the `wide` evaluation split of DeepNets-1M does,
+    deepnets1m_io.item_net_args); it makes no random draw and changes nothing else."""
     vit = rng.rand() < 0.1
     genotype = sample_genotype(rng, vit=vit, max_steps=1 if vit else 4)
     steps = len(genotype.normal_concat)
@@ -79,6 +81,8 @@ def sample_net_args(rng, large_images=False, bn_free_prob=0.0):
     args['num_classes'] = 1000 if large_images else 10
     if bn_free_prob > 0 and rng.rand() < bn_free_prob:
         args['norm'] = None
+    if width_mult != 1:
+        args['C'] = int(args['C']) * int(width_mult)
     return args
 
 
@@ -86,9 +90,9 @@ class SampledNets:
     """A virtual dataset of architectures: ``self[i]`` is a Graph with ``.net`` (a NetworkLight) and ``.net_args``."""
 
     def __init__(self, num_nets=10 ** 6, large_images=False, seed=0, virtual_edges=50, max_nodes=1000, light=True,
-                 verbose=False, bn_free_prob=0.0):
+                 verbose=False, bn_free_prob=0.0, width_mult=1):
         self.num_nets, self.large_images, self.seed = int(num_nets), large_images, int(seed)
-        self.bn_free_prob = float(bn_free_prob)
+        self.bn_free_prob, self.width_mult = float(bn_free_prob), int(width_mult)
         self.virtual_edges, self.max_nodes, self.light, self.verbose = virtual_edges, max_nodes, light, verbose
 
     def __len__(self):
@@ -98,7 +102,7 @@ class SampledNets:
         idx = int(idx) % self.num_nets
         for attempt in range(64):
             rng = np.random.RandomState((self.seed * 1000003 + idx * 64 + attempt) % (2 ** 31 - 1))
-            args = sample_net_args(rng, self.large_images, self.bn_free_prob)
+            args = sample_net_args(rng, self.large_images, self.bn_free_prob, self.width_mult)
             try:
                 model = ops.Network(**args)
                 graph = Graph(model, ve_cutoff=self.virtual_edges, verbose=False)
@@ -162,7 +166,7 @@ class DeepNets1MDDP(SampledNets, torch.utils.data.Dataset):
 
     def __init__(self, split='train', nets_dir=None, virtual_edges=50, num_nets=None, large_images=False, dense=True,
                  wider_nets=True, debug=False, verbose=False, seed=None, max_nodes=1000, light=True, arch=None, bn_free_prob=0.0,
-                 **unused):
+                 width_mult=1, **unused):
         assert dense, 'GHN-3 uses the dense layout'
         self.split, self.is_train, self.dense, self.wider_nets, self.debug = split, split == 'train', dense, wider_nets, debug
         self.store = None
@@ -192,13 +196,15 @@ class DeepNets1MDDP(SampledNets, torch.utils.data.Dataset):
             self.num_nets, self.large_images, self.virtual_edges = len(self.nets), large_images, virtual_edges
             self.light, self.verbose, self.max_nodes, self.seed = light, verbose, max_nodes, 0
             self.bn_free_prob = 0.0                             # (the files carry each network's own `norm`)
+            self.width_mult = 1                                 # (... and the split decides the width: item_net_args)
             return
         if seed is None:                                        # disjoint streams per split
             seed = {'train': 0, 'val': 1, 'test': 2}.get(split, 3)
         if num_nets is None:
             num_nets = 10 ** 6 if self.is_train else 500
         SampledNets.__init__(self, num_nets=num_nets, large_images=large_images, seed=seed, virtual_edges=virtual_edges,
-                             max_nodes=max_nodes, light=light, verbose=verbose, bn_free_prob=bn_free_prob)
+                             max_nodes=max_nodes, light=light, verbose=verbose, bn_free_prob=bn_free_prob,
+                             width_mult=width_mult)
 
     def __len__(self):
         return self.num_nets if self.store is None or self.h5_idx is None else len(self.h5_idx)

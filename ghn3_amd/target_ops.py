@@ -23,9 +23,17 @@ norm='bn-track') is a per-channel affine map with constants known before the lau
 same runners (``_frozen_norm``; GHN3_NATIVE_EVALBN=0 keeps such blocks on the stock layers).  The running statistics are read
 only: they take no gradient and are never written.
 
+WIDE networks (the `wide` evaluation split of DeepNets-1M: up to 2048 channels in the last stage, 8192 into a cell's 1 x 1
+preprocessing layer): the fused depthwise + pointwise kernels keep all output columns of a pixel tile in one workgroup and stop at
+512 channels, so a chain with max(C_in, C_out) > 512 runs as TWO nodes -- ``Depthwise`` / ``depthwise_relu`` (ghn3_dw_fwd / _bwd:
+ReLU + depthwise taps alone, C <= 16384) and the 1 x 1 member of the dense-convolution family that fits the norm slot (``ConvBn``,
+``ConvOnly``, ``ConvBnEval`` with relu=False), which takes C_out <= 4096 and C_in <= 16384; ``SqueezeExcite`` takes C, J <= 4096.
+GHN3_NATIVE_WIDE=0 keeps every layer above the former limits (512 / 4096 -> 512 / 1024) on the stock layers.  The ``msa`` layers
+keep their limits (C <= 256, head dim <= 32): a wide ViT-style network runs them on the stock path.
+
 ``DwPwBn.applicable`` states what the kernels take (fp32 CUDA tensors, batch statistics, C <= 512, ks <= 7); a layer
-outside of it keeps the stock path.  There is no CPU implementation: on a CPU tensor the stock path runs (the target
-networks themselves are torch modules), and ``dwpw_bn`` raises without the library.
+outside of it goes to the two-node form above or keeps the stock path.  There is no CPU implementation: on a CPU tensor the
+stock path runs (the target networks themselves are torch modules), and ``dwpw_bn`` raises without the library.
 """
 
 import ctypes
@@ -133,6 +141,12 @@ def _frozen_norm(batch_stats):
 def _frozen_stats_ok(running_mean, running_var, C_out):
     return all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.numel() == C_out
                for t in (running_mean, running_var))
+
+
+def _wide():
+    """Asked only for a layer wider than the limits the native layers had before they took wide networks: GHN3_NATIVE_WIDE=0
+    keeps such a layer on the stock path (that behaviour, for A/B measurements)."""
+    return os.environ.get('GHN3_NATIVE_WIDE', '1') != '0'
 
 
 def _wants_grad(*tensors):
@@ -341,6 +355,64 @@ def dwpw_bn_eval(x, w_dw, w_pw, gamma, beta, running_mean, running_var, stride=1
                             int(padding), int(dilation), float(eps), _wants_grad(x, w_dw, w_pw, gamma, beta))
 
 
+class Depthwise(torch.autograd.Function):
+    """y = depthwise_conv(relu(x)) as ONE autograd node on ghn3_dw_fwd / _bwd: the first node of a ReLU -> depthwise ->
+    pointwise -> norm chain that is wider than DwPwBn / DwPw / DwPwBnEval take (the second one is a 1 x 1 member of the
+    dense-convolution family).  Same conventions as DwPw: channels_last storage inside, w_dw (C, 1, ks, ks) read in place;
+    only x (and the weight) is saved."""
+
+    @staticmethod
+    def applicable(x, w_dw, stride, pad, dil):
+        if not (enabled() and torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
+            return False
+        if _autocast_excludes():
+            return False
+        if not (torch.is_tensor(w_dw) and w_dw.is_cuda and w_dw.dtype == torch.float32 and w_dw.dim() == 4):
+            return False
+        C, ks = x.shape[1], w_dw.shape[-1]
+        if not (C % 4 == 0 and C <= DW_MAX and ks <= 7 and tuple(w_dw.shape) == (C, 1, ks, ks) and stride > 0 and dil > 0 and
+                pad >= 0 and x.numel() < 2 ** 31):
+            return False
+        d = _desc(x, C, ks, stride, pad, dil, 0.0)
+        return d.Ho > 0 and d.Wo > 0 and d.N * d.Ho * d.Wo * C < 2 ** 31
+
+    @staticmethod
+    def forward(ctx, x, w_dw, stride, pad, dil):
+        lib = L.load()
+        xc = x.contiguous(memory_format=torch.channels_last)
+        wd = w_dw.contiguous()
+        d = _desc(xc, int(xc.shape[1]), int(wd.shape[-1]), stride, pad, dil, 0.0)
+        y = torch.empty((d.N, d.C_in, d.Ho, d.Wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+        L._check(lib.ghn3_dw_fwd(ctypes.byref(d), _ptr(xc), _ptr(wd), _ptr(y), _stream()), 'ghn3_dw_fwd')
+        ctx.save_for_backward(xc, wd)
+        ctx.cfg = (stride, pad, dil)
+        return y
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = L.load()
+        xc, wd = ctx.saved_tensors
+        stride, pad, dil = ctx.cfg
+        d = _desc(xc, int(xc.shape[1]), int(wd.shape[-1]), stride, pad, dil, 0.0)
+        do = dout.contiguous(memory_format=torch.channels_last)
+        dx = torch.empty_like(xc)
+        # (one allocation for the weight gradient and the scratch area, as DwPw)
+        n_par = (wd.numel() + 63) // 64 * 64
+        buf = torch.empty(n_par + _scratch_floats('ghn3_dw_scratch_floats', d, 1), dtype=torch.float32, device=xc.device)
+        dwd = buf[:wd.numel()].view(wd.shape)
+        L._check(lib.ghn3_dw_bwd(ctypes.byref(d), _ptr(do), _ptr(xc), _ptr(wd), _ptr(dx), _ptr(dwd), _ptr(buf[n_par:]), _stream()),
+                 'ghn3_dw_bwd')
+        return dx, dwd, None, None, None
+
+
+def depthwise_relu(x, w_dw, stride=1, padding=0, dilation=1):
+    """depthwise_conv(relu(x)): x (N, C, H, W) fp32 CUDA tensor (channels_last preferred), w_dw (C, 1, ks, ks); the result is a
+    channels_last tensor."""
+    if not x.is_cuda:
+        raise L.Ghn3Error('depthwise_relu runs on an MI355X only (no CPU implementation: use the stock torch layers)')
+    return Depthwise.apply(x, w_dw, int(stride), int(padding), int(dilation))
+
+
 class _ConvDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ('N', 'H', 'W', 'C_in', 'C_out', 'kh', 'kw', 'stride_h', 'stride_w', 'pad_h', 'pad_w',
                                               'dil', 'Ho', 'Wo', 'relu')] + [('eps', ctypes.c_float)]
@@ -351,7 +423,12 @@ def _pair(v):
 
 
 CONV_NO_NORM = 2                  # include/ghn3_hip.h GHN3_CONV_NO_NORM
-CONV_MAX_IN = 4096                # widest input of the dense-convolution op (the kernels walk C_in in chunks)
+CONV_MAX_IN = 16384               # widest input of the dense-convolution op (the kernels walk C_in in chunks)
+CONV_MAX_OUT = 4096               # widest output (the kernels split the columns over the grid)
+CONV_NARROW = (4096, 512)         # (C_in, C_out) the op took before wide networks: beyond them GHN3_NATIVE_WIDE decides
+DWPW_MAX = 512                    # widest side of the fused depthwise + pointwise kernels
+DW_MAX = 16384                    # widest stand-alone depthwise op
+SE_MAX, SE_NARROW = 4096, 1024    # squeeze-and-excitation: C and J
 
 
 def _conv_applicable(x, w):
@@ -363,8 +440,10 @@ def _conv_applicable(x, w):
     if not (torch.is_tensor(w) and w.is_cuda and w.dtype == torch.float32 and w.dim() == 4):
         return False
     C_in, C_out = x.shape[1], w.shape[0]
-    return C_in % 4 == 0 and C_out % 4 == 0 and C_in <= CONV_MAX_IN and C_out <= 512 and w.shape[1] == C_in and \
-        max(w.shape[2], w.shape[3]) <= 7 and x.numel() < 2 ** 31
+    if not (C_in % 4 == 0 and C_out % 4 == 0 and C_in <= CONV_MAX_IN and C_out <= CONV_MAX_OUT and w.shape[1] == C_in and
+            max(w.shape[2], w.shape[3]) <= 7 and x.numel() < 2 ** 31 and w.numel() < 2 ** 30):
+        return False
+    return (C_in <= CONV_NARROW[0] and C_out <= CONV_NARROW[1]) or _wide()
 
 
 def _conv_desc(x, w, stride, pad, dil, relu, eps, no_norm=False):
@@ -562,8 +641,10 @@ class SqueezeExcite(torch.autograd.Function):
         if not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in (w1, b1, w2, b2)):
             return False
         C, J = x.shape[1], w1.shape[0]
-        return C % 4 == 0 and C <= 1024 and J <= 1024 and tuple(w1.shape) == (J, C) and tuple(w2.shape) == (C, J) and \
-            b1.numel() == J and b2.numel() == C and x.numel() < 2 ** 31
+        if not (C % 4 == 0 and C <= SE_MAX and J <= SE_MAX and tuple(w1.shape) == (J, C) and tuple(w2.shape) == (C, J) and
+                b1.numel() == J and b2.numel() == C and x.numel() < 2 ** 31):
+            return False
+        return max(C, J) <= SE_NARROW or _wide()
 
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2):
@@ -893,7 +974,8 @@ def run_pointwise_block(layers, x, keep_layout=False):
         return _hand_on(out, keep_layout, pw, bn)
     ok = hasattr(bn, 'eps') and layer_ok and DwPwBn.applicable(x, None, w_pw, gamma, beta, 1, batch_stats)
     if not ok:
-        # (e.g. more than 512 input channels -- the concatenated states of a wide cell: the dense-convolution op takes those)
+        # (more than 512 channels on either side -- the concatenated states of a cell, the layers of a wide network: the
+        # dense-convolution op takes those)
         return run_conv_block(layers, x, keep_layout)
     out, stats = dwpw_bn(x, None, w_pw, gamma, beta, pw.stride[0], 0, 1, bn.eps)
     _update_running_stats(bn, stats, out, has_run)
@@ -922,6 +1004,40 @@ def reference(x, w_dw, w_pw, gamma, beta, stride=1, padding=0, dilation=1, eps=1
     y = F.conv2d(F.relu(x), w_dw, None, stride, padding, dilation, groups=x.shape[1])
     zz = F.conv2d(y, w_pw.reshape(w_pw.shape[0], -1, 1, 1))
     return F.batch_norm(zz, None, None, gamma, beta, True, 0.1, eps)
+
+
+def _run_wide_block(layers, x, keep_layout):
+    """[ReLU, depthwise Conv2d, pointwise Conv2d, norm] wider than the fused depthwise + pointwise kernels take, as two nodes:
+    Depthwise, then the 1 x 1 member of the dense-convolution family that fits the norm slot, without a ReLU; the intermediate
+    stays NHWC.  None when one of the two does not apply (the caller keeps the stock layers).  The caller has checked the
+    layers' attributes (`layers_ok` of run_block)."""
+    relu, dw, pw, bn = layers
+    w_dw, w_pw = getattr(dw, 'weight', None), getattr(pw, 'weight', None)
+    if not (torch.is_tensor(x) and x.dim() == 4 and torch.is_tensor(w_pw) and w_pw.dim() == 4 and _plain_conv(pw) and
+            max(x.shape[1], w_pw.shape[0]) > DWPW_MAX and _wide()):
+        return None
+    stride, pad, dil = int(dw.stride[0]), int(dw.padding[0]), int(dw.dilation[0])
+    if not Depthwise.applicable(x, w_dw, stride, pad, dil):
+        return None
+    gamma, beta, has_run, batch_stats = _norm_inputs(bn)
+    d = _desc(x, x.shape[1], w_dw.shape[-1], stride, pad, dil, 0.0)
+    probe = x.new_empty(1).expand(d.N, d.C_in, d.Ho, d.Wo)        # (the second node's input: one element, no storage of that size)
+    if _no_norm(bn):
+        if not ConvOnly.applicable(probe, w_pw):
+            return None
+        out = conv_only(depthwise_relu(x, w_dw, stride, pad, dil), w_pw, 1, 0, 1, relu=False)
+    elif _frozen_norm(batch_stats):
+        if not (hasattr(bn, 'eps') and ConvBnEval.applicable(probe, w_pw, gamma, beta, bn.running_mean, bn.running_var, 1, 0, 1)):
+            return None
+        out = conv_bn_eval(depthwise_relu(x, w_dw, stride, pad, dil), w_pw, gamma, beta, bn.running_mean, bn.running_var, 1, 0, 1,
+                           False, bn.eps)
+    else:
+        if not (hasattr(bn, 'eps') and ConvBn.applicable(probe, w_pw, gamma, beta, batch_stats) and
+                conv_desc_fits(_conv_desc(probe, w_pw, 1, 0, 1, False, 0.0))):
+            return None
+        out, stats = conv_bn(depthwise_relu(x, w_dw, stride, pad, dil), w_pw, gamma, beta, 1, 0, 1, False, bn.eps)
+        _update_running_stats(bn, stats, out, has_run)
+    return _hand_on(out, keep_layout, dw, pw, bn)
 
 
 def run_block(layers, x, keep_layout=False):
@@ -955,6 +1071,9 @@ def run_block(layers, x, keep_layout=False):
         return _hand_on(out, keep_layout, dw, pw, bn)
     ok = hasattr(bn, 'eps') and layers_ok and DwPwBn.applicable(x, w_dw, w_pw, gamma, beta, ks, batch_stats)
     if not ok:
+        out = _run_wide_block(layers, x, keep_layout) if layers_ok else None   # (wider than the fused kernels: two nodes)
+        if out is not None:
+            return out
         for m in layers:
             x = m(x)
         return x

@@ -590,14 +590,33 @@ int ghn3_dwpw_frozen_bwd(const ghn3_dwpw_desc* desc, const float* dout, const fl
                          const float* w_pw, const float* gamma, const float* mean, const float* var, float* dx, float* dw_dw,
                          float* dw_pw, float* dgamma, float* dbeta, float* scratch, void* stream);
 
+/* The depthwise stage ALONE, for chains wider than the fused kernels take (max(C_in, C_out) > 512; the `wide` split of
+ * DeepNets-1M):  y = depthwise(relu(x)),  x [N][H][W][C], y / dout [N][Ho][Wo][C] NHWC fp32, w_dw [C][ks][ks] read in place.
+ * The caller runs the pointwise convolution and the norm as a 1 x 1 member of the dense-convolution family below (relu = 0).
+ * Same descriptor with C_out == C_in (GHN3_E_ARG otherwise; `eps` ignored).  Limits (GHN3_E_LIMIT): C a multiple of 4 and
+ * <= 16384, ks <= 7, N H W C and N Ho Wo C below 2^31.  Added without an ABI version step (symbols only).
+ * Forward: ONE launch, no scratch.  Backward: dx = 1[x > 0] . transposed taps of dout, dw_dw [C][ks][ks] from per-chunk partial
+ * sums reduced in a fixed order: 3 launches.  No float atomics, no allocation, no synchronisation inside.  Deterministic.
+ * ghn3_dw_scratch_floats: 0 for the forward; backward = chunks ks ks C + 256 with P = N Ho Wo,
+ * chunks = ceil(P / px), px = clamp(round_up_16(ceil(P / 256)), 16, 128); a negative GHN3_E_* code for a descriptor the op does
+ * not take. */
+int64_t ghn3_dw_scratch_floats(const ghn3_dwpw_desc* desc, int backward);
+int ghn3_dw_fwd(const ghn3_dwpw_desc* desc, const float* x, const float* w_dw, float* y, void* stream);
+int ghn3_dw_bwd(const ghn3_dwpw_desc* desc, const float* dout, const float* x, const float* w_dw, float* dx, float* dw_dw,
+                float* scratch, void* stream);
 
 /* ---- target-network layers, second slice (ABI v19, round 6): [ReLU ->] dense kh x kw convolution -> BatchNorm -------------
  * `ReLUConvBN` with a k x k kernel and its 1 x k / k x 1 halves (/root/reference/ghn3/ops.py:180-198; the `conv_3x3 / 5x5 /
  * 7x7` ops of the DeepNets-1M search space, ops.py:297), forward and backward, NHWC fp32 activations, batch statistics.
  * w [C_out][C_in][kh][kw] is the view of the GHN's flat prediction buffer (read in place; dw is written in the same order),
  * z / out [N Ho Wo][C_out], stats [3 C_out] as for ghn3_dwpw_bn_fwd; relu != 0 applies ReLU to x first (and its mask to dx).
- * Limits (GHN3_E_LIMIT: the caller keeps its stock path): C_in, C_out multiples of 4, C_out <= 512, C_in <= 4096, kernel <= 7 x 7.
- * Deterministic (fixed-order partial sums).
+ * Limits (GHN3_E_LIMIT: the caller keeps its stock path): C_in, C_out multiples of 4, C_out <= 4096, C_in <= 16384, kernel <= 7 x 7,
+ * fewer than 2^30 weights, N H W max(C_in, C_out) and N Ho Wo max(C_in, C_out) below 2^31.  Deterministic (fixed-order partial sums).
+ * `scratch` = ghn3_conv_scratch_floats(desc, backward) floats (a negative GHN3_E_* code for a descriptor the op does not take), with
+ * P = N Ho Wo, tiles = ceil(P / 64), taps = kh kw, pack(rows, k) = round_up_4(ceil(3 taps rows round_up_32(k) / 2)) and
+ * chunks = ceil(P / (32 ceil(ceil(P / n) / 32))) where n = clamp(ceil(768 / (ceil(C_out / 64) ceil(C_in / 64) taps)), 1, ceil(P / 32)):
+ *   forward   2 tiles C_out + pack(C_out, C_in) + 64
+ *   backward  2 tiles C_out + 2 C_out + pack(C_in, C_out) + chunks taps C_out C_in + P C_out + 256
  * relu | GHN3_CONV_NO_NORM: the convolution alone (the first half of the 1 x k / k x 1 pair of ops.py:186-190, which has no norm
  * layer of its own): the forward writes its result to `z` and stops (gamma, beta, out, stats may be NULL); the backward takes
  * `dout` as the gradient of that result and writes dx and dw only (z, stats, gamma, dgamma, dbeta may be NULL). */
@@ -634,7 +653,8 @@ int ghn3_conv_frozen_bwd(const ghn3_conv_desc* desc, const float* dout, const fl
  * x, y, dy, dx [N][HW][C] fp32 (NHWC); w1 [J][C], b1 [J], w2 [C][J], b2 [C] (the Linear layers' own layouts, read in place);
  * save [N][2 C + J] = (s | a | h) written by the forward for the backward; scratch [N][C + J] floats.
  * One workgroup per sample forward, the same + one parameter-gradient launch backward; fixed summation orders.
- * Limits (GHN3_E_LIMIT): C a multiple of 4, C and J <= 1024. */
+ * Limits (GHN3_E_LIMIT): C a multiple of 4, C and J <= 4096 (up to 1024 channels a sample's pixel sums run on (quad, pixel lane)
+ * threads; above, every thread walks its quads over the pixels in sequence). */
 int ghn3_se_fwd(int N, int HW, int C, int J, const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
                 float* y, float* save, void* stream);
 int ghn3_se_bwd(int N, int HW, int C, int J, const float* dy, const float* x, const float* w1, const float* w2, const float* save,

@@ -1,7 +1,8 @@
 """Diagnostic: which layers of the training loop's target networks still run on stock ATen / MIOpen kernels?
 Runs Trainer.update on the architecture stream of examples/train_ghn_ddp.py and counts, per step, the stock Conv2d / BatchNorm2d /
 Linear / pooling calls and F.cross_entropy calls by configuration and by the module class that issued them.
---bn-free-prob P: the share of the stream drawn without norm layers (norm=None), as in examples/train_ghn_ddp.py."""
+--bn-free-prob P: the share of the stream drawn without norm layers (norm=None), as in examples/train_ghn_ddp.py.
+--width-mult M: multiplies the drawn width C of every architecture (4: the widths of the `wide` evaluation split)."""
 import argparse
 import collections
 import inspect
@@ -19,7 +20,8 @@ from ghn3_amd.graph import GraphBatch
 STEPS = int(os.environ.get('CENSUS_STEPS', '12'))
 _ap = argparse.ArgumentParser()
 _ap.add_argument('--bn-free-prob', type=float, default=0.0)
-BN_FREE_PROB = _ap.parse_args().bn_free_prob
+_ap.add_argument('--width-mult', type=int, default=1)
+BN_FREE_PROB, WIDTH_MULT = _ap.parse_args().bn_free_prob, _ap.parse_args().width_mult
 counts = collections.Counter()
 host = collections.Counter()
 
@@ -72,8 +74,9 @@ trainer = Trainer(ghn, opt='adamw', opt_args={'lr': 4e-4, 'weight_decay': 1e-2},
 gen = torch.Generator().manual_seed(1)
 images = torch.randn(64, 3, 32, 32, generator=gen).cuda()
 targets = torch.randint(0, 10, (64,), generator=gen).cuda()
-nets = SampledNets(large_images=False, seed=0, max_nodes=400, bn_free_prob=BN_FREE_PROB)
-print('architecture stream: seed 0, max_nodes 400, bn_free_prob %g, %d steps of 8 networks' % (BN_FREE_PROB, STEPS))
+nets = SampledNets(large_images=False, seed=0, max_nodes=400, bn_free_prob=BN_FREE_PROB, width_mult=WIDTH_MULT)
+print('architecture stream: seed 0, max_nodes 400, bn_free_prob %g, width_mult %d, %d steps of 8 networks' % (BN_FREE_PROB, WIDTH_MULT,
+                                                                                                            STEPS))
 for step in range(STEPS):
     gb = GraphBatch([nets[step * 8 + k] for k in range(8)], dense=True)
     trainer.update(images, targets, graphs=gb)

@@ -1,6 +1,11 @@
 """Micro-benchmark of the dense-convolution op (ghn3_conv_bn_fwd / _bwd) on the shapes the training loop's architecture stream
-produces (batch 64, 32 x 32 images): microseconds per forward / backward, and the same for the stock MIOpen layers."""
+produces (batch 64, 32 x 32 images): microseconds per forward / backward, and the same for the stock MIOpen layers.
+--wide: six blocks of a WIDE network instead (1024 .. 4096 channels at 4 x 4 and 2 x 2, batch 64; torch.nn-flavour modules taking
+and returning NCHW tensors, so the native setting pays its layout copies): forward + backward of the same call with
+GHN3_NATIVE_OPS=1 (above 512 channels: Depthwise + the dense-convolution family) and =0 (the stock ATen / MIOpen layers, WARM: their
+find step is paid before the timing), alternated round by round, median of ROUNDS=5 rounds of REPS calls with max - min."""
 import os
+import statistics
 import sys
 import time
 
@@ -28,6 +33,45 @@ def timed(fn):
     torch.cuda.synchronize()
     return 1e3 * e0.elapsed_time(e1) / REPS
 
+
+WIDE = [  # constructor, arguments, H = W
+    ('ReLUConvBN', (1024, 1024, 3, 1, 1), 4), ('ReLUConvBN', (2048, 2048, 1), 2), ('ReLUConvBN', (4096, 1024, 1), 4),
+    ('DilConv', (1024, 1024, 3, 1, 2, 2), 4), ('SepConv', (2048, 2048, 3, 1, 1), 2), ('SepConv', (1024, 1024, 5, 1, 2), 4),
+]
+
+
+def wide():
+    from ghn3_amd import ops
+    rounds = int(os.environ.get('ROUNDS', '5'))
+    print('%-44s %22s %22s %8s' % ('block (batch 64)', 'native fwd+bwd us', 'stock fwd+bwd us', 'ratio'))
+    for kind, args, hw in WIDE:
+        torch.manual_seed(1)
+        m = getattr(ops, kind)(*args, norm='bn').cuda().train()
+        x = torch.randn(64, args[0], hw, hw, device='cuda', requires_grad=True)
+        up = None
+        res = {'1': [], '0': []}
+
+        def step():
+            m(x).backward(up)
+
+        for setting in ('1', '0'):                             # warm-up of both settings (the stock layers' find step)
+            os.environ['GHN3_NATIVE_OPS'] = setting
+            up = torch.randn_like(m(x)) if up is None else up
+            step()
+        for _ in range(rounds):
+            for setting in ('1', '0'):
+                os.environ['GHN3_NATIVE_OPS'] = setting
+                res[setting].append(timed(step))
+        med = {k: statistics.median(v) for k, v in res.items()}
+        print('%-44s %12.1f +- %-7.1f %12.1f +- %-7.1f %8.2f' % (
+            '%s%s %dx%d' % (kind, args, hw, hw), med['1'], max(res['1']) - min(res['1']), med['0'], max(res['0']) - min(res['0']),
+            med['0'] / med['1']))
+    os.environ['GHN3_NATIVE_OPS'] = '1'
+
+
+if '--wide' in sys.argv[1:]:
+    wide()
+    sys.exit(0)
 
 print('%-34s %10s %10s %10s %10s   %s' % ('shape', 'fwd us', 'bwd us', 'stock fwd', 'stock bwd', 'GFLOP fwd'))
 tot = [0.0, 0.0, 0.0, 0.0]
