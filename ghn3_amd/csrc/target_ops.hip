@@ -46,14 +46,10 @@
 #include <algorithm>
 #include "tnet_common.h"
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
-
 namespace {
 
 constexpr int TP = 64;       // pixels per tile (4 waves x 16-row MFMA tiles)
-constexpr int KC = 32;       // reduction chunk = one v_mfma_f32_16x16x32_bf16 k-step
-constexpr int LDK = 40;      // LDS row pitch in 16-bit elements (80 bytes: 16-byte aligned fragments)
+// (KC, LDK and the split-bf16 product helpers splitS / frag / mma_terms: tnet_common.h, shared with tnet_patch.hip)
 constexpr int MAXT = 49;     // taps (ks <= 7)
 // operand pieces of the kernels templated on NT (16 NT columns per workgroup): three (fp32-equivalent products) up to 256
 // columns, two for the widest tiles (registers)
@@ -84,43 +80,6 @@ __device__ __forceinline__ f32x4 frozen_affine4(const f32x4 v, const Frozen& fz,
 #pragma unroll
     for (int e = 0; e < 4; ++e) o[e] = (v[e] - mu[e]) * (1.f / sqrtf(va[e] + eps)) * ga[e] + be[e];
     return o;
-}
-
-// two values at once on the hardware converter (v_cvt_pk_bf16_f32, round to nearest even as bf16_rn): low half = a
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned bf16_pk(float a, float b) {
-    const f32x2_t v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-}
-__device__ __forceinline__ unsigned short bf16_rn(float v) { return (unsigned short)bf16_pk(v, v); }
-// v = p[0] + p[1] (+ p[2]) in bf16 pieces: 16 (24) bits of mantissa.  With S = 3 pieces and the six products
-// 11 + 12 + 21 + 22 + 13 + 31 the matrix-core product carries fp32's own rounding (~1e-7); S = 2 (hi.hi + lo.hi + hi.lo) ~1e-5.
-template <int S>
-__device__ __forceinline__ void splitS(float v, unsigned short* base, int idx, int stride) {
-    float r = v;
-#pragma unroll
-    for (int q = 0; q < S; ++q) {
-        const unsigned short h = bf16_rn(r);
-        base[q * stride + idx] = h;
-        r -= __uint_as_float((unsigned)h << 16);
-    }
-}
-// acc[e] += sum_k A[lane & 15][k] B[4 (lane >> 4) + e][k]   (B fragment first: a lane owns 4 consecutive columns of a row)
-__device__ __forceinline__ f32x4 mfma_bt(u16x8 b, u16x8 a, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, b), __builtin_bit_cast(bf16x8, a), c, 0, 0, 0);
-}
-__device__ __forceinline__ u16x8 frag(const unsigned short* base, int row, int kc) {
-    return *reinterpret_cast<const u16x8*>(base + row * LDK + 8 * kc);
-}
-
-template <int S>
-__device__ __forceinline__ f32x4 mma_terms(const u16x8 (&a)[S], const u16x8 (&b)[S], f32x4 acc) {
-    if (S == 3) { acc = mfma_bt(b[2], a[0], acc); acc = mfma_bt(b[0], a[2], acc); acc = mfma_bt(b[1], a[1], acc); }   // smallest first
-    acc = mfma_bt(b[1], a[0], acc);
-    acc = mfma_bt(b[0], a[1], acc);
-    acc = mfma_bt(b[0], a[0], acc);
-    return acc;
 }
 
 // ReLU + depthwise taps of 8 consecutive channels c .. c + 7 at output pixel (n, oh, ow); ih0 / iw0 = input origin of the

@@ -1,4 +1,4 @@
-// What the target-network files (target_ops.hip, tnet_msa.hip, tnet_head.hip, tnet_wgrad.hip) share.  Internal: not part of
+// What the target-network files (target_ops.hip, tnet_patch.hip, tnet_msa.hip, tnet_head.hip, tnet_wgrad.hip) share.  Internal: not part of
 // the C ABI.
 #pragma once
 
@@ -21,6 +21,49 @@ __device__ inline int wave_isum(int v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
+}
+
+// ---- split-bf16 products on v_mfma_f32_16x16x32_bf16 (target_ops.hip, tnet_patch.hip) -------------------------------------------
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
+constexpr int KC = 32;       // reduction chunk = one v_mfma_f32_16x16x32_bf16 k-step
+constexpr int LDK = 40;      // LDS row pitch in 16-bit elements (80 bytes: 16-byte aligned fragments)
+
+// two values at once on the hardware converter (v_cvt_pk_bf16_f32, round to nearest even as bf16_rn): low half = a
+typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+typedef float f32x2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned bf16_pk(float a, float b) {
+    const f32x2_t v = {a, b};
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
+}
+__device__ __forceinline__ unsigned short bf16_rn(float v) { return (unsigned short)bf16_pk(v, v); }
+// v = p[0] + p[1] (+ p[2]) in bf16 pieces: 16 (24) bits of mantissa.  With S = 3 pieces and the six products
+// 11 + 12 + 21 + 22 + 13 + 31 the matrix-core product carries fp32's own rounding (~1e-7); S = 2 (hi.hi + lo.hi + hi.lo) ~1e-5.
+template <int S>
+__device__ __forceinline__ void splitS(float v, unsigned short* base, int idx, int stride) {
+    float r = v;
+#pragma unroll
+    for (int q = 0; q < S; ++q) {
+        const unsigned short h = bf16_rn(r);
+        base[q * stride + idx] = h;
+        r -= __uint_as_float((unsigned)h << 16);
+    }
+}
+// acc[e] += sum_k A[lane & 15][k] B[4 (lane >> 4) + e][k]   (B fragment first: a lane owns 4 consecutive columns of a row)
+__device__ __forceinline__ f32x4 mfma_bt(u16x8 b, u16x8 a, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, b), __builtin_bit_cast(bf16x8, a), c, 0, 0, 0);
+}
+__device__ __forceinline__ u16x8 frag(const unsigned short* base, int row, int kc) {
+    return *reinterpret_cast<const u16x8*>(base + row * LDK + 8 * kc);
+}
+
+template <int S>
+__device__ __forceinline__ f32x4 mma_terms(const u16x8 (&a)[S], const u16x8 (&b)[S], f32x4 acc) {
+    if (S == 3) { acc = mfma_bt(b[2], a[0], acc); acc = mfma_bt(b[0], a[2], acc); acc = mfma_bt(b[1], a[1], acc); }   // smallest first
+    acc = mfma_bt(b[1], a[0], acc);
+    acc = mfma_bt(b[0], a[1], acc);
+    acc = mfma_bt(b[0], a[0], acc);
+    return acc;
 }
 
 // scratch sections start on multiples of 64 floats

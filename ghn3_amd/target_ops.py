@@ -31,6 +31,11 @@ ReLU + depthwise taps alone, C <= 16384) and the 1 x 1 member of the dense-convo
 GHN3_NATIVE_WIDE=0 keeps every layer above the former limits (512 / 4096 -> 512 / 1024) on the stock layers.  The ``msa`` layers
 keep their limits (C <= 256, head dim <= 32): a wide ViT-style network runs them on the stock path.
 
+The patch embedding of the ViT-style networks (``run_conv_layer``): 3 x 3 / stride 3 on CIFAR-sized inputs runs on ``ConvOnly``;
+16 x 16 / stride 16 on ImageNet-sized inputs -- a kernel the dense-convolution op refuses -- on ``PatchEmbed`` / ``patch_embed``
+(ghn3_patch_fwd / _bwd, ghn3_amd/csrc/tnet_patch.hip): non-overlapping windows as a GEMM over the image as stored.
+GHN3_NATIVE_STEM=0 keeps the layer stock.
+
 ``DwPwBn.applicable`` states what the kernels take (fp32 CUDA tensors, batch statistics, C <= 512, ks <= 7); a layer
 outside of it goes to the two-node form above or keeps the stock path.  There is no CPU implementation: on a CPU tensor the
 stock path runs (the target networks themselves are torch modules), and ``dwpw_bn`` raises without the library.
@@ -621,6 +626,90 @@ def conv_only(x, w, stride=1, padding=0, dilation=1, relu=False):
     return ConvOnly.apply(x, w, _pair(stride), _pair(padding), int(dilation), bool(relu))
 
 
+class _PatchDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ('N', 'H', 'W', 'C_in', 'C_out', 'kh', 'kw', 'stride_h', 'stride_w', 'Ho', 'Wo', 'nhwc')]
+
+
+PATCH_KERNEL = (8, 32)            # max(kh, kw) the patch-embedding op takes: what the dense-convolution op (<= 7) refuses
+PATCH_MAX_IN = 4                  # image channels
+PATCH_MAX_RED = 4096              # C_in kh kw
+PATCH_MAX_OUT = 4096
+
+
+def _patch_desc(x, w, stride, nhwc=0):
+    N, C, H, W = x.shape
+    C_out, _, kh, kw = w.shape
+    sh, sw = _pair(stride)
+    Ho, Wo = (H - kh) // sh + 1 if H >= kh else 0, (W - kw) // sw + 1 if W >= kw else 0
+    return _PatchDesc(N, H, W, C, C_out, kh, kw, sh, sw, Ho, Wo, int(nhwc))
+
+
+class PatchEmbed(torch.autograd.Function):
+    """A bias-free convolution whose windows do not overlap (stride >= kernel, no padding, no dilation) with a kernel of 8 .. 32 a
+    side, as ONE autograd node on ghn3_patch_fwd / _bwd (ghn3_amd/csrc/tnet_patch.hip): the patch embedding of the ImageNet-sized
+    ViT-style networks, Conv2d(3, C, 16, stride=16).  x is read as stored (NCHW-contiguous or channels_last; three channels as
+    three), the weight [C_out][C_in][kh][kw] in place; the result is channels_last, dx has x's layout and is computed only when x
+    requires a gradient."""
+
+    @staticmethod
+    def applicable(x, w, stride, padding=0, dilation=1):
+        """The limits of the C side (check_pdesc), so that a layer that passes never raises in the middle of a network."""
+        if not (enabled() and os.environ.get('GHN3_NATIVE_CONV', '1') != '0' and torch.is_tensor(x) and x.is_cuda and
+                x.dtype == torch.float32 and x.dim() == 4 and not _autocast_excludes()):
+            return False
+        if not (torch.is_tensor(w) and w.is_cuda and w.dtype == torch.float32 and w.dim() == 4):
+            return False
+        if isinstance(padding, str) or _pair(padding) != (0, 0) or _pair(dilation) != (1, 1):
+            return False
+        (N, C_in, H, W), (C_out, w_in, kh, kw), (sh, sw) = x.shape, w.shape, _pair(stride)
+        if not (PATCH_KERNEL[0] <= max(kh, kw) <= PATCH_KERNEL[1] and w_in == C_in and 1 <= C_in <= PATCH_MAX_IN and
+                C_in * kh * kw <= PATCH_MAX_RED and C_out % 4 == 0 and 0 < C_out <= PATCH_MAX_OUT and sh >= kh and sw >= kw):
+            return False
+        d = _patch_desc(x, w, stride)
+        return N > 0 and d.Ho > 0 and d.Wo > 0 and x.numel() < 2 ** 31 and N * d.Ho * d.Wo * C_out < 2 ** 31
+
+    @staticmethod
+    def forward(ctx, x, w, stride, keep):
+        lib = L.load()
+        nhwc = not x.is_contiguous() and x.is_contiguous(memory_format=torch.channels_last)
+        xc = x if (nhwc or x.is_contiguous()) else x.contiguous()
+        wc = w.contiguous()
+        d = _patch_desc(xc, wc, stride, nhwc)
+        z = torch.empty((d.N, d.C_out, d.Ho, d.Wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+        L._check(lib.ghn3_patch_fwd(ctypes.byref(d), _ptr(xc), _ptr(wc), _ptr(z), None, _stream()), 'ghn3_patch_fwd')
+        if keep:
+            ctx.save_for_backward(xc, wc)
+            ctx.cfg = (stride, nhwc)
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        lib = L.load()
+        xc, wc = ctx.saved_tensors
+        stride, nhwc = ctx.cfg
+        d = _patch_desc(xc, wc, stride, nhwc)
+        do = dz.contiguous(memory_format=torch.channels_last)
+        if do.data_ptr() % 16:                                 # (a view into a larger gradient: the kernels read whole quads)
+            do = do.clone(memory_format=torch.channels_last)
+        dx = torch.empty_like(xc) if ctx.needs_input_grad[0] else None
+        dw = torch.empty_like(wc) if ctx.needs_input_grad[1] else None      # (a tensor of its own: it becomes a leaf's .grad)
+        n = _scratch_floats('ghn3_patch_scratch_floats', d, 1)
+        scratch = torch.empty(n, dtype=torch.float32, device=xc.device) if (n and dw is not None) else None
+        L._check(lib.ghn3_patch_bwd(ctypes.byref(d), _ptr(do), _ptr(xc), _ptr(wc), None if dx is None else _ptr(dx),
+                                    None if dw is None else _ptr(dw), None if scratch is None else _ptr(scratch), _stream()),
+                 'ghn3_patch_bwd')
+        return dx, dw, None, None
+
+
+def patch_embed(x, w, stride):
+    """conv2d(x, w, stride=stride) for non-overlapping windows (see PatchEmbed); x (N, C_in <= 4, H, W) fp32 CUDA tensor, w (C_out,
+    C_in, kh, kw); the result is a channels_last tensor.  Under torch.no_grad(), or when neither input requires a gradient, nothing
+    is saved."""
+    if not x.is_cuda:
+        raise L.Ghn3Error('patch_embed runs on an MI355X only (no CPU implementation: use the stock torch layers)')
+    return PatchEmbed.apply(x, w, _pair(stride), _wants_grad(x, w))
+
+
 def conv_bn(x, w, gamma, beta, stride=1, padding=0, dilation=1, relu=True, eps=1e-5):
     """out = batch_norm(conv2d(relu(x) if relu else x, w)) with batch statistics; returns (out, stats) as dwpw_bn does.
     x: (N, C, H, W) fp32 CUDA tensor (channels_last preferred), w (C_out, C, kh, kw)."""
@@ -831,10 +920,16 @@ def run_conv_pair_block(layers, x, keep_layout=False):
 
 
 def run_conv_layer(conv, x):
-    """A bare Conv2d without bias (the patch embedding of the ViT-style networks, ops.py:296 `conv_stride`) on the
-    dense-convolution op -- 3-channel images padded as in run_layer_seq -- handing an NCHW tensor on; else the stock layer."""
-    if _plain_conv(conv) and torch.is_tensor(x) and x.is_cuda and x.dim() == 4:
+    """A bare Conv2d without bias (the patch embedding of the ViT-style networks, ops.py:296 `conv_stride`), handing an NCHW
+    tensor on: up to 7 x 7 (CIFAR-sized inputs: 3 x 3, stride 3) on the dense-convolution op -- 3-channel images padded as in
+    run_layer_seq --, a larger kernel with non-overlapping windows (ImageNet-sized inputs: 16 x 16, stride 16) on the patch-embedding
+    op, which reads the image as it is; else the stock layer.  GHN3_NATIVE_STEM=0 keeps the stock layer, as for the other stems."""
+    if _plain_conv(conv) and torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and os.environ.get('GHN3_NATIVE_STEM', '1') != '0':
         w, xin = conv.weight, x
+        if w.dim() == 4 and max(w.shape[2], w.shape[3]) > 7:              # (what ConvOnly refuses for its kernel size)
+            if PatchEmbed.applicable(x, w, conv.stride, conv.padding, conv.dilation):
+                return patch_embed(x, w, conv.stride).contiguous(memory_format=torch.contiguous_format)
+            return conv(x)
         if x.shape[1] == 3 and w.shape[1] == 3:
             xin, w = F.pad(x, (0, 0, 0, 0, 0, 1)), F.pad(w, (0, 0, 0, 0, 0, 1))
         if ConvOnly.applicable(xin, w):

@@ -647,6 +647,36 @@ int ghn3_conv_frozen_bwd(const ghn3_conv_desc* desc, const float* dout, const fl
                          const float* gamma, const float* mean, const float* var, float* dx, float* dw, float* dgamma, float* dbeta,
                          float* scratch, void* stream);
 
+/* The patch embedding of the ImageNet-sized ViT-style networks (`conv_stride`: Conv2d(3, C, 16, stride = 16) on 224 x 224
+ * images) -- a bias-free, ungrouped convolution without padding or dilation whose windows do not overlap, which is a plain GEMM
+ * over a permutation of the image (ghn3_amd/csrc/tnet_patch.hip):
+ *   z[n][oh][ow][co] = sum over (ci, a, b) of x[n, ci, oh stride_h + a, ow stride_w + b] w[co][ci][a][b],
+ *   Ho = (H - kh) / stride_h + 1, Wo = (W - kw) / stride_w + 1 (floor: trailing rows / columns no window reaches are ignored).
+ * x (and dx) [N][C_in][H][W] fp32 as stored: nhwc = 0 NCHW-contiguous, nhwc = 1 channels-last [N][H][W][C_in]; it may start
+ * anywhere (scalar loads; W and kw need not be multiples of 4, the three image channels are read as three).  w [C_out][C_in][kh][kw]
+ * is the view of the GHN's flat prediction buffer, read in place and cut into bf16 pieces while staged (no pack, no transpose; it
+ * may start on any float); dw is written in the same order.  z / dz [N Ho Wo][C_out] (NHWC) start on 16 bytes.
+ * Limits (GHN3_E_LIMIT: the caller keeps its stock path): 8 <= max(kh, kw) <= 32 (smaller kernels belong to the
+ * dense-convolution family above), C_in <= 4, C_in kh kw <= 4096, C_out a multiple of 4 and <= 4096, stride_h >= kh and
+ * stride_w >= kw, N C_in H W and N Ho Wo C_out below 2^31.  Ho / Wo that do not follow from the arithmetic, a non-positive size or
+ * another `nhwc`: GHN3_E_ARG.  Added without an ABI version step (symbols only).
+ * Forward: ONE launch (three-piece bf16 products, fp32 accumulate: the dense-convolution family's arithmetic), no scratch.
+ * Backward: dx == NULL (an image batch needs no gradient): dx is not computed; else dx = dz . w scattered to the image's layout
+ * plus one launch that zeroes the elements no window reaches (only when there are any): every element of dx is written.
+ * dw (NULL: not computed) = per-chunk partial products (exact fp32 products) reduced in chunk order: 2 launches, 1 for one chunk.
+ * No float atomics, no allocation, no synchronisation inside.  Deterministic.
+ * ghn3_patch_scratch_floats: 0 for the forward; backward = round_up_64(chunks C_out K) for chunks > 1, else 0, with
+ * K = C_in kh kw, P = N Ho Wo, tiles = ceil(C_out / 32) ceil(K / 32), n = clamp(ceil(1024 / tiles), 1, ceil(P / 64)),
+ * px = round_up_16(ceil(P / n)), chunks = ceil(P / px): partials [chunks][C_out][K]; a negative GHN3_E_* code for a
+ * descriptor the op does not take. */
+typedef struct ghn3_patch_desc {
+    int32_t N, H, W, C_in, C_out, kh, kw, stride_h, stride_w, Ho, Wo, nhwc;
+} ghn3_patch_desc;
+int64_t ghn3_patch_scratch_floats(const ghn3_patch_desc* desc, int backward);   /* < 0: bad descriptor (ghn3_last_error) */
+int ghn3_patch_fwd(const ghn3_patch_desc* desc, const float* x, const float* w, float* z, float* scratch, void* stream);
+int ghn3_patch_bwd(const ghn3_patch_desc* desc, const float* dz, const float* x, const float* w, float* dx, float* dw,
+                   float* scratch, void* stream);
+
 /* ---- target-network layers, third slice (ABI v19, round 6): squeeze-and-excitation with a hard-swish gate -----------------
  * Replaces `ChannelSELayer.forward` (/root/reference/ghn3/ops.py:239-274) executed at trainer.py:308-319 and torch autograd of it:
  *   s = mean over the pixels of x;  h = relu(W1 s + b1);  a = W2 h + b2;  y = x * hardswish(a)

@@ -2,7 +2,9 @@
 Runs Trainer.update on the architecture stream of examples/train_ghn_ddp.py and counts, per step, the stock Conv2d / BatchNorm2d /
 Linear / pooling calls and F.cross_entropy calls by configuration and by the module class that issued them.
 --bn-free-prob P: the share of the stream drawn without norm layers (norm=None), as in examples/train_ghn_ddp.py.
---width-mult M: multiplies the drawn width C of every architecture (4: the widths of the `wide` evaluation split)."""
+--width-mult M: multiplies the drawn width C of every architecture (4: the widths of the `wide` evaluation split).
+--large-images: the ImageNet-sized stream of examples/train_ghn_ddp.py --imagenet (SampledNets(large_images=True), 224 x 224 inputs,
+1000 classes, max_shape 16 x 16); --batch B: images per step (default 64; a small one keeps the large-image census short)."""
 import argparse
 import collections
 import inspect
@@ -21,7 +23,11 @@ STEPS = int(os.environ.get('CENSUS_STEPS', '12'))
 _ap = argparse.ArgumentParser()
 _ap.add_argument('--bn-free-prob', type=float, default=0.0)
 _ap.add_argument('--width-mult', type=int, default=1)
+_ap.add_argument('--large-images', action='store_true')
+_ap.add_argument('--batch', type=int, default=64)
 BN_FREE_PROB, WIDTH_MULT = _ap.parse_args().bn_free_prob, _ap.parse_args().width_mult
+LARGE, BATCH = _ap.parse_args().large_images, _ap.parse_args().batch
+SIDE, CLASSES, MAX_K = (224, 1000, 16) if LARGE else (32, 10, 11)
 counts = collections.Counter()
 host = collections.Counter()
 
@@ -65,18 +71,18 @@ def counted_cross_entropy(*args, **kwargs):
 torch.nn.functional.cross_entropy = counted_cross_entropy
 
 hid, layers, heads = 64, 3, 8
-config = {'max_shape': (hid, hid, 11, 11), 'num_classes': 10, 'weight_norm': True, 've': True, 'layernorm': True, 'hid': hid,
+config = {'max_shape': (hid, hid, MAX_K, MAX_K), 'num_classes': CLASSES, 'weight_norm': True, 've': True, 'layernorm': True, 'hid': hid,
           'layers': layers, 'heads': heads}
 torch.manual_seed(0)
 ghn = GHN3(**config, compute='f16')
 trainer = Trainer(ghn, opt='adamw', opt_args={'lr': 4e-4, 'weight_decay': 1e-2}, scheduler='cosine', n_batches=STEPS, grad_clip=5,
                   device='cuda', log_interval=100, amp=False, predparam_wd=3e-5, verbose=False)
 gen = torch.Generator().manual_seed(1)
-images = torch.randn(64, 3, 32, 32, generator=gen).cuda()
-targets = torch.randint(0, 10, (64,), generator=gen).cuda()
-nets = SampledNets(large_images=False, seed=0, max_nodes=400, bn_free_prob=BN_FREE_PROB, width_mult=WIDTH_MULT)
-print('architecture stream: seed 0, max_nodes 400, bn_free_prob %g, width_mult %d, %d steps of 8 networks' % (BN_FREE_PROB, WIDTH_MULT,
-                                                                                                            STEPS))
+images = torch.randn(BATCH, 3, SIDE, SIDE, generator=gen).cuda()
+targets = torch.randint(0, CLASSES, (BATCH,), generator=gen).cuda()
+nets = SampledNets(large_images=LARGE, seed=0, max_nodes=400, bn_free_prob=BN_FREE_PROB, width_mult=WIDTH_MULT)
+print('architecture stream: seed 0, max_nodes 400, bn_free_prob %g, width_mult %d, %d steps of 8 networks%s' % (
+    BN_FREE_PROB, WIDTH_MULT, STEPS, ', large images (%d x %d x %d, %d classes)' % (BATCH, SIDE, SIDE, CLASSES) if LARGE else ''))
 for step in range(STEPS):
     gb = GraphBatch([nets[step * 8 + k] for k in range(8)], dense=True)
     trainer.update(images, targets, graphs=gb)
