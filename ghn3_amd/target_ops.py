@@ -9,19 +9,26 @@ ghn3_amd/csrc/target_ops.hip) instead of four ATen / MIOpen modules per directio
 
 Activations are torch ``channels_last`` tensors (NHWC in memory, NCHW in shape) inside the op family: the kernels take such
 storage as it is and return it, so consecutive fused blocks (the two halves of a SepConv) never convert.  At the boundary to
-the stock layers the activations are converted (``run_block``): the stock ATen / MIOpen layers of this ROCm build return
+the stock layers the activations are converted (``_hand_on``): the stock ATen / MIOpen layers of this ROCm build return
 wrong gradients for channels_last inputs, so the layout is not allowed to leak into them.  The weights are the views of the GHN's flat prediction buffer the GHN assigned to the
 layers -- read in place, no copy; their gradients leave as dense tensors for autograd to route back into that buffer.
 
-A network built with norm=None has an Identity in every norm slot (`bn_layer`, ops.py:91-96): its blocks run on the members of
-the families without a norm layer -- ``DwPw`` / ``dwpw`` (ghn3_dwpw_plain_fwd / _bwd) and ``ConvOnly`` / ``conv_only`` --, routed
-by the same runners (``_no_norm``; GHN3_NATIVE_NONORM=0 keeps such blocks on the stock layers).
+Two op families, three members each, one per state of the block's norm slot (``_norm_slot``, built once per call):
 
-A BatchNorm that carries running statistics and is not in training mode (``net.eval()`` on a network built with the default
-norm='bn-track') is a per-channel affine map with constants known before the launch: its blocks run on ``DwPwBnEval`` /
-``dwpw_bn_eval`` (ghn3_dwpw_frozen_fwd / _bwd) and ``ConvBnEval`` / ``conv_bn_eval`` (ghn3_conv_frozen_fwd / _bwd), routed by the
-same runners (``_frozen_norm``; GHN3_NATIVE_EVALBN=0 keeps such blocks on the stock layers).  The running statistics are read
-only: they take no gradient and are never written.
+    norm slot                                          depthwise + pointwise            dense convolution
+    BatchNorm2d with batch statistics ('batch')        DwPwBn / dwpw_bn                 ConvBn / conv_bn
+    Identity: a network built with norm=None ('none')  DwPw / dwpw                      ConvOnly / conv_only
+    BatchNorm2d with running statistics that is not    DwPwBnEval / dwpw_bn_eval        ConvBnEval / conv_bn_eval
+    in training mode ('frozen')
+
+(`bn_layer`, ops.py:91-96, puts an Identity in every norm slot of a norm=None network; ``net.eval()`` on a network built with the
+default norm='bn-track' freezes the statistics: a per-channel affine map with constants known before the launch, read only --
+no gradient, never written.)  GHN3_NATIVE_NONORM=0 / GHN3_NATIVE_EVALBN=0 keep the blocks of the second / third row on the stock
+layers.  The three nodes of a family are thin ``autograd.Function`` classes over one forward and one backward
+(``_dwpw_forward`` / ``_dwpw_backward``, ``_conv_forward`` / ``_conv_backward``); every runner (``run_block``,
+``run_pointwise_block``, ``run_conv_block``, ``run_conv_pair_block``, ``run_factorized_reduce``, ``run_layer_seq``) checks its
+layers' attributes, asks ONE dispatch per node (``_dwpw_dispatch`` / ``_conv_dispatch``: the slot's member, its ``applicable``,
+the call, the running statistics of the batch member) and hands the result on or runs the stock layers.
 
 WIDE networks (the `wide` evaluation split of DeepNets-1M: up to 2048 channels in the last stage, 8192 into a cell's 1 x 1
 preprocessing layer): the fused depthwise + pointwise kernels keep all output columns of a pixel tile in one workgroup and stop at
@@ -41,10 +48,11 @@ outside of it goes to the two-node form above or keeps the stock path.  There is
 stock path runs (the target networks themselves are torch modules), and ``dwpw_bn`` raises without the library.
 """
 
+import collections
 import ctypes
+import math
 import os
 
-import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -64,7 +72,13 @@ def _desc(x, C_out, ks, stride, pad, dil, eps):
 
 
 def _ptr(t):
-    return t.data_ptr()               # (an int: ctypes converts it for the c_void_p parameters)
+    """The address of t's storage (an int: ctypes converts it for the c_void_p parameters); None, a null pointer, for None."""
+    return None if t is None else t.data_ptr()
+
+
+def _ptrs(*tensors):
+    """_ptr of every argument, in one call: a launch passes ten or more."""
+    return [None if t is None else t.data_ptr() for t in tensors]
 
 
 def _autocast_excludes():
@@ -128,6 +142,27 @@ def enabled():
     return os.environ.get('GHN3_NATIVE_OPS', '1') != '0'
 
 
+def _f32_cuda(*tensors):
+    """Every argument is an fp32 CUDA tensor (a plain loop: asked several times per fused layer, and a generator costs more
+    than the tests)."""
+    for t in tensors:
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32):
+            return False
+    return True
+
+
+def _native_input(x, switch=None):
+    """What every `applicable` asks first: x is a 4-d fp32 CUDA tensor, and neither GHN3_NATIVE_OPS=0, the op's own switch
+    (`switch`=0, e.g. 'GHN3_NATIVE_CONV') nor autocast with GHN3_NATIVE_AMP=0 keeps the layer on the stock path."""
+    return enabled() and (switch is None or os.environ.get(switch, '1') != '0') and _f32_cuda(x) and x.dim() == 4 and \
+        not _autocast_excludes()
+
+
+def _needs_gpu(name, x):
+    if not x.is_cuda:
+        raise L.Ghn3Error('%s runs on an MI355X only (no CPU implementation: use the stock torch layers)' % name)
+
+
 def _no_norm(bn):
     """True for the norm slot of a network built with norm=None (`bn_layer`, ops.py:91-96: an Identity layer of either flavour):
     the block then runs on the no-norm members of the op families (DwPw, ConvOnly).  GHN3_NATIVE_NONORM=0 keeps such blocks on
@@ -144,8 +179,7 @@ def _frozen_norm(batch_stats):
 
 
 def _frozen_stats_ok(running_mean, running_var, C_out):
-    return all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.numel() == C_out
-               for t in (running_mean, running_var))
+    return _f32_cuda(running_mean, running_var) and running_mean.numel() == C_out and running_var.numel() == C_out
 
 
 def _wide():
@@ -160,71 +194,121 @@ def _wants_grad(*tensors):
     return torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in tensors)
 
 
+def _is_kind(m, name):
+    return type(m).__name__ == name
+
+
+def _carve(like, n_scratch, *shapes, norm=0):
+    """ONE allocation for a backward's parameter gradients and its scratch area (a call is launch- and host-bound for the small
+    layers of a CIFAR network), on like's device: a gradient for every shape (None: no such parameter, None for its gradient),
+    then -- norm = C_out of a node with a norm layer -- dbeta DIRECTLY FOLLOWED by dgamma (the kernels' own pair of sums:
+    bn_param_grads, csrc/target_ops.hip, skips two device copies when dgamma == dbeta + C), then, a multiple of 64 floats from
+    the start, the n_scratch floats the kernels asked for.  Returns ([gradient, ..., dbeta, dgamma], scratch)."""
+    if norm:
+        shapes += ((norm,), (norm,))
+    sizes = [0 if s is None else math.prod(s) for s in shapes]
+    start = (sum(sizes) + 63) // 64 * 64
+    buf = torch.empty(start + n_scratch, dtype=torch.float32, device=like.device)
+    grads, at = [], 0
+    for s, n in zip(shapes, sizes):
+        grads.append(None if s is None else buf[at:at + n].view(s))
+        at += n
+    return grads, buf[start:]
+
+
+# ---- ReLU -> depthwise -> pointwise [-> norm]: one forward and one backward for the three members ----------------------------
+# norm mode -> (forward, backward, scratch size) of the C side
+_DWPW = {'batch': ('ghn3_dwpw_bn_fwd', 'ghn3_dwpw_bn_bwd', 'ghn3_dwpw_scratch_floats'),
+         'none': ('ghn3_dwpw_plain_fwd', 'ghn3_dwpw_plain_bwd', 'ghn3_dwpw_plain_scratch_floats'),
+         'frozen': ('ghn3_dwpw_frozen_fwd', 'ghn3_dwpw_frozen_bwd', 'ghn3_dwpw_frozen_scratch_floats')}
+
+
+def _dwpw_applicable(x, w_dw, w_pw, ks, *norm):
+    """What the three members ask of the input, the weights and the norm layer's tensors: fp32 CUDA tensors within the fused
+    kernels' limits."""
+    if not (_native_input(x) and (_f32_cuda(w_pw, *norm) if w_dw is None else _f32_cuda(w_dw, w_pw, *norm))):
+        return False
+    C_in, C_out = x.shape[1], w_pw.shape[0]
+    return C_in % 4 == 0 and C_out % 4 == 0 and C_in <= DWPW_MAX and C_out <= DWPW_MAX and ks <= 7 and \
+        x.numel() < 2 ** 31 and (w_dw is None or w_dw.shape[1] == 1) and w_pw.numel() == C_out * C_in
+
+
+def _dwpw_forward(ctx, mode, x, w_dw, w_pw, norm, stride, pad, dil, eps, keep=True):
+    """The forward of DwPwBn ('batch': norm = (gamma, beta)), DwPw ('none': ()) and DwPwBnEval ('frozen': (gamma, beta,
+    running_mean, running_var)); w_dw None: no depthwise stage.  One launch; returns (out, stats -- None but for 'batch').  The
+    pre-norm tensor z exists for 'batch', and for 'frozen' when `keep`; without `keep` nothing is saved on ctx."""
+    lib = L.load()
+    fwd, _, scratch_fn = _DWPW[mode]
+    ks = 1 if w_dw is None else int(w_dw.shape[-1])
+    C_out = int(w_pw.shape[0])
+    xc = x.contiguous(memory_format=torch.channels_last)          # (a no-op inside a channels_last network)
+    d = _desc(xc, C_out, ks, stride, pad, dil, eps)
+    wd, wp = (None if w_dw is None else w_dw.contiguous()), w_pw.contiguous()
+    norm = [t.contiguous() for t in norm]
+    dev = x.device
+    out = torch.empty((d.N, C_out, d.Ho, d.Wo), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
+    z = torch.empty_like(out) if (mode == 'batch' or (mode == 'frozen' and keep)) else None
+    stats = None
+    if mode == 'batch':
+        stats = torch.empty(3 * C_out, dtype=torch.float32, device=dev)
+        scratch = torch.empty(_scratch_floats(scratch_fn, d, 0), dtype=torch.float32, device=dev)
+        tail, saved = (z, out, stats, scratch), (z, stats, norm[0])
+    elif mode == 'frozen':
+        tail, saved = (z, out), (z, norm[0], norm[2], norm[3])
+    else:
+        tail, saved = (out,), ()
+    L._check(getattr(lib, fwd)(ctypes.byref(d), *_ptrs(xc, wd, wp, *norm, *tail), _stream()), fwd)
+    if keep:
+        ctx.has_dw = wd is not None
+        ctx.save_for_backward(xc, wp, wd if wd is not None else wp, *saved)     # (wp stands in for a missing depthwise weight)
+        ctx.cfg = (stride, pad, dil, eps)
+    return out, stats
+
+
+def _dwpw_backward(ctx, mode, dout):
+    """The backward of the three members: (dx, dw_dw or None, dw_pw), and (dgamma, dbeta) with a norm layer."""
+    lib = L.load()
+    _, bwd, scratch_fn = _DWPW[mode]
+    xc, wp, wd, *saved = ctx.saved_tensors
+    if not ctx.has_dw:
+        wd = None
+    stride, pad, dil, eps = ctx.cfg
+    C_out, ks = int(wp.shape[0]), (1 if wd is None else int(wd.shape[-1]))
+    d = _desc(xc, C_out, ks, stride, pad, dil, eps)
+    do = dout.contiguous(memory_format=torch.channels_last)
+    dx = torch.empty_like(xc)
+    grads, scratch = _carve(xc, _scratch_floats(scratch_fn, d, 1), None if wd is None else wd.shape, wp.shape,
+                            norm=0 if mode == 'none' else C_out)
+    if mode == 'batch':
+        (z, stats, g), (dwd, dwp, db, dg) = saved, grads
+        args = (do, xc, z, stats, wd, wp, g, dx, dwd, dwp, dg, db, scratch)
+    elif mode == 'frozen':
+        (z, g, rm, rv), (dwd, dwp, db, dg) = saved, grads
+        args = (do, xc, z, wd, wp, g, rm, rv, dx, dwd, dwp, dg, db, scratch)
+    else:
+        dwd, dwp = grads
+        args = (do, xc, wd, wp, dx, dwd, dwp, scratch)
+    L._check(getattr(lib, bwd)(ctypes.byref(d), *_ptrs(*args), _stream()), bwd)
+    return (dx, dwd, dwp) if mode == 'none' else (dx, dwd, dwp, dg, db)
+
+
 class DwPwBn(torch.autograd.Function):
+    """ReLU -> depthwise k x k convolution -> pointwise 1 x 1 convolution -> BatchNorm with BATCH statistics as ONE autograd
+    node on ghn3_dwpw_bn_fwd / _bwd; returns (out, stats), stats not differentiable."""
+
     @staticmethod
     def applicable(x, w_dw, w_pw, gamma, beta, ks, training_stats=True):
-        if not (enabled() and torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
-            return False
-        if _autocast_excludes():
-            return False                       # (GHN3_NATIVE_AMP=0: under AMP the stock path decides the types)
-        if not training_stats or not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32
-                                         for t in (w_pw, gamma, beta) + (() if w_dw is None else (w_dw,))):
-            return False
-        C_in, C_out = x.shape[1], w_pw.shape[0]
-        return C_in % 4 == 0 and C_out % 4 == 0 and C_in <= 512 and C_out <= 512 and ks <= 7 and \
-            x.numel() < 2 ** 31 and (w_dw is None or w_dw.shape[1] == 1) and w_pw.numel() == C_out * C_in
+        return bool(training_stats) and _dwpw_applicable(x, w_dw, w_pw, ks, gamma, beta)
 
     @staticmethod
     def forward(ctx, x, w_dw, w_pw, gamma, beta, stride, pad, dil, eps):
-        lib = L.load()
-        ks = 1 if w_dw is None else int(w_dw.shape[-1])
-        C_out = int(w_pw.shape[0])
-        xc = x.contiguous(memory_format=torch.channels_last)          # (a no-op inside a channels_last network)
-        d = _desc(xc, C_out, ks, stride, pad, dil, eps)
-        wd, wp = (None if w_dw is None else w_dw.contiguous()), w_pw.contiguous()
-        g, b = gamma.contiguous(), beta.contiguous()
-        dev = x.device
-        out = torch.empty((d.N, C_out, d.Ho, d.Wo), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
-        z = torch.empty_like(out)
-        stats = torch.empty(3 * C_out, dtype=torch.float32, device=dev)
-        scratch = torch.empty(_scratch_floats('ghn3_dwpw_scratch_floats', d, 0), dtype=torch.float32, device=dev)
-        stream = _stream()
-        L._check(lib.ghn3_dwpw_bn_fwd(ctypes.byref(d), _ptr(xc), _ptr(wd) if wd is not None else None, _ptr(wp), _ptr(g), _ptr(b),
-                                      _ptr(z), _ptr(out), _ptr(stats), _ptr(scratch), stream), 'ghn3_dwpw_bn_fwd')
-        ctx.has_dw = wd is not None
-        ctx.save_for_backward(xc, z, stats, wd if wd is not None else stats, wp, g)
-        ctx.cfg = (stride, pad, dil, eps)
+        out, stats = _dwpw_forward(ctx, 'batch', x, w_dw, w_pw, (gamma, beta), stride, pad, dil, eps)
         ctx.mark_non_differentiable(stats)
         return out, stats
 
     @staticmethod
     def backward(ctx, dout, _dstats):
-        lib = L.load()
-        xc, z, stats, wd, wp, g = ctx.saved_tensors
-        if not ctx.has_dw:
-            wd = None
-        stride, pad, dil, eps = ctx.cfg
-        C_out, ks = int(wp.shape[0]), (1 if wd is None else int(wd.shape[-1]))
-        d = _desc(xc, C_out, ks, stride, pad, dil, eps)
-        dev = xc.device
-        do = dout.contiguous(memory_format=torch.channels_last)
-        dx = torch.empty_like(xc)
-        # (one allocation for the four parameter gradients and the scratch area: a call is launch- and host-bound for the
-        # small layers of a CIFAR network)
-        n_wd = 0 if wd is None else wd.numel()
-        n_par = n_wd + wp.numel() + 2 * C_out
-        buf = torch.empty(n_par + 64 + _scratch_floats('ghn3_dwpw_scratch_floats', d, 1), dtype=torch.float32, device=dev)
-        dwd = None if wd is None else buf[:n_wd].view(wd.shape)
-        dwp = buf[n_wd:n_wd + wp.numel()].view(wp.shape)
-        db = buf[n_par - 2 * C_out:n_par - C_out]            # (dbeta directly followed by dgamma: the kernels' own pair of sums)
-        dg = buf[n_par - C_out:n_par]
-        scratch = buf[(n_par + 63) // 64 * 64:]
-        stream = _stream()
-        L._check(lib.ghn3_dwpw_bn_bwd(ctypes.byref(d), _ptr(do), _ptr(xc), _ptr(z), _ptr(stats),
-                                      _ptr(wd) if wd is not None else None, _ptr(wp), _ptr(g), _ptr(dx),
-                                      _ptr(dwd) if dwd is not None else None, _ptr(dwp), _ptr(dg), _ptr(db), _ptr(scratch), stream),
-                 'ghn3_dwpw_bn_bwd')
-        return dx, dwd, dwp, dg, db, None, None, None, None
+        return _dwpw_backward(ctx, 'batch', dout) + (None,) * 4
 
 
 class DwPw(torch.autograd.Function):
@@ -233,64 +317,15 @@ class DwPw(torch.autograd.Function):
     (ops.py:91-96).  Same conventions as DwPwBn (channels_last storage inside, weights read in place, w_dw None: no depthwise
     stage); one launch forward, no pre-norm tensor and no statistics: only x and the weights are saved."""
 
-    @staticmethod
-    def applicable(x, w_dw, w_pw, ks):
-        if not (enabled() and torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
-            return False
-        if _autocast_excludes():
-            return False
-        if not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32
-                   for t in (w_pw,) + (() if w_dw is None else (w_dw,))):
-            return False
-        C_in, C_out = x.shape[1], w_pw.shape[0]
-        return C_in % 4 == 0 and C_out % 4 == 0 and C_in <= 512 and C_out <= 512 and ks <= 7 and \
-            x.numel() < 2 ** 31 and (w_dw is None or w_dw.shape[1] == 1) and w_pw.numel() == C_out * C_in
+    applicable = staticmethod(_dwpw_applicable)
 
     @staticmethod
     def forward(ctx, x, w_dw, w_pw, stride, pad, dil):
-        lib = L.load()
-        ks = 1 if w_dw is None else int(w_dw.shape[-1])
-        C_out = int(w_pw.shape[0])
-        xc = x.contiguous(memory_format=torch.channels_last)
-        d = _desc(xc, C_out, ks, stride, pad, dil, 0.0)
-        wd, wp = (None if w_dw is None else w_dw.contiguous()), w_pw.contiguous()
-        out = torch.empty((d.N, C_out, d.Ho, d.Wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-        L._check(lib.ghn3_dwpw_plain_fwd(ctypes.byref(d), _ptr(xc), _ptr(wd) if wd is not None else None, _ptr(wp), _ptr(out),
-                                         _stream()), 'ghn3_dwpw_plain_fwd')
-        ctx.has_dw = wd is not None
-        ctx.save_for_backward(xc, wd if wd is not None else wp, wp)
-        ctx.cfg = (stride, pad, dil)
-        return out
+        return _dwpw_forward(ctx, 'none', x, w_dw, w_pw, (), stride, pad, dil, 0.0)[0]
 
     @staticmethod
     def backward(ctx, dout):
-        lib = L.load()
-        xc, wd, wp = ctx.saved_tensors
-        if not ctx.has_dw:
-            wd = None
-        stride, pad, dil = ctx.cfg
-        C_out, ks = int(wp.shape[0]), (1 if wd is None else int(wd.shape[-1]))
-        d = _desc(xc, C_out, ks, stride, pad, dil, 0.0)
-        do = dout.contiguous(memory_format=torch.channels_last)
-        dx = torch.empty_like(xc)
-        # (one allocation for the parameter gradients and the scratch area, as DwPwBn)
-        n_wd = 0 if wd is None else wd.numel()
-        n_par = (n_wd + wp.numel() + 63) // 64 * 64
-        buf = torch.empty(n_par + _scratch_floats('ghn3_dwpw_plain_scratch_floats', d, 1), dtype=torch.float32, device=xc.device)
-        dwd = None if wd is None else buf[:n_wd].view(wd.shape)
-        dwp = buf[n_wd:n_wd + wp.numel()].view(wp.shape)
-        L._check(lib.ghn3_dwpw_plain_bwd(ctypes.byref(d), _ptr(do), _ptr(xc), _ptr(wd) if wd is not None else None, _ptr(wp),
-                                         _ptr(dx), _ptr(dwd) if dwd is not None else None, _ptr(dwp), _ptr(buf[n_par:]), _stream()),
-                 'ghn3_dwpw_plain_bwd')
-        return dx, dwd, dwp, None, None, None
-
-
-def dwpw(x, w_dw, w_pw, stride=1, padding=0, dilation=1):
-    """out = conv1x1(depthwise_conv(relu(x))), no norm layer; w_dw None: conv1x1(relu(x)) with the stride.  x: (N, C, H, W) fp32
-    CUDA tensor (channels_last preferred), w_dw (C, 1, ks, ks), w_pw (C_out, C, 1, 1) or (C_out, C)."""
-    if not x.is_cuda:
-        raise L.Ghn3Error('dwpw runs on an MI355X only (no CPU implementation: use the stock torch layers)')
-    return DwPw.apply(x, w_dw, w_pw.reshape(w_pw.shape[0], -1), int(stride), int(padding), int(dilation))
+        return _dwpw_backward(ctx, 'none', dout) + (None,) * 3
 
 
 class DwPwBnEval(torch.autograd.Function):
@@ -306,58 +341,44 @@ class DwPwBnEval(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w_dw, w_pw, gamma, beta, running_mean, running_var, stride, pad, dil, eps, keep_z):
-        lib = L.load()
-        ks = 1 if w_dw is None else int(w_dw.shape[-1])
-        C_out = int(w_pw.shape[0])
-        xc = x.contiguous(memory_format=torch.channels_last)
-        d = _desc(xc, C_out, ks, stride, pad, dil, eps)
-        wd, wp = (None if w_dw is None else w_dw.contiguous()), w_pw.contiguous()
-        g, b, rm, rv = gamma.contiguous(), beta.contiguous(), running_mean.contiguous(), running_var.contiguous()
-        out = torch.empty((d.N, C_out, d.Ho, d.Wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-        z = torch.empty_like(out) if keep_z else None
-        L._check(lib.ghn3_dwpw_frozen_fwd(ctypes.byref(d), _ptr(xc), _ptr(wd) if wd is not None else None, _ptr(wp), _ptr(g), _ptr(b),
-                                          _ptr(rm), _ptr(rv), _ptr(z) if keep_z else None, _ptr(out), _stream()),
-                 'ghn3_dwpw_frozen_fwd')
-        if keep_z:
-            ctx.has_dw = wd is not None
-            ctx.save_for_backward(xc, z, wd if wd is not None else wp, wp, g, rm, rv)
-            ctx.cfg = (stride, pad, dil, eps)
-        return out
+        return _dwpw_forward(ctx, 'frozen', x, w_dw, w_pw, (gamma, beta, running_mean, running_var), stride, pad, dil, eps,
+                             keep_z)[0]
 
     @staticmethod
     def backward(ctx, dout):
-        lib = L.load()
-        xc, z, wd, wp, g, rm, rv = ctx.saved_tensors
-        if not ctx.has_dw:
-            wd = None
-        stride, pad, dil, eps = ctx.cfg
-        C_out, ks = int(wp.shape[0]), (1 if wd is None else int(wd.shape[-1]))
-        d = _desc(xc, C_out, ks, stride, pad, dil, eps)
-        do = dout.contiguous(memory_format=torch.channels_last)
-        dx = torch.empty_like(xc)
-        # (one allocation for the four parameter gradients and the scratch area, as DwPwBn)
-        n_wd = 0 if wd is None else wd.numel()
-        n_par = n_wd + wp.numel() + 2 * C_out
-        buf = torch.empty(n_par + 64 + _scratch_floats('ghn3_dwpw_frozen_scratch_floats', d, 1), dtype=torch.float32, device=xc.device)
-        dwd = None if wd is None else buf[:n_wd].view(wd.shape)
-        dwp = buf[n_wd:n_wd + wp.numel()].view(wp.shape)
-        db = buf[n_par - 2 * C_out:n_par - C_out]            # (dbeta directly followed by dgamma: the kernels' own pair of sums)
-        dg = buf[n_par - C_out:n_par]
-        scratch = buf[(n_par + 63) // 64 * 64:]
-        L._check(lib.ghn3_dwpw_frozen_bwd(ctypes.byref(d), _ptr(do), _ptr(xc), _ptr(z), _ptr(wd) if wd is not None else None, _ptr(wp),
-                                          _ptr(g), _ptr(rm), _ptr(rv), _ptr(dx), _ptr(dwd) if dwd is not None else None, _ptr(dwp),
-                                          _ptr(dg), _ptr(db), _ptr(scratch), _stream()), 'ghn3_dwpw_frozen_bwd')
-        return dx, dwd, dwp, dg, db, None, None, None, None, None, None, None
+        return _dwpw_backward(ctx, 'frozen', dout) + (None,) * 7
+
+
+def dwpw_bn(x, w_dw, w_pw, gamma, beta, stride=1, padding=0, dilation=1, eps=1e-5):
+    """out = batch_norm(conv1x1(depthwise_conv(relu(x)))) with batch statistics; returns (out, stats) with
+    stats = [mean | 1 / sqrt(var + eps) | biased variance] per output channel.  x: (N, C, H, W) fp32 CUDA tensor
+    (channels_last preferred), w_dw (C, 1, ks, ks), w_pw (C_out, C, 1, 1) or (C_out, C)."""
+    _needs_gpu('dwpw_bn', x)
+    return DwPwBn.apply(x, w_dw, w_pw.reshape(w_pw.shape[0], -1), gamma, beta, int(stride), int(padding), int(dilation),
+                        float(eps))
+
+
+def dwpw(x, w_dw, w_pw, stride=1, padding=0, dilation=1):
+    """out = conv1x1(depthwise_conv(relu(x))), no norm layer; w_dw None: conv1x1(relu(x)) with the stride.  x: (N, C, H, W) fp32
+    CUDA tensor (channels_last preferred), w_dw (C, 1, ks, ks), w_pw (C_out, C, 1, 1) or (C_out, C)."""
+    _needs_gpu('dwpw', x)
+    return DwPw.apply(x, w_dw, w_pw.reshape(w_pw.shape[0], -1), int(stride), int(padding), int(dilation))
 
 
 def dwpw_bn_eval(x, w_dw, w_pw, gamma, beta, running_mean, running_var, stride=1, padding=0, dilation=1, eps=1e-5):
     """out = batch_norm(conv1x1(depthwise_conv(relu(x)))) with the given running statistics (a BatchNorm in eval mode); w_dw None:
     no depthwise stage.  Tensors as for dwpw_bn, running_mean / running_var (C_out) fp32.  Under torch.no_grad(), or when no
     input requires a gradient, nothing is saved and only the output is written."""
-    if not x.is_cuda:
-        raise L.Ghn3Error('dwpw_bn_eval runs on an MI355X only (no CPU implementation: use the stock torch layers)')
+    _needs_gpu('dwpw_bn_eval', x)
     return DwPwBnEval.apply(x, w_dw, w_pw.reshape(w_pw.shape[0], -1), gamma, beta, running_mean, running_var, int(stride),
                             int(padding), int(dilation), float(eps), _wants_grad(x, w_dw, w_pw, gamma, beta))
+
+
+def reference(x, w_dw, w_pw, gamma, beta, stride=1, padding=0, dilation=1, eps=1e-5):
+    """The four stock layers the op replaces (ops.py:205-212), functional form -- the parity reference of the tests."""
+    y = F.conv2d(F.relu(x), w_dw, None, stride, padding, dilation, groups=x.shape[1])
+    zz = F.conv2d(y, w_pw.reshape(w_pw.shape[0], -1, 1, 1))
+    return F.batch_norm(zz, None, None, gamma, beta, True, 0.1, eps)
 
 
 class Depthwise(torch.autograd.Function):
@@ -368,11 +389,7 @@ class Depthwise(torch.autograd.Function):
 
     @staticmethod
     def applicable(x, w_dw, stride, pad, dil):
-        if not (enabled() and torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
-            return False
-        if _autocast_excludes():
-            return False
-        if not (torch.is_tensor(w_dw) and w_dw.is_cuda and w_dw.dtype == torch.float32 and w_dw.dim() == 4):
+        if not (_native_input(x) and _f32_cuda(w_dw) and w_dw.dim() == 4):
             return False
         C, ks = x.shape[1], w_dw.shape[-1]
         if not (C % 4 == 0 and C <= DW_MAX and ks <= 7 and tuple(w_dw.shape) == (C, 1, ks, ks) and stride > 0 and dil > 0 and
@@ -401,11 +418,8 @@ class Depthwise(torch.autograd.Function):
         d = _desc(xc, int(xc.shape[1]), int(wd.shape[-1]), stride, pad, dil, 0.0)
         do = dout.contiguous(memory_format=torch.channels_last)
         dx = torch.empty_like(xc)
-        # (one allocation for the weight gradient and the scratch area, as DwPw)
-        n_par = (wd.numel() + 63) // 64 * 64
-        buf = torch.empty(n_par + _scratch_floats('ghn3_dw_scratch_floats', d, 1), dtype=torch.float32, device=xc.device)
-        dwd = buf[:wd.numel()].view(wd.shape)
-        L._check(lib.ghn3_dw_bwd(ctypes.byref(d), _ptr(do), _ptr(xc), _ptr(wd), _ptr(dx), _ptr(dwd), _ptr(buf[n_par:]), _stream()),
+        (dwd,), scratch = _carve(xc, _scratch_floats('ghn3_dw_scratch_floats', d, 1), wd.shape)
+        L._check(lib.ghn3_dw_bwd(ctypes.byref(d), _ptr(do), _ptr(xc), _ptr(wd), _ptr(dx), _ptr(dwd), _ptr(scratch), _stream()),
                  'ghn3_dw_bwd')
         return dx, dwd, None, None, None
 
@@ -413,11 +427,11 @@ class Depthwise(torch.autograd.Function):
 def depthwise_relu(x, w_dw, stride=1, padding=0, dilation=1):
     """depthwise_conv(relu(x)): x (N, C, H, W) fp32 CUDA tensor (channels_last preferred), w_dw (C, 1, ks, ks); the result is a
     channels_last tensor."""
-    if not x.is_cuda:
-        raise L.Ghn3Error('depthwise_relu runs on an MI355X only (no CPU implementation: use the stock torch layers)')
+    _needs_gpu('depthwise_relu', x)
     return Depthwise.apply(x, w_dw, int(stride), int(padding), int(dilation))
 
 
+# ---- [ReLU ->] dense kh x kw convolution [-> norm]: one forward and one backward for the three members -----------------------
 class _ConvDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ('N', 'H', 'W', 'C_in', 'C_out', 'kh', 'kw', 'stride_h', 'stride_w', 'pad_h', 'pad_w',
                                               'dil', 'Ho', 'Wo', 'relu')] + [('eps', ctypes.c_float)]
@@ -435,14 +449,16 @@ DWPW_MAX = 512                    # widest side of the fused depthwise + pointwi
 DW_MAX = 16384                    # widest stand-alone depthwise op
 SE_MAX, SE_NARROW = 4096, 1024    # squeeze-and-excitation: C and J
 
+# norm mode -> (forward, backward, scratch size) of the C side: the no-norm member is ghn3_conv_bn_* with GHN3_CONV_NO_NORM
+_CONV = {'batch': ('ghn3_conv_bn_fwd', 'ghn3_conv_bn_bwd', 'ghn3_conv_scratch_floats'),
+         'none': ('ghn3_conv_bn_fwd', 'ghn3_conv_bn_bwd', 'ghn3_conv_scratch_floats'),
+         'frozen': ('ghn3_conv_frozen_fwd', 'ghn3_conv_frozen_bwd', 'ghn3_conv_frozen_scratch_floats')}
+
 
 def _conv_applicable(x, w):
     """What ConvBn and ConvOnly both ask of the input and the weight: fp32 CUDA tensors of four dimensions within the kernels'
     limits, and none of the switches that keep the layer on the stock path."""
-    if not (enabled() and os.environ.get('GHN3_NATIVE_CONV', '1') != '0' and torch.is_tensor(x) and x.is_cuda and
-            x.dtype == torch.float32 and x.dim() == 4 and not _autocast_excludes()):
-        return False
-    if not (torch.is_tensor(w) and w.is_cuda and w.dtype == torch.float32 and w.dim() == 4):
+    if not (_native_input(x, 'GHN3_NATIVE_CONV') and _f32_cuda(w) and w.dim() == 4):
         return False
     C_in, C_out = x.shape[1], w.shape[0]
     if not (C_in % 4 == 0 and C_out % 4 == 0 and C_in <= CONV_MAX_IN and C_out <= CONV_MAX_OUT and w.shape[1] == C_in and
@@ -468,6 +484,57 @@ def conv_desc_fits(d):
     return d.Ho > 0 and d.Wo > 0 and d.N * d.H * d.W * widest < 2 ** 31 and d.N * d.Ho * d.Wo * widest < 2 ** 31
 
 
+def _conv_forward(ctx, mode, x, w, norm, stride, pad, dil, relu, eps, keep=True):
+    """The forward of ConvBn ('batch': norm = (gamma, beta)), ConvOnly ('none': ()) and ConvBnEval ('frozen': (gamma, beta,
+    running_mean, running_var)).  Returns (out, stats -- None but for 'batch').  z and `keep` as for _dwpw_forward; the no-norm
+    member's result is written where the others write z."""
+    lib = L.load()
+    fwd, _, scratch_fn = _CONV[mode]
+    xc = x.contiguous(memory_format=torch.channels_last)
+    wc = w.contiguous()
+    norm = [t.contiguous() for t in norm]
+    d = _conv_desc(xc, wc, stride, pad, dil, relu, eps, no_norm=mode == 'none')
+    dev, C_out = x.device, int(wc.shape[0])
+    out = torch.empty((d.N, C_out, d.Ho, d.Wo), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
+    z = torch.empty_like(out) if (mode == 'batch' or (mode == 'frozen' and keep)) else None
+    stats = torch.empty(3 * C_out, dtype=torch.float32, device=dev) if mode == 'batch' else None
+    scratch = torch.empty(_scratch_floats(scratch_fn, d, 0), dtype=torch.float32, device=dev)
+    if mode == 'batch':
+        tail, saved = (z, out, stats, scratch), (z, stats, norm[0])
+    elif mode == 'frozen':
+        tail, saved = (z, out, scratch), (z, norm[0], norm[2], norm[3])
+    else:
+        tail, saved = (None, None, out, None, None, scratch), ()
+    L._check(getattr(lib, fwd)(ctypes.byref(d), *_ptrs(xc, wc, *norm, *tail), _stream()), fwd)
+    if keep:
+        ctx.save_for_backward(xc, wc, *saved)
+        ctx.cfg = (stride, pad, dil, relu, eps)
+    return out, stats
+
+
+def _conv_backward(ctx, mode, dout):
+    """The backward of the three members: (dx, dw), and (dgamma, dbeta) with a norm layer."""
+    lib = L.load()
+    _, bwd, scratch_fn = _CONV[mode]
+    xc, wc, *saved = ctx.saved_tensors
+    stride, pad, dil, relu, eps = ctx.cfg
+    d = _conv_desc(xc, wc, stride, pad, dil, relu, eps, no_norm=mode == 'none')
+    do = dout.contiguous(memory_format=torch.channels_last)
+    dx = torch.empty_like(xc)
+    grads, scratch = _carve(xc, _scratch_floats(scratch_fn, d, 1), wc.shape, norm=0 if mode == 'none' else int(wc.shape[0]))
+    if mode == 'batch':
+        (z, stats, g), (dw, db, dg) = saved, grads
+        args = (do, xc, z, stats, wc, g, dx, dw, dg, db, scratch)
+    elif mode == 'frozen':
+        (z, g, rm, rv), (dw, db, dg) = saved, grads
+        args = (do, xc, z, wc, g, rm, rv, dx, dw, dg, db, scratch)
+    else:
+        dw, = grads
+        args = (do, xc, None, None, wc, None, dx, dw, None, None, scratch)
+    L._check(getattr(lib, bwd)(ctypes.byref(d), *_ptrs(*args), _stream()), bwd)
+    return (dx, dw) if mode == 'none' else (dx, dw, dg, db)
+
+
 class ConvBn(torch.autograd.Function):
     """[ReLU ->] dense kh x kw convolution -> BatchNorm (batch statistics) as ONE autograd node on ghn3_conv_bn_fwd / _bwd
     (round 6: `ReLUConvBN` with a k x k kernel, ops.py:180-198).  Same conventions as DwPwBn: channels_last storage inside,
@@ -475,88 +542,32 @@ class ConvBn(torch.autograd.Function):
 
     @staticmethod
     def applicable(x, w, gamma, beta, training_stats=True):
-        return bool(training_stats) and all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in (gamma, beta)) and \
-            _conv_applicable(x, w) and gamma.numel() == w.shape[0]
+        return bool(training_stats) and _f32_cuda(gamma, beta) and _conv_applicable(x, w) and gamma.numel() == w.shape[0]
 
     @staticmethod
     def forward(ctx, x, w, gamma, beta, stride, pad, dil, relu, eps):
-        lib = L.load()
-        xc = x.contiguous(memory_format=torch.channels_last)
-        wc, g, b = w.contiguous(), gamma.contiguous(), beta.contiguous()
-        d = _conv_desc(xc, wc, stride, pad, dil, relu, eps)
-        dev, C_out = x.device, int(wc.shape[0])
-        out = torch.empty((d.N, C_out, d.Ho, d.Wo), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
-        z = torch.empty_like(out)
-        stats = torch.empty(3 * C_out, dtype=torch.float32, device=dev)
-        scratch = torch.empty(_scratch_floats('ghn3_conv_scratch_floats', d, 0), dtype=torch.float32, device=dev)
-        stream = _stream()
-        L._check(lib.ghn3_conv_bn_fwd(ctypes.byref(d), _ptr(xc), _ptr(wc), _ptr(g), _ptr(b), _ptr(z), _ptr(out), _ptr(stats),
-                                      _ptr(scratch), stream), 'ghn3_conv_bn_fwd')
-        ctx.save_for_backward(xc, z, stats, wc, g)
-        ctx.cfg = (stride, pad, dil, relu, eps)
+        out, stats = _conv_forward(ctx, 'batch', x, w, (gamma, beta), stride, pad, dil, relu, eps)
         ctx.mark_non_differentiable(stats)
         return out, stats
 
     @staticmethod
     def backward(ctx, dout, _dstats):
-        lib = L.load()
-        xc, z, stats, wc, g = ctx.saved_tensors
-        stride, pad, dil, relu, eps = ctx.cfg
-        d = _conv_desc(xc, wc, stride, pad, dil, relu, eps)
-        dev, C_out = xc.device, int(wc.shape[0])
-        do = dout.contiguous(memory_format=torch.channels_last)
-        dx = torch.empty_like(xc)
-        n_par = wc.numel() + 2 * C_out
-        buf = torch.empty((n_par + 63) // 64 * 64 + _scratch_floats('ghn3_conv_scratch_floats', d, 1), dtype=torch.float32, device=dev)
-        dw = buf[:wc.numel()].view(wc.shape)
-        db = buf[wc.numel():wc.numel() + C_out]              # (dbeta directly followed by dgamma: the kernels' own pair of sums)
-        dg = buf[wc.numel() + C_out:n_par]
-        scratch = buf[(n_par + 63) // 64 * 64:]
-        stream = _stream()
-        L._check(lib.ghn3_conv_bn_bwd(ctypes.byref(d), _ptr(do), _ptr(xc), _ptr(z), _ptr(stats), _ptr(wc), _ptr(g), _ptr(dx), _ptr(dw),
-                                      _ptr(dg), _ptr(db), _ptr(scratch), stream), 'ghn3_conv_bn_bwd')
-        return dx, dw, dg, db, None, None, None, None, None
+        return _conv_backward(ctx, 'batch', dout) + (None,) * 5
 
 
 class ConvOnly(torch.autograd.Function):
     """[ReLU ->] dense kh x kw convolution WITHOUT a norm layer (ghn3_conv_bn_fwd / _bwd with GHN3_CONV_NO_NORM): the first half
     of the 1 x k / k x 1 pair of `ReLUConvBN(double=True)` (ops.py:186-190).  Same storage conventions as ConvBn."""
 
-    @staticmethod
-    def applicable(x, w):
-        return _conv_applicable(x, w)
+    applicable = staticmethod(_conv_applicable)
 
     @staticmethod
     def forward(ctx, x, w, stride, pad, dil, relu):
-        lib = L.load()
-        xc = x.contiguous(memory_format=torch.channels_last)
-        wc = w.contiguous()
-        d = _conv_desc(xc, wc, stride, pad, dil, relu, 0.0, no_norm=True)
-        z = torch.empty((d.N, int(wc.shape[0]), d.Ho, d.Wo), dtype=torch.float32, device=x.device,
-                        memory_format=torch.channels_last)
-        scratch = torch.empty(_scratch_floats('ghn3_conv_scratch_floats', d, 0), dtype=torch.float32, device=x.device)
-        stream = _stream()
-        L._check(lib.ghn3_conv_bn_fwd(ctypes.byref(d), _ptr(xc), _ptr(wc), None, None, _ptr(z), None, None, _ptr(scratch), stream),
-                 'ghn3_conv_bn_fwd')
-        ctx.save_for_backward(xc, wc)
-        ctx.cfg = (stride, pad, dil, relu)
-        return z
+        return _conv_forward(ctx, 'none', x, w, (), stride, pad, dil, relu, 0.0)[0]
 
     @staticmethod
     def backward(ctx, dz):
-        lib = L.load()
-        xc, wc = ctx.saved_tensors
-        stride, pad, dil, relu = ctx.cfg
-        d = _conv_desc(xc, wc, stride, pad, dil, relu, 0.0, no_norm=True)
-        do = dz.contiguous(memory_format=torch.channels_last)
-        dx = torch.empty_like(xc)
-        n_par = (wc.numel() + 63) // 64 * 64
-        buf = torch.empty(n_par + _scratch_floats('ghn3_conv_scratch_floats', d, 1), dtype=torch.float32, device=xc.device)
-        dw = buf[:wc.numel()].view(wc.shape)
-        stream = _stream()
-        L._check(lib.ghn3_conv_bn_bwd(ctypes.byref(d), _ptr(do), _ptr(xc), None, None, _ptr(wc), None, _ptr(dx), _ptr(dw), None,
-                                      None, _ptr(buf[n_par:]), stream), 'ghn3_conv_bn_bwd')
-        return dx, dw, None, None, None, None
+        return _conv_backward(ctx, 'none', dz) + (None,) * 4
 
 
 class ConvBnEval(torch.autograd.Function):
@@ -572,58 +583,39 @@ class ConvBnEval(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, gamma, beta, running_mean, running_var, stride, pad, dil, relu, eps, keep_z):
-        lib = L.load()
-        xc = x.contiguous(memory_format=torch.channels_last)
-        wc, g, b = w.contiguous(), gamma.contiguous(), beta.contiguous()
-        rm, rv = running_mean.contiguous(), running_var.contiguous()
-        d = _conv_desc(xc, wc, stride, pad, dil, relu, eps)
-        dev, C_out = x.device, int(wc.shape[0])
-        out = torch.empty((d.N, C_out, d.Ho, d.Wo), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
-        z = torch.empty_like(out) if keep_z else None
-        scratch = torch.empty(_scratch_floats('ghn3_conv_frozen_scratch_floats', d, 0), dtype=torch.float32, device=dev)
-        L._check(lib.ghn3_conv_frozen_fwd(ctypes.byref(d), _ptr(xc), _ptr(wc), _ptr(g), _ptr(b), _ptr(rm), _ptr(rv),
-                                          _ptr(z) if keep_z else None, _ptr(out), _ptr(scratch), _stream()), 'ghn3_conv_frozen_fwd')
-        if keep_z:
-            ctx.save_for_backward(xc, z, wc, g, rm, rv)
-            ctx.cfg = (stride, pad, dil, relu, eps)
-        return out
+        return _conv_forward(ctx, 'frozen', x, w, (gamma, beta, running_mean, running_var), stride, pad, dil, relu, eps, keep_z)[0]
 
     @staticmethod
     def backward(ctx, dout):
-        lib = L.load()
-        xc, z, wc, g, rm, rv = ctx.saved_tensors
-        stride, pad, dil, relu, eps = ctx.cfg
-        d = _conv_desc(xc, wc, stride, pad, dil, relu, eps)
-        dev, C_out = xc.device, int(wc.shape[0])
-        do = dout.contiguous(memory_format=torch.channels_last)
-        dx = torch.empty_like(xc)
-        n_par = wc.numel() + 2 * C_out
-        buf = torch.empty((n_par + 63) // 64 * 64 + _scratch_floats('ghn3_conv_frozen_scratch_floats', d, 1), dtype=torch.float32,
-                          device=dev)
-        dw = buf[:wc.numel()].view(wc.shape)
-        db = buf[wc.numel():wc.numel() + C_out]              # (dbeta directly followed by dgamma: the kernels' own pair of sums)
-        dg = buf[wc.numel() + C_out:n_par]
-        scratch = buf[(n_par + 63) // 64 * 64:]
-        L._check(lib.ghn3_conv_frozen_bwd(ctypes.byref(d), _ptr(do), _ptr(xc), _ptr(z), _ptr(wc), _ptr(g), _ptr(rm), _ptr(rv), _ptr(dx),
-                                          _ptr(dw), _ptr(dg), _ptr(db), _ptr(scratch), _stream()), 'ghn3_conv_frozen_bwd')
-        return dx, dw, dg, db, None, None, None, None, None, None, None, None
+        return _conv_backward(ctx, 'frozen', dout) + (None,) * 8
+
+
+def conv_bn(x, w, gamma, beta, stride=1, padding=0, dilation=1, relu=True, eps=1e-5):
+    """out = batch_norm(conv2d(relu(x) if relu else x, w)) with batch statistics; returns (out, stats) as dwpw_bn does.
+    x: (N, C, H, W) fp32 CUDA tensor (channels_last preferred), w (C_out, C, kh, kw)."""
+    _needs_gpu('conv_bn', x)
+    return ConvBn.apply(x, w, gamma, beta, _pair(stride), _pair(padding), int(dilation), bool(relu), float(eps))
+
+
+def conv_only(x, w, stride=1, padding=0, dilation=1, relu=False):
+    """conv2d(relu(x) if relu else x, w) on the dense-convolution kernels (no bias, groups = 1)."""
+    _needs_gpu('conv_only', x)
+    return ConvOnly.apply(x, w, _pair(stride), _pair(padding), int(dilation), bool(relu))
 
 
 def conv_bn_eval(x, w, gamma, beta, running_mean, running_var, stride=1, padding=0, dilation=1, relu=True, eps=1e-5):
     """out = batch_norm(conv2d(relu(x) if relu else x, w)) with the given running statistics (a BatchNorm in eval mode).  Tensors
     as for conv_bn, running_mean / running_var (C_out) fp32.  Under torch.no_grad(), or when no input requires a gradient, nothing
     is saved and only the output is written."""
-    if not x.is_cuda:
-        raise L.Ghn3Error('conv_bn_eval runs on an MI355X only (no CPU implementation: use the stock torch layers)')
+    _needs_gpu('conv_bn_eval', x)
     return ConvBnEval.apply(x, w, gamma, beta, running_mean, running_var, _pair(stride), _pair(padding), int(dilation), bool(relu),
                             float(eps), _wants_grad(x, w, gamma, beta))
 
 
-def conv_only(x, w, stride=1, padding=0, dilation=1, relu=False):
-    """conv2d(relu(x) if relu else x, w) on the dense-convolution kernels (no bias, groups = 1)."""
-    if not x.is_cuda:
-        raise L.Ghn3Error('conv_only runs on an MI355X only (no CPU implementation: use the stock torch layers)')
-    return ConvOnly.apply(x, w, _pair(stride), _pair(padding), int(dilation), bool(relu))
+def conv_reference(x, w, gamma, beta, stride=1, padding=0, dilation=1, relu=True, eps=1e-5):
+    """The stock layers ConvBn replaces (ops.py:186-193), functional form -- the parity reference of the tests."""
+    y = F.conv2d(F.relu(x) if relu else x, w, None, stride, padding, dilation)
+    return F.batch_norm(y, None, None, gamma, beta, True, 0.1, eps)
 
 
 class _PatchDesc(ctypes.Structure):
@@ -654,10 +646,7 @@ class PatchEmbed(torch.autograd.Function):
     @staticmethod
     def applicable(x, w, stride, padding=0, dilation=1):
         """The limits of the C side (check_pdesc), so that a layer that passes never raises in the middle of a network."""
-        if not (enabled() and os.environ.get('GHN3_NATIVE_CONV', '1') != '0' and torch.is_tensor(x) and x.is_cuda and
-                x.dtype == torch.float32 and x.dim() == 4 and not _autocast_excludes()):
-            return False
-        if not (torch.is_tensor(w) and w.is_cuda and w.dtype == torch.float32 and w.dim() == 4):
+        if not (_native_input(x, 'GHN3_NATIVE_CONV') and _f32_cuda(w) and w.dim() == 4):
             return False
         if isinstance(padding, str) or _pair(padding) != (0, 0) or _pair(dilation) != (1, 1):
             return False
@@ -695,8 +684,7 @@ class PatchEmbed(torch.autograd.Function):
         dw = torch.empty_like(wc) if ctx.needs_input_grad[1] else None      # (a tensor of its own: it becomes a leaf's .grad)
         n = _scratch_floats('ghn3_patch_scratch_floats', d, 1)
         scratch = torch.empty(n, dtype=torch.float32, device=xc.device) if (n and dw is not None) else None
-        L._check(lib.ghn3_patch_bwd(ctypes.byref(d), _ptr(do), _ptr(xc), _ptr(wc), None if dx is None else _ptr(dx),
-                                    None if dw is None else _ptr(dw), None if scratch is None else _ptr(scratch), _stream()),
+        L._check(lib.ghn3_patch_bwd(ctypes.byref(d), _ptr(do), _ptr(xc), _ptr(wc), _ptr(dx), _ptr(dw), _ptr(scratch), _stream()),
                  'ghn3_patch_bwd')
         return dx, dw, None, None
 
@@ -705,17 +693,8 @@ def patch_embed(x, w, stride):
     """conv2d(x, w, stride=stride) for non-overlapping windows (see PatchEmbed); x (N, C_in <= 4, H, W) fp32 CUDA tensor, w (C_out,
     C_in, kh, kw); the result is a channels_last tensor.  Under torch.no_grad(), or when neither input requires a gradient, nothing
     is saved."""
-    if not x.is_cuda:
-        raise L.Ghn3Error('patch_embed runs on an MI355X only (no CPU implementation: use the stock torch layers)')
+    _needs_gpu('patch_embed', x)
     return PatchEmbed.apply(x, w, _pair(stride), _wants_grad(x, w))
-
-
-def conv_bn(x, w, gamma, beta, stride=1, padding=0, dilation=1, relu=True, eps=1e-5):
-    """out = batch_norm(conv2d(relu(x) if relu else x, w)) with batch statistics; returns (out, stats) as dwpw_bn does.
-    x: (N, C, H, W) fp32 CUDA tensor (channels_last preferred), w (C_out, C, kh, kw)."""
-    if not x.is_cuda:
-        raise L.Ghn3Error('conv_bn runs on an MI355X only (no CPU implementation: use the stock torch layers)')
-    return ConvBn.apply(x, w, gamma, beta, _pair(stride), _pair(padding), int(dilation), bool(relu), float(eps))
 
 
 class SqueezeExcite(torch.autograd.Function):
@@ -724,10 +703,7 @@ class SqueezeExcite(torch.autograd.Function):
 
     @staticmethod
     def applicable(x, w1, b1, w2, b2):
-        if not (enabled() and os.environ.get('GHN3_NATIVE_SE', '1') != '0' and torch.is_tensor(x) and x.is_cuda and
-                x.dtype == torch.float32 and x.dim() == 4 and not _autocast_excludes()):
-            return False
-        if not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in (w1, b1, w2, b2)):
+        if not (_native_input(x, 'GHN3_NATIVE_SE') and _f32_cuda(w1, b1, w2, b2)):
             return False
         C, J = x.shape[1], w1.shape[0]
         if not (C % 4 == 0 and C <= SE_MAX and J <= SE_MAX and tuple(w1.shape) == (J, C) and tuple(w2.shape) == (C, J) and
@@ -757,21 +733,15 @@ class SqueezeExcite(torch.autograd.Function):
         J = int(w1c.shape[0])
         do = dy.contiguous(memory_format=torch.channels_last)
         dx = torch.empty_like(xc)
-        n_par = 2 * C * J + C + J
-        buf = torch.empty((n_par + 63) // 64 * 64 + N * (C + J), dtype=torch.float32, device=xc.device)
-        dw1 = buf[:C * J].view(J, C)
-        dw2 = buf[C * J:2 * C * J].view(C, J)
-        db1 = buf[2 * C * J:2 * C * J + J]
-        db2 = buf[2 * C * J + J:n_par]
+        (dw1, dw2, db1, db2), scratch = _carve(xc, N * (C + J), (J, C), (C, J), (J,), (C,))
         L._check(lib.ghn3_se_bwd(N, H * W, C, J, _ptr(do), _ptr(xc), _ptr(w1c), _ptr(w2c), _ptr(save), _ptr(dx), _ptr(dw1), _ptr(db1),
-                                 _ptr(dw2), _ptr(db2), _ptr(buf[(n_par + 63) // 64 * 64:]), _stream()), 'ghn3_se_bwd')
+                                 _ptr(dw2), _ptr(db2), _ptr(scratch), _stream()), 'ghn3_se_bwd')
         return dx, dw1, db1, dw2, db2
 
 
 def se_layer(x, w1, b1, w2, b2):
     """Squeeze-and-excitation with a hard-swish gate on the fused op: x (N, C, H, W) fp32 CUDA; w1 (J, C), b1 (J), w2 (C, J), b2 (C)."""
-    if not x.is_cuda:
-        raise L.Ghn3Error('se_layer runs on an MI355X only (no CPU implementation: use the stock torch layers)')
+    _needs_gpu('se_layer', x)
     return SqueezeExcite.apply(x, w1, b1, w2, b2)
 
 
@@ -796,8 +766,7 @@ class Pool2d(torch.autograd.Function):
 
     @staticmethod
     def applicable(x, k, stride, pad):
-        return enabled() and os.environ.get('GHN3_NATIVE_POOL', '1') != '0' and torch.is_tensor(x) and x.is_cuda and \
-            x.dtype == torch.float32 and x.dim() == 4 and not _autocast_excludes() and x.shape[1] % 4 == 0 and \
+        return _native_input(x, 'GHN3_NATIVE_POOL') and x.shape[1] % 4 == 0 and \
             isinstance(k, int) and isinstance(stride, int) and isinstance(pad, int) and 0 < k <= 15 and 2 * pad <= k and \
             stride > 0 and x.shape[2] + 2 * pad >= k and x.shape[3] + 2 * pad >= k and x.numel() < 2 ** 31
 
@@ -809,7 +778,7 @@ class Pool2d(torch.autograd.Function):
         d = _PoolDesc(N, H, W, C, k, stride, pad, (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1, mode)
         y = torch.empty((N, C, d.Ho, d.Wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
         idx = torch.empty(y.numel(), dtype=torch.uint8, device=x.device) if mode else None
-        L._check(lib.ghn3_pool_fwd(ctypes.byref(d), _ptr(xc), _ptr(y), _ptr(idx) if mode else None, _stream()), 'ghn3_pool_fwd')
+        L._check(lib.ghn3_pool_fwd(ctypes.byref(d), _ptr(xc), _ptr(y), _ptr(idx), _stream()), 'ghn3_pool_fwd')
         ctx.desc, ctx.idx = d, idx
         return y
 
@@ -819,7 +788,7 @@ class Pool2d(torch.autograd.Function):
         d = ctx.desc
         do = dy.contiguous(memory_format=torch.channels_last)
         dx = torch.empty((d.N, d.C, d.H, d.W), dtype=torch.float32, device=dy.device, memory_format=torch.channels_last)
-        L._check(lib.ghn3_pool_bwd(ctypes.byref(d), _ptr(do), _ptr(ctx.idx) if d.mode else None, _ptr(dx), _stream()), 'ghn3_pool_bwd')
+        L._check(lib.ghn3_pool_bwd(ctypes.byref(d), _ptr(do), _ptr(ctx.idx), _ptr(dx), _stream()), 'ghn3_pool_bwd')
         return dx, None, None, None, None
 
 
@@ -838,247 +807,34 @@ def run_pool(x, kernel_size, stride, padding, mode):
     return Pool2d.apply(x, k, s, p, mode)
 
 
-def conv_reference(x, w, gamma, beta, stride=1, padding=0, dilation=1, relu=True, eps=1e-5):
-    """The stock layers ConvBn replaces (ops.py:186-193), functional form -- the parity reference of the tests."""
-    y = F.conv2d(F.relu(x) if relu else x, w, None, stride, padding, dilation)
-    return F.batch_norm(y, None, None, gamma, beta, True, 0.1, eps)
+# ---- the runners: a block's layers -> the member of a family that fits its norm slot, or the stock layers --------------------
+_Slot = collections.namedtuple('_Slot', 'kind gamma beta mean var eps bn update')
+_BARE = _Slot('none', None, None, None, None, 0.0, None, False)       # (no norm layer: an Identity, or no norm slot at all)
+_STOCK = _Slot('stock', None, None, None, None, 0.0, None, False)
 
 
-def run_conv_block(layers, x, keep_layout=False):
-    """[ReLU, k x k Conv2d, BatchNorm2d] -- `ReLUConvBN` (ops.py:180-198) -- on the fused dense-convolution op where it applies,
-    else layer by layer.  Same layout contract as run_block.  An Identity in the norm slot (norm=None): ConvOnly with the ReLU."""
-    relu, conv, bn = layers
+def _norm_slot(bn):
+    """What a block's norm slot asks of the op families in this call, decided once: kind 'none' (an Identity, `_no_norm`: the
+    members without a norm layer), 'batch' (batch statistics: DwPwBn / ConvBn; `update`: the layer's running statistics follow,
+    as torch's would), 'frozen' (running statistics outside training, `_frozen_norm`: DwPwBnEval / ConvBnEval) or 'stock' (leave
+    the block to the stock layers: a layer without `eps`, or one of the two switches says so), with the tensors the members
+    read."""
+    if _no_norm(bn):
+        return _BARE
     gamma, beta, has_run, batch_stats = _norm_inputs(bn)
-    w = getattr(conv, 'weight', None)
-    if _no_norm(bn) and _plain_conv(conv) and ConvOnly.applicable(x, w):
-        out = conv_only(x, w, conv.stride, conv.padding, _pair(conv.dilation)[0], relu=True)
-        return _hand_on(out, keep_layout, conv, bn)
-    if _frozen_norm(batch_stats) and hasattr(bn, 'eps') and _plain_conv(conv) and \
-            ConvBnEval.applicable(x, w, gamma, beta, bn.running_mean, bn.running_var, conv.stride, conv.padding,
-                                  _pair(conv.dilation)[0]):
-        # (running statistics in eval mode: the family's member with a frozen norm; the statistics are not touched)
-        out = conv_bn_eval(x, w, gamma, beta, bn.running_mean, bn.running_var, conv.stride, conv.padding,
-                           _pair(conv.dilation)[0], True, bn.eps)
-        return _hand_on(out, keep_layout, conv, bn)
-    ok = hasattr(bn, 'eps') and _plain_conv(conv) and ConvBn.applicable(x, w, gamma, beta, batch_stats)
-    if not ok:
-        for m in layers:
-            x = m(x)
-        return x
-    out, stats = conv_bn(x, w, gamma, beta, conv.stride, conv.padding, _pair(conv.dilation)[0], True, bn.eps)
-    _update_running_stats(bn, stats, out, has_run)
-    return _hand_on(out, keep_layout, conv, bn)
+    if not hasattr(bn, 'eps'):
+        return _STOCK
+    if batch_stats:
+        return _Slot('batch', gamma, beta, None, None, bn.eps, bn,
+                     has_run and getattr(bn, 'training', True) and getattr(bn, 'track_running_stats', False))
+    if _frozen_norm(batch_stats):
+        return _Slot('frozen', gamma, beta, bn.running_mean, bn.running_var, bn.eps, bn, False)
+    return _STOCK
 
 
-def _plain_conv(conv):
-    """A bias-free, ungrouped convolution with numeric padding and one dilation for both axes (what the dense kernels take)."""
-    return hasattr(conv, 'kernel_size') and getattr(conv, 'bias', None) is None and not isinstance(conv.padding, str) and \
-        getattr(conv, 'groups', 1) == 1 and torch.is_tensor(getattr(conv, 'weight', None)) and \
-        len(set(_pair(getattr(conv, 'dilation', 1)))) == 1
-
-
-def run_conv_pair_block(layers, x, keep_layout=False):
-    """[ReLU, 1 x k Conv2d, k x 1 Conv2d, BatchNorm2d] -- `ReLUConvBN(double=True)`, the `conv_1x7_7x1` op (ops.py:186-190,
-    298) -- as two dense-convolution nodes: ReLU + the first convolution alone (ConvOnly), then the second one with the norm
-    (ConvBn without a ReLU); the intermediate stays NHWC.  Else layer by layer."""
-    relu, conv_a, conv_b, bn = layers
-    gamma, beta, has_run, batch_stats = _norm_inputs(bn)
-    if _no_norm(bn) and _plain_conv(conv_a) and _plain_conv(conv_b) and ConvOnly.applicable(x, conv_a.weight) and \
-            conv_b.weight.shape[1] == conv_a.weight.shape[0]:
-        # (norm=None: two convolution-only nodes; the second one's input is checked on a stand-in, as below)
-        probe = x if conv_a.weight.shape[0] == x.shape[1] else x.new_empty((1, conv_a.weight.shape[0], 1, 1))
-        if ConvOnly.applicable(probe, conv_b.weight):
-            y = conv_only(x, conv_a.weight, conv_a.stride, conv_a.padding, _pair(conv_a.dilation)[0], relu=True)
-            out = conv_only(y, conv_b.weight, conv_b.stride, conv_b.padding, _pair(conv_b.dilation)[0], relu=False)
-            return _hand_on(out, keep_layout, conv_a, conv_b, bn)
-    ok = hasattr(bn, 'eps') and _plain_conv(conv_a) and _plain_conv(conv_b) and ConvOnly.applicable(x, conv_a.weight) and \
-        conv_b.weight.shape[1] == conv_a.weight.shape[0]
-    if ok and _frozen_norm(batch_stats):
-        # (running statistics in eval mode: ConvOnly, then the second convolution with the frozen norm.  The second node's input
-        # has conv_a's channel count, x's type and the first convolution's output size: checked on a stand-in of that shape)
-        da = _conv_desc(x, conv_a.weight, conv_a.stride, conv_a.padding, _pair(conv_a.dilation)[0], True, 0.0)
-        if conv_desc_fits(da):
-            probe = x.new_empty(1).expand(da.N, da.C_out, da.Ho, da.Wo)        # (one element, no storage of that size)
-            if ConvBnEval.applicable(probe, conv_b.weight, gamma, beta, bn.running_mean, bn.running_var, conv_b.stride,
-                                     conv_b.padding, _pair(conv_b.dilation)[0]):
-                y = conv_only(x, conv_a.weight, conv_a.stride, conv_a.padding, _pair(conv_a.dilation)[0], relu=True)
-                out = conv_bn_eval(y, conv_b.weight, gamma, beta, bn.running_mean, bn.running_var, conv_b.stride, conv_b.padding,
-                                   _pair(conv_b.dilation)[0], False, bn.eps)
-                return _hand_on(out, keep_layout, conv_a, conv_b, bn)
-    if ok:
-        # (the second node's input has conv_a's channel count and x's type: checked on a stand-in of that shape)
-        probe = x if conv_a.weight.shape[0] == x.shape[1] else x.new_empty((1, conv_a.weight.shape[0], 1, 1))
-        ok = ConvBn.applicable(probe, conv_b.weight, gamma, beta, batch_stats)
-    if not ok:
-        for m in layers:
-            x = m(x)
-        return x
-    y = conv_only(x, conv_a.weight, conv_a.stride, conv_a.padding, _pair(conv_a.dilation)[0], relu=True)
-    out, stats = conv_bn(y, conv_b.weight, gamma, beta, conv_b.stride, conv_b.padding, _pair(conv_b.dilation)[0], False, bn.eps)
-    _update_running_stats(bn, stats, out, has_run)
-    return _hand_on(out, keep_layout, conv_a, conv_b, bn)
-
-
-def run_conv_layer(conv, x):
-    """A bare Conv2d without bias (the patch embedding of the ViT-style networks, ops.py:296 `conv_stride`), handing an NCHW
-    tensor on: up to 7 x 7 (CIFAR-sized inputs: 3 x 3, stride 3) on the dense-convolution op -- 3-channel images padded as in
-    run_layer_seq --, a larger kernel with non-overlapping windows (ImageNet-sized inputs: 16 x 16, stride 16) on the patch-embedding
-    op, which reads the image as it is; else the stock layer.  GHN3_NATIVE_STEM=0 keeps the stock layer, as for the other stems."""
-    if _plain_conv(conv) and torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and os.environ.get('GHN3_NATIVE_STEM', '1') != '0':
-        w, xin = conv.weight, x
-        if w.dim() == 4 and max(w.shape[2], w.shape[3]) > 7:              # (what ConvOnly refuses for its kernel size)
-            if PatchEmbed.applicable(x, w, conv.stride, conv.padding, conv.dilation):
-                return patch_embed(x, w, conv.stride).contiguous(memory_format=torch.contiguous_format)
-            return conv(x)
-        if x.shape[1] == 3 and w.shape[1] == 3:
-            xin, w = F.pad(x, (0, 0, 0, 0, 0, 1)), F.pad(w, (0, 0, 0, 0, 0, 1))
-        if ConvOnly.applicable(xin, w):
-            y = conv_only(xin, w, conv.stride, conv.padding, _pair(conv.dilation)[0], relu=False)
-            return y.contiguous(memory_format=torch.contiguous_format)
-    return conv(x)
-
-
-def _is_kind(m, name):
-    return type(m).__name__ == name
-
-
-def run_layer_seq(seq, x):
-    """A stem (`nn.Sequential` of Conv2d / BatchNorm2d / ReLU / MaxPool2d / Identity, ops.py:443-463) with every
-    [Conv2d, BatchNorm2d] and [ReLU, Conv2d, BatchNorm2d] window on the fused dense-convolution op and the rest layer by layer
-    (an Identity in the norm slot, norm=None: the same windows on ConvOnly).
-    A 3-channel image (the first convolution of every network) is given a zero fourth channel -- and the weight a zero fourth
-    input slice, through autograd -- because the kernels read channels in groups of four."""
-    layers = list(seq)
-    k, n = 0, len(layers)
-    while k < n:
-        m = layers[k]
-        relu = _is_kind(m, 'ReLU') and k + 2 < n
-        conv = layers[k + 1] if relu else m
-        bn = layers[k + 2] if relu else (layers[k + 1] if k + 1 < n else None)
-        done = False
-        if _is_kind(conv, 'Conv2d') and bn is not None and _no_norm(bn) and _plain_conv(conv) and torch.is_tensor(x) and \
-                x.is_cuda and x.dim() == 4:
-            # the same windows of a norm=None stem, [Conv2d, Identity] and [ReLU, Conv2d, Identity], on the convolution alone
-            w, xin = conv.weight, x
-            if x.shape[1] == 3 and w.shape[1] == 3:
-                xin, w = F.pad(x, (0, 0, 0, 0, 0, 1)), F.pad(w, (0, 0, 0, 0, 0, 1))
-            if ConvOnly.applicable(xin, w):
-                fold = bool(relu)
-                if relu and k == 0 and getattr(m, 'inplace', False):
-                    xin, fold = m(xin), False                  # (the caller's tensor is rewritten, as below: stem1)
-                x = conv_only(xin, w, conv.stride, conv.padding, _pair(conv.dilation)[0], relu=fold)
-                x = _hand_on(x, False, conv, bn)
-                k += 3 if relu else 2
-                done = True
-        elif _is_kind(conv, 'Conv2d') and bn is not None and _is_kind(bn, 'BatchNorm2d') and hasattr(bn, 'eps') and \
-                _plain_conv(conv) and torch.is_tensor(x) and x.is_cuda and x.dim() == 4:
-            w = conv.weight
-            gamma, beta, has_run, batch_stats = _norm_inputs(bn)
-            xin = x
-            if x.shape[1] == 3 and w.shape[1] == 3:
-                xin = F.pad(x, (0, 0, 0, 0, 0, 1))
-                w = F.pad(w, (0, 0, 0, 0, 0, 1))
-            frozen = _frozen_norm(batch_stats) and ConvBnEval.applicable(xin, w, gamma, beta, bn.running_mean, bn.running_var,
-                                                                         conv.stride, conv.padding, _pair(conv.dilation)[0])
-            if frozen:
-                # (running statistics in eval mode: the same windows on the member with a frozen norm, the same rules for the
-                # padded image and an in-place ReLU at the head)
-                fold = bool(relu)
-                if relu and k == 0 and getattr(m, 'inplace', False):
-                    xin, fold = m(xin), False
-                x = conv_bn_eval(xin, w, gamma, beta, bn.running_mean, bn.running_var, conv.stride, conv.padding,
-                                 _pair(conv.dilation)[0], fold, bn.eps)
-                x = _hand_on(x, False, conv, bn)
-                k += 3 if relu else 2
-                done = True
-            elif ConvBn.applicable(xin, w, gamma, beta, batch_stats):
-                fold = bool(relu)
-                if relu and k == 0 and getattr(m, 'inplace', False):
-                    # an in-place ReLU at the head of the sequence rewrites the CALLER's tensor (stem1 of the two-stem networks:
-                    # the cells read relu(stem0's output) afterwards, ops.py:449,545-546): kept as the layer it is
-                    xin, fold = m(xin), False
-                x, stats = conv_bn(xin, w, gamma, beta, conv.stride, conv.padding, _pair(conv.dilation)[0], fold, bn.eps)
-                _update_running_stats(bn, stats, x, has_run)
-                x = _hand_on(x, False, conv, bn)
-                k += 3 if relu else 2
-                done = True
-        if not done:
-            x = m(x)
-            k += 1
-    return x
-
-
-def run_factorized_reduce(relu, conv_1, conv_2, bn, x, stride=2, keep_layout=False):
-    """`FactorizedReduce` (ops.py:163-178: ReLU, two 1 x 1 convolutions of stride 2 on the even and the odd pixel grid, concat,
-    norm) as ONE dense-convolution node: a 2 x 2 kernel of stride 2 whose tap (0, 0) carries conv_1's weights for the first half
-    of the output channels and whose tap (1, 1) carries conv_2's for the second half (the other entries are zeros) reads exactly
-    the pixels the two strided convolutions read.  The 2 x 2 weight is assembled by differentiable torch ops, so the gradients
-    reach conv_1 / conv_2 (views of the GHN's prediction buffer) through autograd.  Returns None when the fused op does not
-    apply (the caller keeps the stock layers)."""
-    w1, w2 = getattr(conv_1, 'weight', None), getattr(conv_2, 'weight', None)
-    gamma, beta, has_run, batch_stats = _norm_inputs(bn)
-    plain = _no_norm(bn)
-    if not (stride == 2 and (plain or hasattr(bn, 'eps')) and torch.is_tensor(w1) and torch.is_tensor(w2) and x.dim() == 4 and
-            x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0 and getattr(conv_1, 'bias', None) is None and
-            getattr(conv_2, 'bias', None) is None and w1.shape == w2.shape and tuple(w1.shape[2:]) == (1, 1)):
-        return None
-    half, C_in = int(w1.shape[0]), int(w1.shape[1])
-    w = torch.zeros(2 * half, C_in, 2, 2, dtype=w1.dtype, device=w1.device)
-    w[:half, :, 0, 0] = w1[:, :, 0, 0]
-    w[half:, :, 1, 1] = w2[:, :, 0, 0]
-    if plain:                                              # (norm=None: the same 2 x 2 convolution alone)
-        if not ConvOnly.applicable(x, w):
-            return None
-        return _hand_on(conv_only(x, w, 2, 0, 1, relu=True), keep_layout, conv_1, conv_2, bn)
-    if _frozen_norm(batch_stats) and ConvBnEval.applicable(x, w, gamma, beta, bn.running_mean, bn.running_var, 2, 0, 1):
-        # (running statistics in eval mode: the same 2 x 2 convolution with the frozen norm)
-        out = conv_bn_eval(x, w, gamma, beta, bn.running_mean, bn.running_var, 2, 0, 1, True, bn.eps)
-        return _hand_on(out, keep_layout, conv_1, conv_2, bn)
-    if not ConvBn.applicable(x, w, gamma, beta, batch_stats):
-        return None
-    out, stats = conv_bn(x, w, gamma, beta, 2, 0, 1, True, bn.eps)
-    _update_running_stats(bn, stats, out, has_run)
-    return _hand_on(out, keep_layout, conv_1, conv_2, bn)
-
-
-def dwpw_bn(x, w_dw, w_pw, gamma, beta, stride=1, padding=0, dilation=1, eps=1e-5):
-    """out = batch_norm(conv1x1(depthwise_conv(relu(x)))) with batch statistics; returns (out, stats) with
-    stats = [mean | 1 / sqrt(var + eps) | biased variance] per output channel.  x: (N, C, H, W) fp32 CUDA tensor
-    (channels_last preferred), w_dw (C, 1, ks, ks), w_pw (C_out, C, 1, 1) or (C_out, C)."""
-    if not x.is_cuda:
-        raise L.Ghn3Error('dwpw_bn runs on an MI355X only (no CPU implementation: use the stock torch layers)')
-    return DwPwBn.apply(x, w_dw, w_pw.reshape(w_pw.shape[0], -1), gamma, beta, int(stride), int(padding), int(dilation),
-                        float(eps))
-
-
-def run_pointwise_block(layers, x, keep_layout=False):
-    """[ReLU, 1 x 1 Conv2d, BatchNorm2d] -- `ReLUConvBN` with a 1 x 1 kernel (ops.py:180-198: the preprocessing layer of every
-    cell, the `conv_1x1` op) -- on the fused op without a depthwise stage where it applies, else layer by layer."""
-    relu, pw, bn = layers
-    w_pw = getattr(pw, 'weight', None)
-    gamma, beta, has_run, batch_stats = _norm_inputs(bn)
-    layer_ok = getattr(pw, 'bias', None) is None and hasattr(pw, 'kernel_size') and \
-        tuple(pw.kernel_size) == (1, 1) and pw.stride[0] == pw.stride[1] and not isinstance(pw.padding, str) and \
-        tuple(pw.padding) == (0, 0) and getattr(pw, 'groups', 1) == 1 and torch.is_tensor(w_pw)
-    if _no_norm(bn) and layer_ok and DwPw.applicable(x, None, w_pw, 1):
-        return _hand_on(dwpw(x, None, w_pw, pw.stride[0], 0, 1), keep_layout, pw, bn)
-    if _frozen_norm(batch_stats) and hasattr(bn, 'eps') and layer_ok and \
-            DwPwBnEval.applicable(x, None, w_pw, gamma, beta, bn.running_mean, bn.running_var, 1):
-        # (running statistics in eval mode: the family's member with a frozen norm; the statistics are not touched)
-        out = dwpw_bn_eval(x, None, w_pw, gamma, beta, bn.running_mean, bn.running_var, pw.stride[0], 0, 1, bn.eps)
-        return _hand_on(out, keep_layout, pw, bn)
-    ok = hasattr(bn, 'eps') and layer_ok and DwPwBn.applicable(x, None, w_pw, gamma, beta, 1, batch_stats)
-    if not ok:
-        # (more than 512 channels on either side -- the concatenated states of a cell, the layers of a wide network: the
-        # dense-convolution op takes those)
-        return run_conv_block(layers, x, keep_layout)
-    out, stats = dwpw_bn(x, None, w_pw, gamma, beta, pw.stride[0], 0, 1, bn.eps)
-    _update_running_stats(bn, stats, out, has_run)
-    return _hand_on(out, keep_layout, pw, bn)
-
-
-def _update_running_stats(bn, stats, out, has_run):
-    if has_run and getattr(bn, 'training', True) and getattr(bn, 'track_running_stats', False):
+def _update_running_stats(slot, stats, out):
+    if slot.update:
+        bn = slot.bn
         with torch.no_grad():
             C = bn.weight.numel()
             n = out.numel() // C
@@ -1094,19 +850,190 @@ def _update_running_stats(bn, stats, out, has_run):
             bn.running_var.mul_(1 - mom).add_(stats[2 * C:] * (n / max(n - 1, 1)), alpha=mom)
 
 
-def reference(x, w_dw, w_pw, gamma, beta, stride=1, padding=0, dilation=1, eps=1e-5):
-    """The four stock layers the op replaces (ops.py:205-212), functional form -- the parity reference of the tests."""
-    y = F.conv2d(F.relu(x), w_dw, None, stride, padding, dilation, groups=x.shape[1])
-    zz = F.conv2d(y, w_pw.reshape(w_pw.shape[0], -1, 1, 1))
-    return F.batch_norm(zz, None, None, gamma, beta, True, 0.1, eps)
+def _conv_dispatch(x, w, slot, stride, pad, dil, relu, first=None):
+    """[ReLU ->] convolution -> the norm slot on the member of the dense-convolution family the slot names, where that member
+    applies -- its NHWC output; the running statistics of a batch member are updated --, else None (the caller keeps the stock
+    layers).  `first`: x only stands for the input (its shape, type and device); the real one is first() -- a block's first node,
+    a layer that has to run before --, called once the member is known to apply."""
+    g, b = slot.gamma, slot.beta
+    if slot.kind == 'none':
+        if ConvOnly.applicable(x, w):
+            return conv_only(first() if first else x, w, stride, pad, dil, relu)
+    elif slot.kind == 'frozen':
+        # (running statistics in eval mode: the statistics are not touched)
+        if ConvBnEval.applicable(x, w, g, b, slot.mean, slot.var, stride, pad, dil):
+            return conv_bn_eval(first() if first else x, w, g, b, slot.mean, slot.var, stride, pad, dil, relu, slot.eps)
+    elif slot.kind == 'batch':
+        if ConvBn.applicable(x, w, g, b):
+            out, stats = conv_bn(first() if first else x, w, g, b, stride, pad, dil, relu, slot.eps)
+            _update_running_stats(slot, stats, out)
+            return out
+    return None
 
 
-def _run_wide_block(layers, x, keep_layout):
+def _dwpw_dispatch(x, w_dw, w_pw, slot, stride, pad, dil):
+    """ReLU -> depthwise (w_dw None: none) -> pointwise -> the norm slot on the member of the fused depthwise + pointwise family
+    the slot names; as _conv_dispatch."""
+    ks = w_dw.shape[-1] if torch.is_tensor(w_dw) else 1
+    g, b = slot.gamma, slot.beta
+    if slot.kind == 'none':
+        if DwPw.applicable(x, w_dw, w_pw, ks):
+            return dwpw(x, w_dw, w_pw, stride, pad, dil)
+    elif slot.kind == 'frozen':
+        if DwPwBnEval.applicable(x, w_dw, w_pw, g, b, slot.mean, slot.var, ks):
+            return dwpw_bn_eval(x, w_dw, w_pw, g, b, slot.mean, slot.var, stride, pad, dil, slot.eps)
+    elif slot.kind == 'batch':
+        if DwPwBn.applicable(x, w_dw, w_pw, g, b, ks):
+            out, stats = dwpw_bn(x, w_dw, w_pw, g, b, stride, pad, dil, slot.eps)
+            _update_running_stats(slot, stats, out)
+            return out
+    return None
+
+
+def _stand_in(x, N, C, H, W):
+    """The input of a block's second node before the first one has run, for `applicable`: x's type and device, the
+    intermediate's true shape, one element (no storage of that size)."""
+    return x.new_empty(1).expand(N, C, H, W)
+
+
+def _stock(layers, x):
+    for m in layers:
+        x = m(x)
+    return x
+
+
+def _plain_conv(conv):
+    """A bias-free, ungrouped convolution with numeric padding and one dilation for both axes (what the dense kernels take)."""
+    return hasattr(conv, 'kernel_size') and getattr(conv, 'bias', None) is None and not isinstance(conv.padding, str) and \
+        getattr(conv, 'groups', 1) == 1 and torch.is_tensor(getattr(conv, 'weight', None)) and \
+        len(set(_pair(getattr(conv, 'dilation', 1)))) == 1
+
+
+def _image_pad(x, w):
+    """A 3-channel image (the first convolution of every network) is given a zero fourth channel -- and the weight a zero fourth
+    input slice, through autograd -- because the kernels read channels in groups of four."""
+    if x.shape[1] == 3 and w.shape[1] == 3:
+        return F.pad(x, (0, 0, 0, 0, 0, 1)), F.pad(w, (0, 0, 0, 0, 0, 1))
+    return x, w
+
+
+def run_conv_block(layers, x, keep_layout=False):
+    """[ReLU, k x k Conv2d, BatchNorm2d] -- `ReLUConvBN` (ops.py:180-198) -- on the fused dense-convolution op where it applies,
+    else layer by layer.  Same layout contract as run_block.  An Identity in the norm slot (norm=None): ConvOnly with the ReLU."""
+    relu, conv, bn = layers
+    out = None
+    if _plain_conv(conv):
+        out = _conv_dispatch(x, conv.weight, _norm_slot(bn), conv.stride, conv.padding, _pair(conv.dilation)[0], True)
+    return _stock(layers, x) if out is None else _hand_on(out, keep_layout, conv, bn)
+
+
+def run_conv_pair_block(layers, x, keep_layout=False):
+    """[ReLU, 1 x k Conv2d, k x 1 Conv2d, BatchNorm2d] -- `ReLUConvBN(double=True)`, the `conv_1x7_7x1` op (ops.py:186-190,
+    298) -- as two dense-convolution nodes: ReLU + the first convolution alone (ConvOnly), then the second one with the norm
+    slot's member, without a ReLU; the intermediate stays NHWC.  Else layer by layer."""
+    relu, conv_a, conv_b, bn = layers
+    out = None
+    if _plain_conv(conv_a) and _plain_conv(conv_b) and ConvOnly.applicable(x, conv_a.weight) and \
+            conv_b.weight.shape[1] == conv_a.weight.shape[0]:
+        a = (conv_a.weight, conv_a.stride, conv_a.padding, _pair(conv_a.dilation)[0], True)
+        da = _conv_desc(x, *a, 0.0)
+        if conv_desc_fits(da):
+            # (the second node's input has conv_a's channel count, x's type and the first convolution's output size)
+            out = _conv_dispatch(_stand_in(x, da.N, da.C_out, da.Ho, da.Wo), conv_b.weight, _norm_slot(bn), conv_b.stride,
+                                 conv_b.padding, _pair(conv_b.dilation)[0], False, first=lambda: conv_only(x, *a))
+    return _stock(layers, x) if out is None else _hand_on(out, keep_layout, conv_a, conv_b, bn)
+
+
+def run_conv_layer(conv, x):
+    """A bare Conv2d without bias (the patch embedding of the ViT-style networks, ops.py:296 `conv_stride`), handing an NCHW
+    tensor on: up to 7 x 7 (CIFAR-sized inputs: 3 x 3, stride 3) on the dense-convolution op -- 3-channel images padded as in
+    run_layer_seq --, a larger kernel with non-overlapping windows (ImageNet-sized inputs: 16 x 16, stride 16) on the patch-embedding
+    op, which reads the image as it is; else the stock layer.  GHN3_NATIVE_STEM=0 keeps the stock layer, as for the other stems."""
+    if _plain_conv(conv) and torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and os.environ.get('GHN3_NATIVE_STEM', '1') != '0':
+        w, y = conv.weight, None
+        if w.dim() == 4 and max(w.shape[2], w.shape[3]) > 7:              # (what ConvOnly refuses for its kernel size)
+            if PatchEmbed.applicable(x, w, conv.stride, conv.padding, conv.dilation):
+                y = patch_embed(x, w, conv.stride)
+        else:
+            y = _conv_dispatch(*_image_pad(x, w), _BARE, conv.stride, conv.padding, _pair(conv.dilation)[0], False)
+        if y is not None:
+            return y.contiguous(memory_format=torch.contiguous_format)
+    return conv(x)
+
+
+def run_layer_seq(seq, x):
+    """A stem (`nn.Sequential` of Conv2d / BatchNorm2d / ReLU / MaxPool2d / Identity, ops.py:443-463) with every
+    [Conv2d, norm] and [ReLU, Conv2d, norm] window -- norm a BatchNorm2d, or the Identity of a norm=None stem -- on the
+    dense-convolution member that fits the norm slot and the rest layer by layer; 3-channel images as `_image_pad` says."""
+    layers = list(seq)
+    k, n = 0, len(layers)
+    while k < n:
+        m = layers[k]
+        relu = _is_kind(m, 'ReLU') and k + 2 < n
+        conv = layers[k + 1] if relu else m
+        bn = layers[k + 2] if relu else (layers[k + 1] if k + 1 < n else None)
+        out = None
+        if _is_kind(conv, 'Conv2d') and bn is not None and _plain_conv(conv) and torch.is_tensor(x) and x.is_cuda and x.dim() == 4:
+            slot = _norm_slot(bn)
+            if slot.kind == 'none' or _is_kind(bn, 'BatchNorm2d'):
+                xin, w = _image_pad(x, conv.weight)
+                # an in-place ReLU at the head of the sequence rewrites the CALLER's tensor (stem1 of the two-stem networks:
+                # the cells read relu(stem0's output) afterwards, ops.py:449,545-546): kept as the layer it is
+                head = relu and k == 0 and getattr(m, 'inplace', False)
+                out = _conv_dispatch(xin, w, slot, conv.stride, conv.padding, _pair(conv.dilation)[0], relu and not head,
+                                     first=(lambda: m(xin)) if head else None)
+        if out is None:
+            x = m(x)
+            k += 1
+        else:
+            x = _hand_on(out, False, conv, bn)
+            k += 3 if relu else 2
+    return x
+
+
+def run_factorized_reduce(relu, conv_1, conv_2, bn, x, stride=2, keep_layout=False):
+    """`FactorizedReduce` (ops.py:163-178: ReLU, two 1 x 1 convolutions of stride 2 on the even and the odd pixel grid, concat,
+    norm) as ONE dense-convolution node: a 2 x 2 kernel of stride 2 whose tap (0, 0) carries conv_1's weights for the first half
+    of the output channels and whose tap (1, 1) carries conv_2's for the second half (the other entries are zeros) reads exactly
+    the pixels the two strided convolutions read.  The 2 x 2 weight is assembled by differentiable torch ops, so the gradients
+    reach conv_1 / conv_2 (views of the GHN's prediction buffer) through autograd.  Returns None when the fused op does not
+    apply (the caller keeps the stock layers)."""
+    w1, w2 = getattr(conv_1, 'weight', None), getattr(conv_2, 'weight', None)
+    slot = _norm_slot(bn)
+    if not (stride == 2 and slot.kind != 'stock' and torch.is_tensor(w1) and torch.is_tensor(w2) and
+            x.dim() == 4 and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0 and getattr(conv_1, 'bias', None) is None and
+            getattr(conv_2, 'bias', None) is None and w1.shape == w2.shape and tuple(w1.shape[2:]) == (1, 1)):
+        return None
+    half, C_in = int(w1.shape[0]), int(w1.shape[1])
+    w = torch.zeros(2 * half, C_in, 2, 2, dtype=w1.dtype, device=w1.device)
+    w[:half, :, 0, 0] = w1[:, :, 0, 0]
+    w[half:, :, 1, 1] = w2[:, :, 0, 0]
+    out = _conv_dispatch(x, w, slot, 2, 0, 1, True)
+    return None if out is None else _hand_on(out, keep_layout, conv_1, conv_2, bn)
+
+
+def run_pointwise_block(layers, x, keep_layout=False):
+    """[ReLU, 1 x 1 Conv2d, BatchNorm2d] -- `ReLUConvBN` with a 1 x 1 kernel (ops.py:180-198: the preprocessing layer of every
+    cell, the `conv_1x1` op) -- on the fused op without a depthwise stage where it applies, else as run_conv_block."""
+    relu, pw, bn = layers
+    w_pw = getattr(pw, 'weight', None)
+    out = None
+    if getattr(pw, 'bias', None) is None and hasattr(pw, 'kernel_size') and \
+            tuple(pw.kernel_size) == (1, 1) and pw.stride[0] == pw.stride[1] and not isinstance(pw.padding, str) and \
+            tuple(pw.padding) == (0, 0) and getattr(pw, 'groups', 1) == 1 and torch.is_tensor(w_pw):
+        out = _dwpw_dispatch(x, None, w_pw, _norm_slot(bn), pw.stride[0], 0, 1)
+    if out is None:
+        # (more than 512 channels on either side -- the concatenated states of a cell, the layers of a wide network: the
+        # dense-convolution op takes those)
+        return run_conv_block(layers, x, keep_layout)
+    return _hand_on(out, keep_layout, pw, bn)
+
+
+def _wide_block(dw, pw, slot, x):
     """[ReLU, depthwise Conv2d, pointwise Conv2d, norm] wider than the fused depthwise + pointwise kernels take, as two nodes:
     Depthwise, then the 1 x 1 member of the dense-convolution family that fits the norm slot, without a ReLU; the intermediate
     stays NHWC.  None when one of the two does not apply (the caller keeps the stock layers).  The caller has checked the
     layers' attributes (`layers_ok` of run_block)."""
-    relu, dw, pw, bn = layers
     w_dw, w_pw = getattr(dw, 'weight', None), getattr(pw, 'weight', None)
     if not (torch.is_tensor(x) and x.dim() == 4 and torch.is_tensor(w_pw) and w_pw.dim() == 4 and _plain_conv(pw) and
             max(x.shape[1], w_pw.shape[0]) > DWPW_MAX and _wide()):
@@ -1114,25 +1041,11 @@ def _run_wide_block(layers, x, keep_layout):
     stride, pad, dil = int(dw.stride[0]), int(dw.padding[0]), int(dw.dilation[0])
     if not Depthwise.applicable(x, w_dw, stride, pad, dil):
         return None
-    gamma, beta, has_run, batch_stats = _norm_inputs(bn)
     d = _desc(x, x.shape[1], w_dw.shape[-1], stride, pad, dil, 0.0)
-    probe = x.new_empty(1).expand(d.N, d.C_in, d.Ho, d.Wo)        # (the second node's input: one element, no storage of that size)
-    if _no_norm(bn):
-        if not ConvOnly.applicable(probe, w_pw):
-            return None
-        out = conv_only(depthwise_relu(x, w_dw, stride, pad, dil), w_pw, 1, 0, 1, relu=False)
-    elif _frozen_norm(batch_stats):
-        if not (hasattr(bn, 'eps') and ConvBnEval.applicable(probe, w_pw, gamma, beta, bn.running_mean, bn.running_var, 1, 0, 1)):
-            return None
-        out = conv_bn_eval(depthwise_relu(x, w_dw, stride, pad, dil), w_pw, gamma, beta, bn.running_mean, bn.running_var, 1, 0, 1,
-                           False, bn.eps)
-    else:
-        if not (hasattr(bn, 'eps') and ConvBn.applicable(probe, w_pw, gamma, beta, batch_stats) and
-                conv_desc_fits(_conv_desc(probe, w_pw, 1, 0, 1, False, 0.0))):
-            return None
-        out, stats = conv_bn(depthwise_relu(x, w_dw, stride, pad, dil), w_pw, gamma, beta, 1, 0, 1, False, bn.eps)
-        _update_running_stats(bn, stats, out, has_run)
-    return _hand_on(out, keep_layout, dw, pw, bn)
+    mid = _stand_in(x, d.N, d.C_in, d.Ho, d.Wo)
+    if slot.kind == 'batch' and not conv_desc_fits(_conv_desc(mid, w_pw, 1, 0, 1, False, 0.0)):
+        return None                                # (ConvBnEval.applicable asks this itself, ConvBn.applicable does not)
+    return _conv_dispatch(mid, w_pw, slot, 1, 0, 1, False, first=lambda: depthwise_relu(x, w_dw, stride, pad, dil))
 
 
 def run_block(layers, x, keep_layout=False):
@@ -1145,9 +1058,6 @@ def run_block(layers, x, keep_layout=False):
     profiles/r05c_target_ops_channels_last_diag.txt), so the layout must not leak into them -- one transposing copy per
     direction at the op's boundary until the neighbouring layers are native as well."""
     relu, dw, pw, bn = layers
-    w_dw, w_pw = getattr(dw, 'weight', None), getattr(pw, 'weight', None)
-    gamma, beta, has_run, batch_stats = _norm_inputs(bn)
-    ks = dw.kernel_size[0] if hasattr(dw, 'kernel_size') else 0
     layers_ok = getattr(dw, 'bias', None) is None and getattr(pw, 'bias', None) is None and \
         hasattr(dw, 'kernel_size') and dw.kernel_size[0] == dw.kernel_size[1] and dw.stride[0] == dw.stride[1] and \
         not isinstance(dw.padding, str) and dw.padding[0] == dw.padding[1] and dw.dilation[0] == dw.dilation[1] and \
@@ -1155,26 +1065,14 @@ def run_block(layers, x, keep_layout=False):
         tuple(getattr(pw, 'stride', (1, 1))) == (1, 1) and not isinstance(getattr(pw, 'padding', 0), str) and \
         tuple(getattr(pw, 'padding', (0, 0))) == (0, 0) and getattr(pw, 'groups', 1) == 1 and \
         tuple(getattr(pw, 'dilation', (1, 1))) == (1, 1)
-    if _no_norm(bn) and layers_ok and DwPw.applicable(x, w_dw, w_pw, ks):
-        # (norm=None: the family's member without a norm layer)
-        return _hand_on(dwpw(x, w_dw, w_pw, dw.stride[0], dw.padding[0], dw.dilation[0]), keep_layout, dw, pw, bn)
-    if _frozen_norm(batch_stats) and hasattr(bn, 'eps') and layers_ok and \
-            DwPwBnEval.applicable(x, w_dw, w_pw, gamma, beta, bn.running_mean, bn.running_var, ks):
-        # (running statistics in eval mode: the family's member with a frozen norm; the statistics are not touched)
-        out = dwpw_bn_eval(x, w_dw, w_pw, gamma, beta, bn.running_mean, bn.running_var, dw.stride[0], dw.padding[0],
-                           dw.dilation[0], bn.eps)
-        return _hand_on(out, keep_layout, dw, pw, bn)
-    ok = hasattr(bn, 'eps') and layers_ok and DwPwBn.applicable(x, w_dw, w_pw, gamma, beta, ks, batch_stats)
-    if not ok:
-        out = _run_wide_block(layers, x, keep_layout) if layers_ok else None   # (wider than the fused kernels: two nodes)
-        if out is not None:
-            return out
-        for m in layers:
-            x = m(x)
-        return x
-    out, stats = dwpw_bn(x, w_dw, w_pw, gamma, beta, dw.stride[0], dw.padding[0], dw.dilation[0], bn.eps)
-    _update_running_stats(bn, stats, out, has_run)
-    return _hand_on(out, keep_layout, dw, pw, bn)
+    out = None
+    if layers_ok:
+        slot = _norm_slot(bn)
+        out = _dwpw_dispatch(x, getattr(dw, 'weight', None), getattr(pw, 'weight', None), slot, dw.stride[0], dw.padding[0],
+                             dw.dilation[0])
+        if out is None:
+            out = _wide_block(dw, pw, slot, x)                 # (wider than the fused kernels: two nodes)
+    return _stock(layers, x) if out is None else _hand_on(out, keep_layout, dw, pw, bn)
 
 
 class _MsaDesc(ctypes.Structure):
@@ -1250,14 +1148,14 @@ class LeanAttention(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qkv, heads):
-        if not (torch.is_tensor(qkv) and qkv.is_cuda and qkv.dtype == torch.float32 and qkv.dim() == 3 and qkv.shape[2] % 3 == 0):
+        if not (_f32_cuda(qkv) and qkv.dim() == 3 and qkv.shape[2] % 3 == 0):
             raise L.Ghn3Error('lean_attention takes a float32 CUDA tensor (B, N, 3 C); there is no other implementation')
         lib = L.load()
         q = _aligned(qkv.contiguous())
         B, N, C = q.shape[0], q.shape[1], q.shape[2] // 3
         out = torch.empty((B, N, C), dtype=torch.float32, device=q.device)
         lse = torch.empty((B, heads, N), dtype=torch.float32, device=q.device) if ctx.needs_input_grad[0] else None
-        L._check(lib.ghn3_attn_lean_fwd(_ptr(out), None if lse is None else _ptr(lse), _ptr(q), B, N, C, heads, _stream()),
+        L._check(lib.ghn3_attn_lean_fwd(_ptr(out), _ptr(lse), _ptr(q), B, N, C, heads, _stream()),
                  'ghn3_attn_lean_fwd')
         if lse is not None:
             ctx.save_for_backward(q, lse, out)
@@ -1289,8 +1187,7 @@ class MsaLayer(torch.autograd.Function):
 
     @staticmethod
     def applicable(layer, x):
-        if not (enabled() and os.environ.get('GHN3_NATIVE_MSA', '1') != '0' and torch.is_tensor(x) and x.is_cuda and
-                x.dtype == torch.float32 and x.dim() == 4 and not _autocast_excludes() and x.numel() < 2 ** 31):
+        if not (_native_input(x, 'GHN3_NATIVE_MSA') and x.numel() < 2 ** 31):
             return False
         mods = _msa_modules(layer)
         if mods is None or getattr(layer, 'edge_dim', 0) != 0:
@@ -1310,7 +1207,7 @@ class MsaLayer(torch.autograd.Function):
         w = [getattr(m, a, None) for m in (ln1, qkv, out, ln2, ff1, ff2) for a in ('weight', 'bias')]
         if w[3] is None:                                   # (to_qkv without a bias, the search space's default)
             w = w[:3] + w[4:]
-        if not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in w):
+        if not _f32_cuda(*w):
             return False
         hidden = int(ff1.weight.shape[0])
         want = [(ln1.weight, (C,)), (ln1.bias, (C,)), (qkv.weight, (3 * C, C)), (out.weight, (C, C)), (out.bias, (C,)),
@@ -1345,7 +1242,7 @@ class MsaLayer(torch.autograd.Function):
         # (P and everything the backward reads only when the layer is differentiated)
         P = torch.empty(B * heads * H * W * H * W, dtype=torch.float32, device=dev) if train else None
         L._check(lib.ghn3_msa_fwd(ctypes.byref(d), _ptr(xc), ctypes.byref(_msa_ptrs(ps)), _ptr(out),
-                                  _ptr(P) if P is not None else None, _ptr(scratch), _stream()), 'ghn3_msa_fwd')
+                                  _ptr(P), _ptr(scratch), _stream()), 'ghn3_msa_fwd')
         if train:
             ctx.save_for_backward(xc, scratch, P, *ps)
             ctx.desc = d
@@ -1472,8 +1369,7 @@ class ClassifierHead(torch.autograd.Function):
 
     @staticmethod
     def applicable(pool, classifier, x):
-        if not (head_enabled() and torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and
-                not _autocast_excludes()):
+        if not _native_input(x, 'GHN3_NATIVE_HEAD'):
             return False
         if pool is not None and not _is_global_pool(pool):
             return False
@@ -1487,7 +1383,7 @@ class ClassifierHead(torch.autograd.Function):
         dims = [C if pool is not None else C * H * W]
         for m in lin:
             w, b = getattr(m, 'weight', None), getattr(m, 'bias', None)
-            if not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in (w, b)):
+            if not _f32_cuda(w, b):
                 return False
             if w.dim() != 2 or w.shape[1] != dims[-1] or tuple(b.shape) != (w.shape[0],):
                 return False
@@ -1543,8 +1439,7 @@ class ClassifierHead(torch.autograd.Function):
 def classifier_head(x, weights, biases, masks=(), ps=(), glob_avg=True):
     """The head on the fused op with explicit tensors: weights[j] (d_j+1, d_j), biases[j]; masks[j] (uint8 (B, d_j+1) or
     None) the keep mask of the dropout after linear j (rate ps[j])."""
-    if not x.is_cuda:
-        raise L.Ghn3Error('classifier_head runs on an MI355X only (no CPU implementation: use the stock torch layers)')
+    _needs_gpu('classifier_head', x)
     n = len(weights)
     masks = list(masks) + [None] * (n - 1 - len(masks))
     ps = [float(p) if m is not None else 0.0 for p, m in zip(list(ps) + [0.0] * (n - 1), masks)]
