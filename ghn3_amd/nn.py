@@ -170,7 +170,7 @@ class _Plan:
         # as finite zeros: those regions are zero-filled once per plan; every other region is written before it is read (or
         # zeroed by an op of the programs) and starts uninitialised -- a NEW architecture every step paid 0.4 ms of GPU time
         # for the full fill.  GHN3_WS_ZERO_ALL=1: the full fill; GHN3_WS_POISON=1 (tests): NaN bytes everywhere else.
-        regions = getattr(program, 'ws_zero', None)
+        regions = program.ws_zero
         self.ws_dout_ready = regions is None or os.environ.get('GHN3_WS_ZERO_ALL', '0') == '1'
         self.zero_fill_bytes = int(program.ws_bytes + program.scal_bytes)     # (what this plan zero-fills: see bench.py)
         if self.ws_dout_ready:
@@ -234,7 +234,7 @@ class _ParamNormLoss(torch.autograd.Function):
         prog = plan.program
         ghn._fill_bufs(plan, out=flat)
         stream = torch.cuda.current_stream().cuda_stream
-        ctx.fused = prog.training and getattr(prog, 'tile_bwd_op', None) is not None
+        ctx.fused = prog.training and prog.tile_bwd_op is not None
         if ctx.fused:
             ghn._ctx().run(prog.norm_fin_ops(), prog.problems, plan.bufs, stream)
             ctx.b_ops = None
@@ -548,15 +548,15 @@ class GHN3(nn.Module):
         gflat = torch.empty(self._flat_numel, dtype=torch.float32, device=self.device)
         # (the direct 16-bit tile route -- the fused norm term alone, and compiled in: not with GHN3_TILE_D16=0 / bf16 backward
         # operands -- never reads the fp32 tile gradient; every other route does)
-        direct = dout is None and norm_g is not None and bool(getattr(prog, 'tile_bwd_h16', 0))
+        direct = dout is None and norm_g is not None and bool(prog.tile_bwd_h16)
         if not direct and not getattr(plan, 'ws_dout_ready', False):
             # (regions only the fp32 tile-gradient route reads before it has written every byte of them: see _Plan)
-            for off, n in getattr(prog, 'ws_zero_dout', ()):
+            for off, n in prog.ws_zero_dout:
                 plan.ws[off:min(off + n, prog.ws_bytes)].zero_()
             plan.ws_dout_ready = True
         self._fill_bufs(plan, out=plan.out, dout=dout, gflat=gflat)
         self._patch_grad_memsets(prog)
-        kt = getattr(prog, 'tile_bwd_op', None)
+        kt = prog.tile_bwd_op
         if kt is not None:                               # which upstream terms the tile backward reads in this step
             r = prog.bwd_ops[kt]['r']
             for slot, (buf, off) in prog.tile_bwd_refs.items():
@@ -574,7 +574,7 @@ class GHN3(nn.Module):
         # copies -> the persistent weight gradient on the run's own stream and every CU -> dgrad -> rest of the decoder ->
         # Graphormer backward.  Measured alternating on one box (profiles/r06s_*): 6.12 ms per step against 5.90 for the default
         # side-stream schedule at one graph, 10.16 / 9.82 at two, 16.27 / 15.96 at four: slower everywhere, off.
-        use_parts = reducer is not None or (len(getattr(prog, 'bwd_parts', ())) > 1 and os.environ.get('GHN3_BWD_PARTS', '0') == '1')
+        use_parts = reducer is not None or (len(prog.bwd_parts) > 1 and os.environ.get('GHN3_BWD_PARTS', '0') == '1')
         if not use_parts:
             self._ctx().run(prog.bwd_ops, prog.problems, plan.bufs, stream)
         else:

@@ -58,7 +58,7 @@ class FusedAdamW:
         current for the parameters of the last forward."""
         ghn = self.ghn
         prog = plan.program if plan is not None else None
-        w2 = getattr(prog, 'shadow_w2', None) if prog is not None else None
+        w2 = prog.shadow_w2 if prog is not None else None
         if w2 is None or not prog.training or ghn._shadow is None or os.environ.get('GHN3_ADAMW_CAST', '1') == '0':
             return None
         # (the W2 copies must be current for the parameters as they are now -- written by the last forward's refresh or by
@@ -114,7 +114,7 @@ class FusedAdamW:
         clip = self.max_grad_norm and self.max_grad_norm > 0
         fuse = self._w2_fusion(plan)
         overlap = bool(overlap) and getattr(ghn, 'side_stream', True) and plan is not None and \
-            hasattr(plan.program, 'decoder_slots') and os.environ.get('GHN3_ADAMW_OVERLAP', '1') != '0'
+            plan.program.decoder_slots is not None and os.environ.get('GHN3_ADAMW_OVERLAP', '1') != '0'
         ops = np.zeros(9, dtype=L.OP_DT)
         ops['r']['buf'][:] = -1
         bufs = [flat.data_ptr(), gflat.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
@@ -126,7 +126,7 @@ class FusedAdamW:
         ops[1]['kind'] = L.OP_SUMSQ if guard else L.OP_NOP
         ops[1]['r']['buf'][:3] = (4, 1, 5)         # (r2: scratch for the fixed-order sum of the workgroup partials)
         ops[1]['i'][0] = n
-        gs = getattr(plan.program, 'grad_sumsq', None) if (plan is not None and local_grads and guard) else None
+        gs = plan.program.grad_sumsq if (plan is not None and local_grads and guard) else None
         if gs is not None and getattr(plan, 'gflat', None) is gflat and os.environ.get('GHN3_WGRAD_SUMSQ', '1') != '0':
             prog = plan.program
             k2 = prog.slot[gs['name']]

@@ -12,6 +12,7 @@ Everything here is host-side shape bookkeeping (numpy); no tensor math.  The com
 
 import math
 import os
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -51,11 +52,39 @@ def round_up(x, m):
     return (x + m - 1) // m * m
 
 
+class _Backward:
+    """What one stage of Program._build_backward hands to a later one (and, at the end, to the scheduling): one object per
+    build, never kept on the program.  A stage that reads a field no earlier stage has set fails with an AttributeError."""
+    __slots__ = ('sw',                                   # the switches (Program._backward_switches)
+                 'd_rows',                               # gradient of the gathered node rows [M + n1][C]
+                 'scaled', 'amax_t', 'amax_u',           # f16 gradient copies: scaled?  running-max refs of d_tiles / d_u
+                 't', 'u', 'd_t', 'd_u',                 # decoder activations of the forward and their gradients
+                 'bct', 'g16',                           # backward operand type; the gemm groups of the 16-bit pipeline
+                 'planes16', 'planes32',                 # W2 dgrad: K chunks into partial planes (16-bit / exact-fp32 groups)
+                 'n_planes', 'rows16', 'd_up', 'pinned',     # ... their count, the rows that have them, their ref, chunk j on XCD j
+                 'sub',                                  # ... the parts every K chunk of the 16-bit dgrad is cut into
+                 'bands',                                # wgrad bands (= Program.wgrad_bands)
+                 'd16_on', 'd16_off',                    # ops of the direct 16-bit route / of the fp32 route of the tile gradient
+                 'late_ops',                             # ops of the weight gradient's operand copies, issued behind the dgrad
+                 'i_dgrad', 'i_late0', 'i_late1',        # op indices: the W2 dgrad launch, [first, end) of late_ops
+                 'do', 'dBias', 'hist', 'hist_amax')     # Graphormer backward: attention-output gradient, edge-bias gradient
+
+    def __init__(self, sw):
+        self.sw = sw
+        self.g16, self.bands, self.d16_on, self.d16_off, self.late_ops = [], [], [], [], []
+        self.i_dgrad = self.i_late0 = self.i_late1 = self.d_up = None
+
+
 class Program:
     """See module docstring.  cfg: dict(hid, heads, layers, num_classes, max_shape)."""
 
     # extra buffer slots after the 2*P parameter / gradient pointers
     X_WS, X_IDX, X_EDGES, X_OUT, X_DOUT, X_TOK, X_SCAL, X_GRADFLAT, X_SHADOW, X_NORMG, X_COUNT = range(11)
+
+    # builder-only state (problem tuples, index chunks, group dictionaries ...): what strip() drops
+    BUILD_ONLY = ('_probs', '_ops', '_ln', '_idx_chunks', '_gap_cache', 'conv_groups', 'gemm_groups', 'param_groups',
+                  'params_map', 'wgrad_bands', 'd1', 'row_src', 'row_pos', 'oned_src', 'oned_index', 'oned_plain', 'oned_clsb',
+                  'shape_idx', 'node_types', 'shadow_lay', '_tile_desc_arr')
 
     def __init__(self, cfg, node_infos, n_nodes, node_types, max_edge, nets, index_mode='reference',
                  training=True, predict_class_layers=True, reduce_graph=False, layernorm=True, weight_norm=True,
@@ -137,6 +166,30 @@ class Program:
         self._ws = 0
         self._ws_names = {}
         self._idx_chunks, self._idx_size = [], 0
+        self._gap_cache = {}                    # param_gap(): running sums of the padded parameter sizes
+        # ---- fields that only some programs fill (a program without 16-bit groups, without decoder rows, an inference
+        # program ...), with the value their readers -- later stages, the scheduling, GHN3, FusedAdamW, bench.py -- take
+        # for "absent".  Names listed in BUILD_ONLY serve the build alone and are dropped by strip().
+        self.ws_zero = None                     # [(offset, bytes)] of the 16-bit regions a plan zero-fills once (ws16)
+        self.ws_zero_dout = ()                  # ... and in front of its first backward on the upstream-gradient route
+        self.uses_op16 = False                  # _cast_w2: some family multiplies 16-bit operand copies
+        self.shadow_w2 = None                   # _cast_w2: dict(op, item, name) of the W2 cast a fused optimizer step replaces
+        self.w0hT = None                        # _cast_w2: offset of the 16-bit decoder.conv.0.weight^T (D2 dgrad B operand)
+        self.shadow_lay = None
+        self.d1 = []                            # decoder forward: (position, rows, row refs) of the fc problems
+        self.tiles_floats = 0
+        self._tile_desc_arr = None
+        self.r_amax = None                      # running max |x| slots of the f16 gradient copies
+        self.memset_grad_op = self.bwd_split = self.bwd_cut_w2 = None       # op indices of the backward (training)
+        self.tile_bwd_op, self.tile_bwd_refs, self.tile_bwd_h16 = None, {}, 0
+        self.d16_on_idx, self.d16_off_idx, self.d16_kinds = [], [], {}      # route switch of the tile gradient
+        self.wgrad_op_range, self.wgrad_cap, self.wgrad_order, self.wgrad_bands = None, 0, None, []
+        self.dgrad_sub = None
+        self.grad_sumsq = None                  # set when the W2 weight gradient leaves its own sum of squares
+        self.grad_no_memset = []                # parameters whose gradient the backward fully overwrites
+        self.decoder_slots = None               # (training programs only: `is not None` = "this is a training program")
+        self.bwd_ops_a = self.bwd_ops_b = None
+        self.bwd_parts, self.ddp_index, self.ddp_wgrad_first = (), {}, False
 
         self.param_groups, self.params_map = bk.map_net_params(node_infos, self.n_nodes, nets, self.max_shape,
                                                                reduce_graph=reduce_graph)
@@ -149,127 +202,139 @@ class Program:
         self.predict_class_layers = predict_class_layers
 
         self._layout_decoder()
-        # 16-bit shadows of the decoder weights (a separate, plan-independent program: GHN3 runs it only when the
-        # parameters changed since the shadows were written)
+        self._build_shadows()
+        self._build_forward()
+        self.fwd_ops = self._finish_ops()
+        self.n_fwd_problems = len(self._probs)
+        self.bwd_ops = np.zeros(0, dtype=L.OP_DT)
+        if training:
+            sw = self._backward_switches()
+            self._schedule_backward(sw, self._build_backward(sw))
+        self._pack()
+
+    def _build_shadows(self):
+        """16-bit shadows of the decoder weights (a separate, plan-independent program: GHN3 runs it only when the
+        parameters changed since the shadows were written)."""
         self._cast_w2()
         if self._ops:
             self.op(L.OP_DETACH)
         self.shadow_ops = self._finish_ops()
         self.shadow_ops_rest = self.shadow_ops
-        if getattr(self, 'shadow_w2', None) is not None:
+        if self.shadow_w2 is not None:
             self.shadow_ops_rest = self.shadow_ops.copy()
             assert int(self.shadow_ops_rest[self.shadow_w2['op']]['kind']) == L.OP_CAST16
             self.shadow_ops_rest[self.shadow_w2['op']]['kind'] = L.OP_NOP
-        self._build_forward()
-        self.fwd_ops = self._finish_ops()
-        self.n_fwd_problems = len(self._probs)
-        if training:
-            self._build_backward()
-            # direct 16-bit tiles: ops of the direct route (off unless GHN3._run_backward turns them on) and of the fp32 route
-            on, off = getattr(self, '_d16_on', []), getattr(self, '_d16_off', [])
-            self.d16_on_idx = [k for k, o in enumerate(self._ops) if any(o is t for t in on)]
-            self.d16_off_idx = [k for k, o in enumerate(self._ops) if any(o is t for t in off)]
-            assert all(k < self.bwd_cut_w2 and (self.wgrad_op_range is None or k < self.wgrad_op_range[0])
-                       for k in self.d16_on_idx + self.d16_off_idx)
-            self.bwd_ops = self._finish_ops()
-            self.d16_kinds = {k: int(self.bwd_ops[k]['kind']) for k in self.d16_on_idx + self.d16_off_idx}
-            if not hasattr(self, 'tile_bwd_h16'):
-                self.tile_bwd_h16 = 0
-            for k in self.d16_on_idx:
-                self.bwd_ops[k]['kind'] = L.OP_NOP               # (compiled state = the fp32 route)
-            detach = np.zeros(1, dtype=L.OP_DT)
-            detach['kind'] = L.OP_DETACH
-            detach['r']['buf'][:] = -1
-            self.bwd_ops_a = np.concatenate([self.bwd_ops[:self.bwd_split], detach])
-            self.bwd_ops_b = self.bwd_ops[self.bwd_split:]
-            # flat-gradient slots of the decoder parameters (contiguous in the parameter order)
-            self.decoder_slots = (self.slot['decoder.fc.0.weight'], self.slot['bias_class.1.bias'] + 1)
-            # Data-parallel schedule: the backward program is run in parts; after part k the gradients of `slots`
-            # (half-open slot ranges) are complete once the side stream has drained, and their all-reduce may start
-            # while the next parts execute.  Part 1 ends behind the W2 weight gradient (69 % of all gradient bytes at
-            # ghn3xlm16), part 2 behind the rest of the decoder (24 %), the Graphormer backward is the last part.
-            # The schedule (number of parts, slot ranges = collective sizes) depends on the GHN's parameter layout ONLY,
-            # never on the rank's graph: every rank compiles a different architecture each step and mismatched
-            # collective sequences would hang RCCL.  A batch without any 2-D / 4-D weight node gets an empty first part
-            # (just the gradient memsets, which always live in part 1).
-            w2 = self.slot['decoder.conv.2.weight']
-            lo, hi = self.decoder_slots
-            cut1 = min(max(self.bwd_cut_w2, self.memset_grad_op + 2), self.bwd_split)
-            cuts = [(cut1, [(w2, w2 + 1)]), (self.bwd_split, [(lo, w2), (w2 + 1, hi)])]
-            self.bwd_parts, pos = [], 0
-            self.ddp_index = {}                          # op index in bwd_ops -> index inside part 1, where they differ
-            wg_first = self.wgrad_op_range is not None and getattr(self, '_i_dgrad', None) is not None and \
-                os.environ.get('GHN3_DDP_WGRAD_FIRST', '1') != '0'
-            self.ddp_wgrad_first = bool(wg_first)
-            if wg_first:
-                # Round 5: the W2 weight gradient FIRST.  dW2 is 69 % of the gradient bytes and needs nothing but the tile
-                # gradient and the forward's u: issued right behind the tile backward and its operand copies -- on the
-                # run's own stream, every CU -- its exchange overlaps the W2 dgrad, the conv.0 / fc backward AND the whole
-                # Graphormer backward (~2.5 ms at ghn3xlm16) instead of the Graphormer backward alone (~1.1 ms).
-                o = self.bwd_ops
-                a, b = self.wgrad_op_range
-                dg0, l0, l1 = self._i_dgrad, self._i_late0, self._i_late1
-                assert self.memset_grad_op + 2 <= dg0 <= l0 <= l1 <= a <= b <= self.bwd_split
-                # (the operand copies run on the side stream: MARK + WAIT on slot 1 -- not a full join, which would also
-                # consume the pending mark of the 1-D decoder backward that part 3 waits for)
-                join = np.zeros(2, dtype=L.OP_DT)
-                join['kind'] = L.OP_JOIN
-                join['r']['buf'][:] = -1
-                join[0]['i'][:2] = (1, 1)
-                join[1]['i'][:2] = (2, 1)
-                wg = o[a:b].copy()
-                for q in range(len(wg)):                 # the persistent band launch: chain's stream, no grid cap
-                    if int(wg[q]['kind']) == L.OP_GEMM and int(wg[q]['i'][2]) == 29:
-                        wg[q]['flags'] &= ~L.OPFLAG_SIDE
-                        wg[q]['i'][3] = 0
-                part1 = np.concatenate([o[:dg0], o[l0:l1], join, wg, detach])
-                part2 = np.concatenate([o[dg0:l0], o[l1:a], o[b:self.bwd_split], detach])
-                self.ddp_index = {k: dg0 + (k - l0) for k in range(l0, l1)}
-                self.bwd_parts = [(part1, cuts[0][1]), (part2, cuts[1][1])]
-                pos = self.bwd_split
-            else:
-                for end, slots in cuts:
-                    self.bwd_parts.append((np.concatenate([self.bwd_ops[pos:end], detach]), slots))
-                    pos = end
-            self.bwd_parts.append((self.bwd_ops[pos:], []))
-            # Single-process order (bwd_ops; the parts above keep the early order so that a data-parallel run can start the
-            # exchange of dW2 -- 69 % of the gradient bytes -- as soon as possible): the W2 weight gradient is issued
-            # BEHIND the rest of the decoder backward.  The conv.0 / fc dgrads, the plane sums and the node-row gather are on
-            # the dependent chain and no longer share the chip with it (fc dgrad 0.39 -> 0.1 ms); the weight gradient then
-            # runs beside the Graphormer backward only, which is long enough to hide it (GHN3_WGRAD_LATE=0: early order).
-            # Round 5b, GHN3_WGRAD_ORDER=first (default when the weight gradient runs on the side stream): issued right behind the
-            # tile backward and its operand copies, on 128 workgroups -- half of every XCD.  The lowest-priority stream gets its CUs
-            # when the W2 dgrad has handed out its last tiles (forcing the launch beside the dgrad gains nothing: two MFMA-bound
-            # kernels share the chip's work), so it runs beside the conv.0 / fc backward and only the first third of the Graphormer
-            # backward, which is the part of the step that suffers beside it (tools/contention_probe: a streaming kernel on the
-            # other CUs turns the chain's L2 hits into 350 ns misses and costs 8-15 % of the clock).  5.85-5.86 against 5.91-5.93
-            # ms (one graph), 9.65-9.83 against 10.03-10.12 (two), 15.76-15.80 against 16.28-16.35 (four); 112 / 144 / 160
-            # workgroups are all slower than 128 (profiles/r05s_*, r05v_*, r05w_*).
-            order = self._wgrad_order_env()
-            if order == 'first' and not getattr(self, 'wgrad_cap', 0):
-                order = 'late'                           # (on the chain's own stream it stays in front of the Graphormer backward)
-            self.wgrad_order = order if (self.wgrad_op_range is not None and self.SIDE) else 'early'
-            if self.wgrad_order == 'late':
-                a, b = self.wgrad_op_range
-                o = self.bwd_ops
-                self.bwd_ops = np.concatenate([o[:a], o[b:self.bwd_split], o[a:b], o[self.bwd_split:]])
-            elif self.wgrad_order == 'first' and getattr(self, '_i_dgrad', None) is not None:
-                a, b = self.wgrad_op_range               # (a: the zero-fill of its sum-of-squares slots, then the launches)
-                dg0, l0, l1 = self._i_dgrad, self._i_late0, self._i_late1
-                o = self.bwd_ops
-                perm = list(range(dg0)) + list(range(l0, l1)) + list(range(a, b)) + list(range(dg0, l0)) + \
-                    list(range(l1, a)) + list(range(b, len(o)))
-                assert sorted(perm) == list(range(len(o)))
-                inv = {old: new for new, old in enumerate(perm)}
-                self.bwd_ops = o[np.asarray(perm, dtype=np.int64)]
-                # (op indices recorded for the route switch of the tile gradient / the data-parallel parts follow the ops)
-                if hasattr(self, 'd16_kinds'):
-                    self.d16_kinds = {inv[k]: v for k, v in self.d16_kinds.items()}
-                    self.d16_on_idx = [inv[k] for k in self.d16_on_idx]
-                    self.d16_off_idx = [inv[k] for k in self.d16_off_idx]
-                self.ddp_index = {inv[k]: v for k, v in self.ddp_index.items()}
+
+    def _schedule_backward(self, sw, bb):
+        """Turns the ops _build_backward emitted (in dependency order, the W2 weight gradient behind the dgrad) into what is
+        run: bwd_ops in the single-process order, bwd_parts for a data-parallel run, bwd_ops_a / _b, and the op indices that
+        GHN3._run_backward patches per step."""
+        # direct 16-bit tiles: ops of the direct route (off unless GHN3._run_backward turns them on) and of the fp32 route
+        self.d16_on_idx = [k for k, o in enumerate(self._ops) if any(o is t for t in bb.d16_on)]
+        self.d16_off_idx = [k for k, o in enumerate(self._ops) if any(o is t for t in bb.d16_off)]
+        assert all(k < self.bwd_cut_w2 and (self.wgrad_op_range is None or k < self.wgrad_op_range[0])
+                   for k in self.d16_on_idx + self.d16_off_idx)
+        self.bwd_ops = self._finish_ops()
+        self.d16_kinds = {k: int(self.bwd_ops[k]['kind']) for k in self.d16_on_idx + self.d16_off_idx}
+        for k in self.d16_on_idx:
+            self.bwd_ops[k]['kind'] = L.OP_NOP               # (compiled state = the fp32 route)
+        detach = np.zeros(1, dtype=L.OP_DT)
+        detach['kind'] = L.OP_DETACH
+        detach['r']['buf'][:] = -1
+        self.bwd_ops_a = np.concatenate([self.bwd_ops[:self.bwd_split], detach])
+        self.bwd_ops_b = self.bwd_ops[self.bwd_split:]
+        # flat-gradient slots of the decoder parameters (contiguous in the parameter order)
+        self.decoder_slots = (self.slot['decoder.fc.0.weight'], self.slot['bias_class.1.bias'] + 1)
+        # The two schedules that issue the W2 weight gradient FIRST share one description of the decoder backward, cut at five
+        # op indices: [0, dgrad) tile backward and the dgrad's operand copy | [dgrad, late0) the W2 dgrad | [late0, late1) the
+        # weight gradient's operand copies | [late1, a) DACT | [a, b) the weight gradient | [b, bwd_split) conv.0, fc, 1-D.
+        first = None
+        if self.wgrad_op_range is not None and bb.i_dgrad is not None:
+            (a, b), dg0, l0, l1 = self.wgrad_op_range, bb.i_dgrad, bb.i_late0, bb.i_late1
+            assert self.memset_grad_op + 2 <= dg0 <= l0 <= l1 <= a <= b <= self.bwd_split
+            first = (list(range(dg0)), list(range(l0, l1)), list(range(a, b)),
+                     list(range(dg0, l0)) + list(range(l1, a)) + list(range(b, self.bwd_split)))
+        self._data_parallel_parts(sw, first, detach)
+        self._single_process_order(sw, first)
+
+    def _data_parallel_parts(self, sw, first, detach):
+        """Data-parallel schedule: the backward program is run in parts; after part k the gradients of `slots`
+        (half-open slot ranges) are complete once the side stream has drained, and their all-reduce may start
+        while the next parts execute.  Part 1 ends behind the W2 weight gradient (69 % of all gradient bytes at
+        ghn3xlm16), part 2 behind the rest of the decoder (24 %), the Graphormer backward is the last part.
+        The schedule (number of parts, slot ranges = collective sizes) depends on the GHN's parameter layout ONLY,
+        never on the rank's graph: every rank compiles a different architecture each step and mismatched
+        collective sequences would hang RCCL.  A batch without any 2-D / 4-D weight node gets an empty first part
+        (just the gradient memsets, which always live in part 1)."""
+        o = self.bwd_ops
+        w2 = self.slot['decoder.conv.2.weight']
+        lo, hi = self.decoder_slots
+        slots1, slots2 = [(w2, w2 + 1)], [(lo, w2), (w2 + 1, hi)]
+        self.ddp_wgrad_first = first is not None and sw.ddp_wgrad_first
+        if self.ddp_wgrad_first:
+            # Round 5: the W2 weight gradient FIRST.  dW2 is 69 % of the gradient bytes and needs nothing but the tile
+            # gradient and the forward's u: issued right behind the tile backward and its operand copies -- on the
+            # run's own stream, every CU -- its exchange overlaps the W2 dgrad, the conv.0 / fc backward AND the whole
+            # Graphormer backward (~2.5 ms at ghn3xlm16) instead of the Graphormer backward alone (~1.1 ms).
+            head, copies, wgrad, rest = first
+            # (the operand copies run on the side stream: MARK + WAIT on slot 1 -- not a full join, which would also
+            # consume the pending mark of the 1-D decoder backward that part 3 waits for)
+            join = np.zeros(2, dtype=L.OP_DT)
+            join['kind'] = L.OP_JOIN
+            join['r']['buf'][:] = -1
+            join[0]['i'][:2] = (1, 1)
+            join[1]['i'][:2] = (2, 1)
+            wg = o[np.asarray(wgrad, dtype=np.int64)]
+            for q in range(len(wg)):                 # the persistent band launch: chain's stream, no grid cap
+                if int(wg[q]['kind']) == L.OP_GEMM and int(wg[q]['i'][2]) == 29:
+                    wg[q]['flags'] &= ~L.OPFLAG_SIDE
+                    wg[q]['i'][3] = 0
+            part1 = np.concatenate([o[np.asarray(head + copies, dtype=np.int64)], join, wg, detach])
+            part2 = np.concatenate([o[np.asarray(rest, dtype=np.int64)], detach])
+            # op index in bwd_ops -> index inside part 1, where they differ (the weight gradient's operand copies)
+            self.ddp_index = {k: len(head) + n for n, k in enumerate(copies)}
         else:
-            self.bwd_ops = np.zeros(0, dtype=L.OP_DT)
+            cut1 = min(max(self.bwd_cut_w2, self.memset_grad_op + 2), self.bwd_split)
+            part1 = np.concatenate([o[:cut1], detach])
+            part2 = np.concatenate([o[cut1:self.bwd_split], detach])
+        self.bwd_parts = [(part1, slots1), (part2, slots2), (o[self.bwd_split:], [])]
+
+    def _single_process_order(self, sw, first):
+        """Single-process order (bwd_ops; the parts above keep the early order so that a data-parallel run can start the
+        exchange of dW2 -- 69 % of the gradient bytes -- as soon as possible): the W2 weight gradient is issued
+        BEHIND the rest of the decoder backward.  The conv.0 / fc dgrads, the plane sums and the node-row gather are on
+        the dependent chain and no longer share the chip with it (fc dgrad 0.39 -> 0.1 ms); the weight gradient then
+        runs beside the Graphormer backward only, which is long enough to hide it (GHN3_WGRAD_LATE=0: early order).
+        Round 5b, GHN3_WGRAD_ORDER=first (default when the weight gradient runs on the side stream): issued right behind the
+        tile backward and its operand copies, on 128 workgroups -- half of every XCD.  The lowest-priority stream gets its CUs
+        when the W2 dgrad has handed out its last tiles (forcing the launch beside the dgrad gains nothing: two MFMA-bound
+        kernels share the chip's work), so it runs beside the conv.0 / fc backward and only the first third of the Graphormer
+        backward, which is the part of the step that suffers beside it (tools/contention_probe: a streaming kernel on the
+        other CUs turns the chain's L2 hits into 350 ns misses and costs 8-15 % of the clock).  5.85-5.86 against 5.91-5.93
+        ms (one graph), 9.65-9.83 against 10.03-10.12 (two), 15.76-15.80 against 16.28-16.35 (four); 112 / 144 / 160
+        workgroups are all slower than 128 (profiles/r05s_*, r05v_*, r05w_*)."""
+        o = self.bwd_ops
+        order = sw.wgrad_order
+        if order == 'first' and not self.wgrad_cap:
+            order = 'late'                           # (on the chain's own stream it stays in front of the Graphormer backward)
+        self.wgrad_order = order if (self.wgrad_op_range is not None and self.SIDE) else 'early'
+        if self.wgrad_order == 'late':
+            a, b = self.wgrad_op_range
+            self.bwd_ops = np.concatenate([o[:a], o[b:self.bwd_split], o[a:b], o[self.bwd_split:]])
+        elif self.wgrad_order == 'first' and first is not None:
+            # (wgrad: the zero-fill of its sum-of-squares slots, then the launches)
+            head, copies, wgrad, rest = first
+            perm = head + copies + wgrad + rest + list(range(self.bwd_split, len(o)))
+            assert sorted(perm) == list(range(len(o)))
+            inv = {old: new for new, old in enumerate(perm)}
+            self.bwd_ops = o[np.asarray(perm, dtype=np.int64)]
+            # (op indices recorded for the route switch of the tile gradient / the data-parallel parts follow the ops)
+            self.d16_kinds = {inv[k]: v for k, v in self.d16_kinds.items()}
+            self.d16_on_idx = [inv[k] for k in self.d16_on_idx]
+            self.d16_off_idx = [inv[k] for k in self.d16_off_idx]
+            self.ddp_index = {inv[k]: v for k, v in self.ddp_index.items()}
+
+    def _pack(self):
         self.problems = self._pack_problems()
         # scalar buffer (X_SCAL): loss [0:256) | per-tensor norms | per-(chunk, tensor) partial sums of the norm pass
         self.scal_bytes = 256 + round_up(4 * max(self.n_seg, 1), 64) + \
@@ -284,11 +349,8 @@ class Program:
         """Drops the builder-only state (problem tuples, index chunks, group dictionaries): what remains is what a plan
         needs at run time.  A loader worker calls it before sending the program to the training process (the pickle
         shrinks from 4.5 MB / ~60k objects to the packed arrays)."""
-        for name in ('_probs', '_ops', '_ln', '_idx_chunks', 'conv_groups', 'gemm_groups', 'param_groups', 'params_map',
-                     'wgrad_bands', 'd1', 'row_src', 'row_pos', 'oned_src', 'oned_index', 'oned_plain', 'oned_clsb',
-                     'shape_idx', 'node_types', 'shadow_lay', '_tile_desc_arr', '_d16_on', '_d16_off'):
-            if hasattr(self, name):
-                setattr(self, name, None)
+        for name in self.BUILD_ONLY:
+            setattr(self, name, None)
         for p_ in self.predicted:
             p_.pop('tok', None)
         return self
@@ -325,7 +387,7 @@ class Program:
         known = name in self._ws_names
         off = self.ws(name, 2 * (int(n_halfs) + 128))
         if not known:
-            self.__dict__.setdefault('ws_zero', []).append((off, round_up(2 * (int(n_halfs) + 128), ALIGN)))
+            self.ws_zero = (self.ws_zero or []) + [(off, round_up(2 * (int(n_halfs) + 128), ALIGN))]
         return off // 2
 
     def href(self, off_halfs):
@@ -660,30 +722,32 @@ class Program:
             m0 += 320
         return np.asarray(out, dtype=np.int32).reshape(-1, 3)
 
+    def _dgrad_makespan(self, g16, sub, nt, n_cu):
+        """Longest-first list schedule of ONE XCD's work items (families x row tiles x nt column tiles x parts `sub`) on its
+        n_cu CUs; chunk 0 (all extents still alive) is the fullest and is the one simulated."""
+        items = []
+        for g in g16:
+            if not g.get('p8'):
+                continue
+            oc = (g['o'] + 7) // 8
+            for (m0, mi, ext) in g['mtiles']:
+                steps = min(int(ext), oc * g['i_ld']) / 64.0
+                for f in sub:
+                    items += [self.p8_cost(mi) * steps * f / sum(sub)] * nt
+        items.sort(reverse=True)
+        cu = [0.0] * n_cu
+        for it in items:
+            k = cu.index(min(cu))
+            cu[k] += it + 4.0                      # (+ prologue / epilogue of a tile, in the same relative units)
+        return max(cu) if items else 0.0
+
     def _dgrad_sub_split(self, g16, n_cols, n_cu=32):
-        """Split of every XCD's K chunk of the W2 dgrad into parts (see _build_backward).  Candidates are scored by a
-        longest-first list schedule of ONE XCD's work items (families x row tiles x 256-column tiles x parts) on its CUs;
-        chunk 0 (all extents still alive) is the fullest and is the one simulated."""
+        """Split of every XCD's K chunk of the W2 dgrad into parts (see _bwd_w2_dgrad_planes): the candidate with the
+        shortest simulated makespan."""
         nt = (n_cols + 255) // 256
-        def makespan(sub):
-            items = []
-            for g in g16:
-                if not g.get('p8'):
-                    continue
-                oc = (g['o'] + 7) // 8
-                for (m0, mi, ext) in g['mtiles']:
-                    steps = min(int(ext), oc * g['i_ld']) / 64.0
-                    for f in sub:
-                        items += [self.p8_cost(mi) * steps * f / sum(sub)] * nt
-            items.sort(reverse=True)
-            cu = [0.0] * n_cu
-            for it in items:
-                k = cu.index(min(cu))
-                cu[k] += it + 4.0                      # (+ prologue / epilogue of a tile, in the same relative units)
-            return max(cu) if items else 0.0
         best, best_sub = None, (1,)
         for sub in ((1,), (3, 1), (1, 1), (2, 1, 1), (1, 1, 1, 1)):
-            score = makespan(sub) + 14.0 * 8 * (len(sub) - 1)     # (a partial plane: ~7 us written + read again)
+            score = self._dgrad_makespan(g16, sub, nt, n_cu) + 14.0 * 8 * (len(sub) - 1)     # (a partial plane: ~7 us written + read again)
             if best is None or score < best - 1e-9:
                 best, best_sub = score, sub
         return best_sub
@@ -934,8 +998,7 @@ class Program:
         assert sa <= sb
         # running sums from slot sa, extended on demand (the one-launch cast of all Graphormer layers asks for the gap from the
         # first layer to every later weight: summing afresh each time was 25 of the 41 ms a ghn3xlm16 program took to compile)
-        cache = self.__dict__.setdefault('_gap_cache', {})
-        pre = cache.setdefault(sa, [0])
+        pre = self._gap_cache.setdefault(sa, [0])
         while len(pre) <= sb - sa:
             pre.append(pre[-1] + round_up(self.param_numel(self.names[sa + len(pre) - 1]), 64))
         return pre[sb - sa]
@@ -1583,7 +1646,7 @@ class Program:
         self._ops = saved
         return ops
 
-    def _layer_side_ops(self, layers, rows):
+    def _layer_side_ops(self, sw, layers, rows):
         """Weight gradients (one grouped GEMM launch) and LayerNorm parameter gradients of the given Graphormer layers
         (autograd of graphormer.py:208-248), on the side stream."""
         C = self.C
@@ -1600,12 +1663,7 @@ class Program:
                       accum=True, dbias=self.gref(pre + 'attn.to_out.0.bias'))
             self.gemm(d['dqkv'], d['h1'], self.gref(Wq), 3 * C, C, rows, 3 * C, C, C, a_mode=L.MODE_COL, b_mode=L.MODE_COL,
                       accum=True)
-        # the split-bf16 weight-gradient kernel on 64 x 64 tiles (48); exact fp32 tiles (64) outside the 16-bit modes; the
-        # small-problem kernel for narrow models.  (49 = the same kernel on 128 x 128 tiles, half the operand bytes per flop:
-        # measured slower for the grouped launch, 6.61-6.63 against 6.54-6.56 ms per step -- fewer, fatter workgroups.)
-        dflt = ('48' if self.x3 else '64') if C >= 256 else '0'
-        self.gemm_op(p0, side=True, tile=int(os.environ.get('GHN3_LAYER_WGRAD_TILE', dflt)),
-                     grid_cap=int(os.environ.get('GHN3_LAYER_WGRAD_CAP', '0')) if self.SIDE else 0)
+        self.gemm_op(p0, side=True, tile=sw.layer_wgrad_tile, grid_cap=sw.layer_wgrad_cap if self.SIDE else 0)
         if len(layers) == 1:
             d = layers[0]
             pre = d['pre']
@@ -1628,17 +1686,13 @@ class Program:
                 ints=(len(tab), rows, C), flags=self.SIDE)
 
     # ------------------------------------------------------------------ backward
-    def _colsum(self, out, X, M, N, ld, q=0, s=0, stride=1, gather=None):
-        self.op(L.OP_COLSUM, refs=(out, X, gather if gather is not None else self.NONE),
-                ints=(M, N, ld, q, s, stride, 1))
-
     def set_tile_route(self, direct):
         """Switches the compiled backward between the fp32 route of the tile gradient (tile backward -> fp32 d_tiles ->
         cast passes with the measured maximum) and the direct 16-bit route (see _build_backward; only valid when the fused
         norm loss is the ONLY upstream term of the step).  Returns the indices of the ops it touched (all lie in front of
         the W2 weight gradient, i.e. in the first part of bwd_parts at the same index)."""
-        direct = bool(direct and getattr(self, 'tile_bwd_h16', 0))
-        if self.tile_bwd_op is None or not hasattr(self, 'd16_kinds'):
+        direct = bool(direct and self.tile_bwd_h16)
+        if self.tile_bwd_op is None:
             return []
         self.bwd_ops[self.tile_bwd_op]['i'][5] = self.tile_bwd_h16 if direct else 0
         touched = []
@@ -1648,17 +1702,45 @@ class Program:
                 touched.append(k)
         return touched
 
-    @staticmethod
-    def _wgrad_order_env():
-        """GHN3_WGRAD_ORDER: where the side-stream W2 weight gradient is issued in the single-process backward -- 'first'
-        (default; behind the tile backward and its operand copies, beside the W2 dgrad and the rest of the decoder backward),
-        'late' (rounds 3-5a: behind the decoder backward, beside the Graphormer backward only), 'early' (behind the dgrad)."""
-        return os.environ.get('GHN3_WGRAD_ORDER', 'first' if os.environ.get('GHN3_WGRAD_LATE', '1') != '0' else 'early')
+    def _backward_switches(self):
+        """Every GHN3_* variable the backward build and its scheduling read, each read once, here (what a switch governs and
+        the measurements behind its default stand with the code that uses it)."""
+        sw = SimpleNamespace()
+        sw.early_1d = os.environ.get('GHN3_EARLY_1D', '1') != '0'                   # _build_backward: 1-D decoder beside the dgrad
+        sw.tile_d16 = os.environ.get('GHN3_TILE_D16', '1') != '0'                   # _bwd_w2_operands: direct 16-bit tiles
+        sw.wgrad_prep_late = os.environ.get('GHN3_WGRAD_PREP_LATE', '1') == '1'     # ... weight-gradient copies behind the dgrad
+        sw.dgrad_planes = os.environ.get('GHN3_DGRAD_PLANES', '1') != '0'           # _bwd_w2_plane_mode
+        sw.dgrad_rect = os.environ.get('GHN3_DGRAD_RECT', '1') != '0'               # _bwd_w2_dgrad
+        sw.dgrad_pin = os.environ.get('GHN3_DGRAD_PIN', '1') != '0'                 # _bwd_w2_dgrad_planes
+        sw.dgrad_sub = os.environ.get('GHN3_DGRAD_SUB')
+        sw.dgrad_eq = os.environ.get('GHN3_DGRAD_EQ', '1') != '0'                   # _dgrad_chunk_bounds
+        sw.wgrad_tile = int(os.environ.get('GHN3_WGRAD_TILE', '29'))                # _bwd_w2_wgrad
+        sw.wgrad_sumsq = os.environ.get('GHN3_WGRAD_SUMSQ', '1') != '0'
+        sw.wgrad_tpw = int(os.environ.get('GHN3_WGRAD_TPW', '0'))
+        sw.wgrad_main, sw.wgrad_cap = os.environ.get('GHN3_WGRAD_MAIN'), os.environ.get('GHN3_WGRAD_CAP')     # _wgrad_schedule
+        # GHN3_WGRAD_ORDER: where the side-stream W2 weight gradient is issued in the single-process backward -- 'first'
+        # (default; behind the tile backward and its operand copies, beside the W2 dgrad and the rest of the decoder backward),
+        # 'late' (rounds 3-5a: behind the decoder backward, beside the Graphormer backward only), 'early' (behind the dgrad).
+        sw.wgrad_order = os.environ.get('GHN3_WGRAD_ORDER', 'first' if os.environ.get('GHN3_WGRAD_LATE', '1') != '0' else 'early')
+        sw.ddp_wgrad_first = os.environ.get('GHN3_DDP_WGRAD_FIRST', '1') != '0'     # _data_parallel_parts
+        sw.d2_dgrad_tile = int(os.environ.get('GHN3_D2_DGRAD_TILE', '0'))           # _bwd_conv0
+        sw.d2_dgrad_ks = int(os.environ.get('GHN3_D2_DGRAD_KS', '0'))
+        sw.d1_dgrad_tile = int(os.environ.get('GHN3_D1_DGRAD_TILE', '0'))           # _bwd_fc
+        sw.side_group = int(os.environ.get('GHN3_SIDE_GROUP', '4'))                 # _bwd_graphormer
+        sw.layer_wgrad_defer = os.environ.get('GHN3_LAYER_WGRAD_DEFER', '1') != '0'
+        sw.layer_wgrad_group = int(os.environ.get('GHN3_LAYER_WGRAD_GROUP', '0'))   # 0: one launch behind the chain
+        # _layer_side_ops: the split-bf16 weight-gradient kernel on 64 x 64 tiles (48); exact fp32 tiles (64) outside the 16-bit
+        # modes; the small-problem kernel for narrow models.  (49 = the same kernel on 128 x 128 tiles, half the operand bytes per
+        # flop: measured slower for the grouped launch, 6.61-6.63 against 6.54-6.56 ms per step -- fewer, fatter workgroups.)
+        sw.layer_wgrad_tile = int(os.environ.get('GHN3_LAYER_WGRAD_TILE', ('48' if self.x3 else '64') if self.C >= 256 else '0'))
+        sw.layer_wgrad_cap = int(os.environ.get('GHN3_LAYER_WGRAD_CAP', '0'))
+        sw.embed_bwd_main = os.environ.get('GHN3_EMBED_BWD_MAIN', '1') == '1'       # _bwd_embed_and_edge_bias
+        return sw
 
-    def _wgrad_schedule(self, flops, rows):
+    def _wgrad_schedule(self, sw, flops, rows):
         """Workgroups of the side-stream W2 weight gradient (a multiple of 8: a worker's tiles keep their XCD), or 0 = on the
         chain's stream in front of the Graphormer backward.  See the call site for the model and its measurements."""
-        env_main, env_cap = os.environ.get('GHN3_WGRAD_MAIN'), os.environ.get('GHN3_WGRAD_CAP')
+        env_main, env_cap = sw.wgrad_main, sw.wgrad_cap
         if not self.SIDE or env_main == '1':
             return 0
         if env_cap is not None:
@@ -1669,14 +1751,20 @@ class Program:
         ch_ms = self.Lyr * (0.030 + 0.014 * (rows / 256.0) * (self.C / 384.0) ** 2)      # the backward chain alone
         if env_main != '0' and w_ms < 0.75 * ch_ms:
             return 0
-        if self._wgrad_order_env() == 'first':
+        if sw.wgrad_order == 'first':
             return 128                                   # half of every XCD (see the call site)
         c = int(round(256.0 * w_ms / (1.75 * ch_ms) / 8.0)) * 8
         if c >= 232:
             return 0 if env_main != '0' else 224
         return max(64, c)
 
-    def _build_h16_table(self, g16, direct_member):
+    @staticmethod
+    def _direct_member(m_):
+        """Family members whose tile gradient GHN3_OP_TILE_BWD can write as 16-bit itself; classifier-weight rows (head dgrad)
+        and resized kernels (a GEMM over d_tiles) keep the fp32 route."""
+        return m_['kind'] == 'conv' and 'resize' not in m_
+
+    def _build_h16_table(self, g16):
         """Per tile descriptor {h, rel0, ld32 | ld16 << 32} of GHN3_OP_TILE_BWD's direct 16-bit output: where the fp32
         region of the descriptor lies inside its family's tile matrix and where that matrix's 16-bit copy `dth` starts
         (relative to d_tiles, in 16-bit elements).  h = INT64_MIN: the descriptor keeps its fp32 output."""
@@ -1687,7 +1775,7 @@ class Program:
         members = []
         for g in g16:
             for m_ in g['members']:
-                if direct_member(m_):
+                if self._direct_member(m_):
                     members.append((m_['tile_off'], m_['tile_off'] + m_['rows'] * g['ld'], g))
         members.sort(key=lambda t: t[0])
         if members and nd:
@@ -1710,15 +1798,42 @@ class Program:
         assert r_tab[0] == self.r_desc[0] and r_tab[1] > self.r_desc[1]
         self.tile_bwd_h16 = r_tab[1] - self.r_desc[1]        # ints[5] of the tile backward when the direct route is on
 
-    def _build_backward(self):
-        C, H, B, N, V, K = self.C, self.H, self.B, self.N, self.V, self.K
-        rows = B * N
-        ldT, ldK = self.ldT, self.ldK
-        ms = self.max_shape
-        S2 = self.S * self.S
+    def _build_backward(self, sw):
+        """The backward program (what torch autograd would run for GHN3.forward), one stage method per thing it computes, in
+        program order.  The bump allocator hands out workspace in call order, so the stages keep calling wsf / ws16 / idx / gemm
+        in this order (tests/test_program_digest_cpu.py catches a slip).  Returns the build state the scheduling needs."""
+        bb = _Backward(sw)
         M, n1 = self.M, self.n1
-        (r_types, r_shape, r_nn, r_noff, deg_in, deg_out, dist0, pair) = self.r_graph
-        xe = self.r_xe
+        self._bwd_memsets_and_tile(bb)
+        # The 1-D decoder backward needs the tile backward only: on the side stream beside the W2 dgrad instead of behind the
+        # decoder.fc backward on the chain; joined in front of the node-row gather that adds its rows
+        early_1d = bool(self.SIDE) and M > 0 and n1 > 0 and sw.early_1d
+        if early_1d:
+            self._bwd_decoder_1d(bb, True)
+            self.op(L.OP_JOIN, ints=(1, 0))              # mark: the 1-D backward (waited for in front of the node-row gather)
+        if M > 0:
+            self._bwd_resize_and_head(bb)
+            self._bwd_w2_plane_mode(bb)
+            if bb.g16:
+                self._bwd_w2_operands(bb)
+            self._bwd_w2_dgrad(bb)
+            self._bwd_w2_wgrad(bb)
+            self._bwd_conv0(bb)
+            self._bwd_fc(bb)
+        if not early_1d:
+            self._bwd_decoder_1d(bb, False)
+        # Everything above produces the decoder gradients (93 % of the gradient bytes at XL); a data-parallel caller
+        # may run the program in two parts (bwd_ops[:bwd_split] + DETACH, then the rest) and start their all-reduce here.
+        self.bwd_split = len(self._ops)
+        g_xe = self._bwd_node_rows(bb, early_1d)
+        g_xl = self._bwd_final_layernorm(bb, g_xe)
+        g_x0 = self._bwd_graphormer(bb, g_xl)
+        self._bwd_embed_and_edge_bias(bb, g_x0)
+        return bb
+
+    def _bwd_memsets_and_tile(self, bb):
+        """Gradient memsets, the workspace zero-fills of this program point and the tile backward."""
+        M, n1, ldK = self.M, self.n1, self.ldK
         # gradients of all GHN parameters start at zero; every parameter-gradient op accumulates
         # two memset ranges over the flat gradient buffer, patched at run time (offset, bytes): everything except
         # the parameters listed in grad_no_memset (tensors the backward fully overwrites)
@@ -1727,15 +1842,8 @@ class Program:
         self.op(L.OP_MEMSET0, refs=((self.xbuf(self.X_GRADFLAT), 0),), ints=(-1,))
         self.op(L.OP_MEMSET0, refs=((self.xbuf(self.X_GRADFLAT), 0),), ints=(-1,))
         self.memset_grad_op = 0
-        self.tile_bwd_op = None
-        self.grad_no_memset = []
         self.bwd_cut_w2 = 0
-        late_ops = []
-        self.wgrad_op_range = None
-        self.grad_sumsq = None      # set when the W2 weight gradient leaves its own sum of squares (see the band problems)
-
-        d_rows = self.wsf('d_xrows', (M + n1) * C)
-        # ---- tile backward -------------------------------------------------------------------------
+        bb.d_rows = self.wsf('d_xrows', (M + n1) * self.C)
         # (zero-fills of this program point are collected and emitted as ONE fill per run of neighbouring workspace regions -- the
         # regions are bump-allocated here, one behind the other, separated by their slack and alignment padding only: four
         # 5 us launches on the critical stream become one)
@@ -1750,19 +1858,18 @@ class Program:
                 self.wsf('d_clsout', n_cls * ldK)
                 zeros.append((self.wref('d_clsout'), 4 * n_cls * ldK))
         if n1 > 0:
-            mc = self.mc
-            self.wsf('d_w1d', n1 * 2 * mc)
-            zeros.append((self.wref('d_w1d'), 4 * n1 * 2 * mc))
+            self.wsf('d_w1d', n1 * 2 * self.mc)
+            zeros.append((self.wref('d_w1d'), 4 * n1 * 2 * self.mc))
             if self.n1_clsb:
                 self.wsf('d_cbout', self.n1_clsb * ldK)
                 zeros.append((self.wref('d_cbout'), 4 * self.n1_clsb * ldK))
         # running max |x| of d_tiles ([0], written by TILE_BWD) and d_u ([4], written by DACT): the power-of-two
         # scales of the f16 gradient copies
         self.r_amax = self.wsf('amax', 16)
-        scaled = self.bwd_scaled and self.direct16 and M > 0
-        amax_t = self.r_amax if scaled else None
-        amax_u = (self.r_amax[0], self.r_amax[1] + 16) if scaled else None
-        if scaled:
+        bb.scaled = self.bwd_scaled and self.direct16 and M > 0
+        bb.amax_t = self.r_amax if bb.scaled else None
+        bb.amax_u = (self.r_amax[0], self.r_amax[1] + 16) if bb.scaled else None
+        if bb.scaled:
             zeros.append((self.r_amax, 64))
         run = None
         for (buf, off), n in sorted(zeros, key=lambda it: (it[0][0], it[0][1])) + [((None, 0), 0)]:
@@ -1774,8 +1881,8 @@ class Program:
             run = [buf, off, n]
         if self.n_desc:
             grads = self._tile_sources(True)
-            if scaled:
-                grads[5] = amax_t
+            if bb.scaled:
+                grads[5] = bb.amax_t
             # r0 = upstream gradient of the predicted tensors and / or the fused norm loss (r6 = its device-side weight g,
             # r14 = per-tensor norms, r15 = the predicted values): GHN3._run_backward disables what a step does not use
             # (compiled with the norm term off: r6 / r14 / r15 absent; tile_bwd_refs = what GHN3._run_backward patches in)
@@ -1789,650 +1896,688 @@ class Program:
                           1 if self.decoder_bwd_ctype == L.CT_BF16 else 0),
                     flags=L.OPFLAG_TIMED | (self.TAG_TILE_BWD << 16))
 
-        def decoder_1d_bwd(side):
-            if n1 <= 0:
-                return
-            mc = self.mc
-            W1, b1 = 'decoder_1d.fc.0.weight', 'decoder_1d.fc.0.bias'
-            W2d, b2d = 'decoder_1d.fc.2.weight', 'decoder_1d.fc.2.bias'
-            Wb, bb = 'bias_class.1.weight', 'bias_class.1.bias'
-            h1d, w1d, d_w1d = self.wref('h1d'), self.wref('w1d'), self.wref('d_w1d')
-            d_h1d = self.wsf('d_h1d', n1 * 2 * C)
-            if self.n1_clsb:
-                cb0 = self.n1_plain
-                d_cb = self.wref('d_cbout')
-                w_cb = self.wref('w1d', cb0 * 2 * mc + mc)
-                p0 = self.gemm(d_cb, self.pref(Wb), self.wref('d_w1d', cb0 * 2 * mc + mc), self.n1_clsb, mc, K, ldK,
-                               mc, 2 * mc, a_mode=L.MODE_ROW, b_mode=L.MODE_COL, dact=L.DACT_RELU, aux_in=w_cb)
-                self.gemm_op(p0, side=side)
-                p0 = self.gemm(d_cb, w_cb, self.gref(Wb), K, mc, self.n1_clsb, ldK, 2 * mc, mc, a_mode=L.MODE_COL,
-                               b_mode=L.MODE_COL, accum=True, dbias=self.gref(bb))
-                self.gemm_op(p0, side=True)
-            p0 = self.gemm(d_w1d, self.pref(W2d), d_h1d, n1, 2 * C, 2 * mc, 2 * mc, 2 * C, 2 * C, a_mode=L.MODE_ROW,
-                           b_mode=L.MODE_COL, dact=L.DACT_RELU, aux_in=h1d)
+    def _bwd_decoder_1d(self, bb, side):
+        """1-D decoder backward (bn / bias / norm nodes); side: its dependent GEMMs run on the side stream too (issued early,
+        beside the W2 dgrad) instead of on the chain (issued late, behind the decoder.fc backward)."""
+        C, K, ldK, M, n1 = self.C, self.K, self.ldK, self.M, self.n1
+        if n1 <= 0:
+            return
+        mc = self.mc
+        W1, b1 = 'decoder_1d.fc.0.weight', 'decoder_1d.fc.0.bias'
+        W2d, b2d = 'decoder_1d.fc.2.weight', 'decoder_1d.fc.2.bias'
+        Wb, b_cls = 'bias_class.1.weight', 'bias_class.1.bias'
+        h1d, w1d, d_w1d = self.wref('h1d'), self.wref('w1d'), self.wref('d_w1d')
+        d_h1d = self.wsf('d_h1d', n1 * 2 * C)
+        if self.n1_clsb:
+            cb0 = self.n1_plain
+            d_cb = self.wref('d_cbout')
+            w_cb = self.wref('w1d', cb0 * 2 * mc + mc)
+            p0 = self.gemm(d_cb, self.pref(Wb), self.wref('d_w1d', cb0 * 2 * mc + mc), self.n1_clsb, mc, K, ldK,
+                           mc, 2 * mc, a_mode=L.MODE_ROW, b_mode=L.MODE_COL, dact=L.DACT_RELU, aux_in=w_cb)
             self.gemm_op(p0, side=side)
-            p0 = self.gemm(d_w1d, h1d, self.gref(W2d), 2 * mc, 2 * C, n1, 2 * mc, 2 * C, 2 * C, a_mode=L.MODE_COL,
-                           b_mode=L.MODE_COL, accum=True, dbias=self.gref(b2d))
+            p0 = self.gemm(d_cb, w_cb, self.gref(Wb), K, mc, self.n1_clsb, ldK, 2 * mc, mc, a_mode=L.MODE_COL,
+                           b_mode=L.MODE_COL, accum=True, dbias=self.gref(b_cls))
             self.gemm_op(p0, side=True)
-            p0 = self.gemm(d_h1d, self.pref(W1), (d_rows[0], d_rows[1] + 4 * M * C), n1, C, 2 * C, 2 * C, C, C,
-                           a_mode=L.MODE_ROW, b_mode=L.MODE_COL)
-            self.gemm_op(p0, side=side)
-            p0 = self.gemm(d_h1d, xe, self.gref(W1), 2 * C, C, n1, 2 * C, C, C, a_mode=L.MODE_COL, b_mode=L.MODE_COL,
-                           b_gather=self.r_src1, accum=True, dbias=self.gref(b1))
-            self.gemm_op(p0, side=True)
+        p0 = self.gemm(d_w1d, self.pref(W2d), d_h1d, n1, 2 * C, 2 * mc, 2 * mc, 2 * C, 2 * C, a_mode=L.MODE_ROW,
+                       b_mode=L.MODE_COL, dact=L.DACT_RELU, aux_in=h1d)
+        self.gemm_op(p0, side=side)
+        p0 = self.gemm(d_w1d, h1d, self.gref(W2d), 2 * mc, 2 * C, n1, 2 * mc, 2 * C, 2 * C, a_mode=L.MODE_COL,
+                       b_mode=L.MODE_COL, accum=True, dbias=self.gref(b2d))
+        self.gemm_op(p0, side=True)
+        p0 = self.gemm(d_h1d, self.pref(W1), (bb.d_rows[0], bb.d_rows[1] + 4 * M * C), n1, C, 2 * C, 2 * C, C, C,
+                       a_mode=L.MODE_ROW, b_mode=L.MODE_COL)
+        self.gemm_op(p0, side=side)
+        p0 = self.gemm(d_h1d, self.r_xe, self.gref(W1), 2 * C, C, n1, 2 * C, C, C, a_mode=L.MODE_COL, b_mode=L.MODE_COL,
+                       b_gather=self.r_src1, accum=True, dbias=self.gref(b1))
+        self.gemm_op(p0, side=True)
 
-        # The 1-D decoder backward needs the tile backward only: on the side stream beside the W2 dgrad instead of behind the
-        # decoder.fc backward on the chain; joined in front of the node-row gather that adds its rows
-        early_1d = bool(self.SIDE) and M > 0 and n1 > 0 and os.environ.get('GHN3_EARLY_1D', '1') != '0'
-        if early_1d:
-            decoder_1d_bwd(True)
-            self.op(L.OP_JOIN, ints=(1, 0))              # mark: the 1-D backward (waited for in front of the node-row gather)
-        Wfc, bfc = 'decoder.fc.0.weight', 'decoder.fc.0.bias'
-        W0, b0 = 'decoder.conv.0.weight', 'decoder.conv.0.bias'
-        W2, b2 = 'decoder.conv.2.weight', 'decoder.conv.2.bias'
+    def _bwd_resize_and_head(self, bb):
+        """Resized-kernel GEMMs and the classifier-head backward: what else writes the tile gradient d_tiles."""
+        K, ldK, ms, S2 = self.K, self.ldK, self.max_shape, self.S * self.S
         Wc, bc = 'decoder.class_layer_predictor.1.weight', 'decoder.class_layer_predictor.1.bias'
-        if M > 0:
-            # kernels larger than the decoder grid: d_tiles[p][c] = sum_pout Wb[pout][p] d_resized[pout][c]
+        # kernels larger than the decoder grid: d_tiles[p][c] = sum_pout Wb[pout][p] d_resized[pout][c]
+        p0 = len(self._probs)
+        for g in self.conv_groups:
+            if 'resize' in g:
+                kh, kw = g['resize']
+                self.gemm(g['r_wb'], self.wref('d_tiles', g['rs_off']), self.wref('d_tiles', g['tile_off']),
+                          S2, g['cols'], kh * kw, S2, g['ld'], g['ld'], a_mode=L.MODE_COL, b_mode=L.MODE_COL)
+        self.gemm_op(p0)
+        bb.t, bb.u = self.wref('t'), self.wref('u')
+        bb.d_t = self.wsf('d_t', self.M * 4 * self.C)
+        bb.d_u = self.wsf('d_u', self.M * 8 * self.C)
+        for g in self.conv_groups:
+            if g['kind'] != 'cls':
+                continue
+            # the head dgrad writes columns i' < i only; the pad columns (i <= i' < i_ld) must read as zero
+            self.op(L.OP_MEMSET0, refs=(self.wref('d_tiles', g['tile_off']),), ints=(4 * g['rows'] * g['ld'],))
             p0 = len(self._probs)
-            for g in self.conv_groups:
-                if 'resize' in g:
-                    kh, kw = g['resize']
-                    self.gemm(g['r_wb'], self.wref('d_tiles', g['rs_off']), self.wref('d_tiles', g['tile_off']),
-                              S2, g['cols'], kh * kw, S2, g['ld'], g['ld'], a_mode=L.MODE_COL, b_mode=L.MODE_COL)
+            for n_idx in range(len(g['inds'])):
+                tile_n = self.wref('tiles', g['tile_off'] + n_idx * g['ld'])
+                dtile_n = self.wref('d_tiles', g['tile_off'] + n_idx * g['ld'])
+                dout_n = self.wref('d_clsout', g['cls_off'][n_idx])
+                # d relu(tile)[o'][i'] = sum_k dout[i'][k] Wcls[k][o'], masked by tile > 0
+                self.gemm(self.pref(Wc), dout_n, dtile_n, ms[0], g['i'], K, ms[0], ldK, g['i_ld'],
+                          a_mode=L.MODE_COL, b_mode=L.MODE_ROW, dact=L.DACT_RELU, aux_in=tile_n)
             self.gemm_op(p0)
-            t, u = self.wref('t'), self.wref('u')
-            d_t = self.wsf('d_t', M * 4 * C)
-            d_u = self.wsf('d_u', M * 8 * C)
-            # classifier head backward
-            for g in self.conv_groups:
-                if g['kind'] != 'cls':
-                    continue
-                # the head dgrad writes columns i' < i only; the pad columns (i <= i' < i_ld) must read as zero
-                self.op(L.OP_MEMSET0, refs=(self.wref('d_tiles', g['tile_off']),), ints=(4 * g['rows'] * g['ld'],))
-                p0 = len(self._probs)
-                for n_idx in range(len(g['inds'])):
-                    tile_n = self.wref('tiles', g['tile_off'] + n_idx * g['ld'])
-                    dtile_n = self.wref('d_tiles', g['tile_off'] + n_idx * g['ld'])
-                    dout_n = self.wref('d_clsout', g['cls_off'][n_idx])
-                    # d relu(tile)[o'][i'] = sum_k dout[i'][k] Wcls[k][o'], masked by tile > 0
-                    self.gemm(self.pref(Wc), dout_n, dtile_n, ms[0], g['i'], K, ms[0], ldK, g['i_ld'],
-                              a_mode=L.MODE_COL, b_mode=L.MODE_ROW, dact=L.DACT_RELU, aux_in=tile_n)
-                self.gemm_op(p0)
-                for n_idx in range(len(g['inds'])):
-                    tile_n = self.wref('tiles', g['tile_off'] + n_idx * g['ld'])
-                    dout_n = self.wref('d_clsout', g['cls_off'][n_idx])
-                    p0 = self.gemm(dout_n, tile_n, self.gref(Wc), K, ms[0], g['i'], ldK, g['i_ld'], ms[0],
-                                   a_mode=L.MODE_COL, b_mode=L.MODE_ROW, accum=True, dbias=self.gref(bc))
-                    self.gemm_op(p0, side=True)
-            # D3 backward: d_u = (d_tiles . W2sub) * (u > 0)   -- all groups, one launch.  The reduction runs over
-            # the o*i columns of a group (up to C^2 = 147456) while M x N is only rows x 8C, so the K range is
-            # split into chunks (partial sums added atomically into the zeroed d_u) to fill the 256 CUs; the ReLU
-            # mask is applied afterwards in place.
-            bct = self.decoder_bwd_ctype
-            g16 = [g for g in self.gemm_groups if g['op16']]
-            # planes: the K splits of the 16-bit dgrad write separate partial planes (plane 0 = d_u) that the DACT pass
-            # sums in a fixed order -- no atomics, no memset of d_u, deterministic gradients
-            planes = bool(g16) and os.environ.get('GHN3_DGRAD_PLANES', '1') != '0'
-            # exact-fp32 mode (no 16-bit groups): the K chunks write partial planes as well (round 3; they used to add
-            # atomically into a zeroed d_u, the one non-deterministic reduction left on the path)
-            planes32 = (not g16) and os.environ.get('GHN3_DGRAD_PLANES', '1') != '0'
-            if not planes and not planes32:
-                self.op(L.OP_MEMSET0, refs=(d_u,), ints=(4 * M * 8 * C,))
-            if g16:
-                # 16-bit copies of the backward operands: per group d_tiles straight (dgrad A operand); for the wgrad
-                # transposed copies of d_tiles (A) and u (B) + the column sums of d_tiles = the conv.2 bias gradient.
-                # wgrad bands.  dW2 row (o', i') sums over every decoder row r with o_r > o' and i_r > i' (nn.py:749-750,
-                # 760: a row only consumes the W2 rows o' < o_r, i' < i_r).  The input-channel axis is cut at the distinct
-                # group widths into BANDS [i_lo, i_hi): for i' in a band the contributing rows are exactly those with
-                # i_r >= i_hi, whatever their family.  Per band these rows are concatenated along k in order of
-                # decreasing o_r (transposed copy dthT_b [(o', i' - i_lo)][k], u copy uhT_b [8C][k]), so the W2 rows
-                # with o' in [o_lo, o_hi) need exactly a k PREFIX: one GEMM problem per (band, o range), all in ONE
-                # launch, and every dW2 row is written exactly once -- no accumulation into dW2 between families (was
-                # 2 GB read + 2 GB written per step at ghn3xlm16) and no memset of it when the bands cover it.
-                # Direct 16-bit tiles (round 4, GHN3_TILE_D16): with the fused norm loss alone the tile backward writes the
-                # scaled 16-bit copy `dth` itself (scale from an a-priori bound, GHN3_OP_TILE_BWD) -- no fp32 d_tiles for
-                # the rows it produces, no straight cast pass on the critical path, and the transposed wgrad operands are
-                # re-laid out from the 16-bit copy.  Rows the tile backward does not produce (classifier-weight rows: head
-                # dgrad; resized kernels: a GEMM over d_tiles) keep the fp32 route.  Both op sets are compiled; GHN3.
-                # _run_backward switches per step (an upstream gradient `dout` has no bound: fp32 + measured maximum).
-                d16 = bool(scaled and self.tile_bwd_op is not None and os.environ.get('GHN3_TILE_D16', '1') != '0')
-                direct_member = lambda m_: m_['kind'] == 'conv' and 'resize' not in m_
-                items, side_items, items_d16, side_d16, u_items = [], [], [], [], []
-                rowsets, bias_sets, n_parts = [], [], 0
-                for g in g16:
-                    g['dth_ld'] = round_up(g['cols'], 64) + 64        # (+64: rows never a power of two apart)
-                    g['dth'] = self.ws16('dth%d' % g['row0'], g['rows'] * g['dth_ld'])
-                    # (rows of a family with a smaller extent keep zeros beyond it: d_tiles is never written there)
-                    items.append(dict(src_off=self._ws_names['d_tiles'] // 4 + g['tile_off'], rows=g['rows'],
-                                      cols=g['cols'], ld_src=g['ld'], straight=(g['dth'], g['dth_ld'], bct),
-                                      scaled=scaled))
-                    for m_ in g['members']:
-                        if not direct_member(m_):
-                            r_ = m_['row0'] - g['row0']
-                            items_d16.append(dict(src_off=self._ws_names['d_tiles'] // 4 + g['tile_off'] + r_ * g['ld'],
-                                                  rows=m_['rows'], cols=g['cols'], ld_src=g['ld'],
-                                                  straight=(g['dth'] + r_ * g['dth_ld'], g['dth_ld'], bct), scaled=scaled))
-                    for sb in g['subs']:
-                        rowsets.append(dict(o=sb['o'], i=g['i_ld'], row0=sb['row0'], rows=sb['rows'], g=g))
-                self.wgrad_bands = []
-                i_lo = 0
-                for i_hi in sorted({rs['i'] for rs in rowsets}):
-                    members = sorted((rs for rs in rowsets if rs['i'] >= i_hi), key=lambda rs: -rs['o'])
-                    bw = i_hi - i_lo
-                    k_off, mem = 0, []
-                    for rs in members:
-                        mem.append(dict(rs, k_off=k_off))
-                        k_off += round_up(rs['rows'], 8)
-                    ktot = round_up(k_off, 64)
-                    band = dict(i_lo=i_lo, bw=bw, members=mem, ktot=ktot, o_max=mem[0]['o'])
-                    band['dthT'] = self.ws16('dthT_b%d' % i_lo, band['o_max'] * bw * ktot)
-                    band['uhT'] = self.ws16('uhT_b%d' % i_lo, 8 * C * ktot)
-                    self.wgrad_bands.append(band)
-                    for m_ in mem:
-                        g = m_['g']
-                        side_items.append(dict(src_off=self._ws_names['d_tiles'] // 4 + g['tile_off'] +
-                                               (m_['row0'] - g['row0']) * g['ld'] + i_lo, rows=m_['rows'],
-                                               cols=m_['o'] * bw, ld_src=g['ld'], src_map=(bw, m_['i']),
-                                               transposed=(band['dthT'] + m_['k_off'], ktot, bct),
-                                               scaled=scaled, tight=True, colsum_parts=n_parts))
-                        # (direct 16-bit tiles: the same band copy from the family's 16-bit matrix -- every row of it is
-                        # complete once the straight cast of the fp32-route rows has run)
-                        side_d16.append(dict(src_off=g['dth'] + (m_['row0'] - g['row0']) * g['dth_ld'] + i_lo, rows=m_['rows'],
-                                             cols=m_['o'] * bw, ld_src=g['dth_ld'], src_map=(bw, m_['i']),
-                                             transposed=(band['dthT'] + m_['k_off'], ktot, bct),
-                                             scaled=scaled, tight=True, colsum_parts=n_parts, src16=True))
-                        bias_sets.append((n_parts, (m_['rows'] + 63) // 64, m_['o'], bw, m_['o'] * bw, i_lo))
-                        n_parts += ((m_['rows'] + 63) // 64) * m_['o'] * bw
-                        u_items.append(dict(src_off=u[1] // 4 + m_['row0'] * 8 * C, rows=m_['rows'], cols=8 * C,
-                                            ld_src=8 * C, transposed=(band['uhT'] + m_['k_off'], ktot, bct),
-                                            tight=True))
-                    i_lo = i_hi
-                self._d16_on, self._d16_off = [], []
+            for n_idx in range(len(g['inds'])):
+                tile_n = self.wref('tiles', g['tile_off'] + n_idx * g['ld'])
+                dout_n = self.wref('d_clsout', g['cls_off'][n_idx])
+                p0 = self.gemm(dout_n, tile_n, self.gref(Wc), K, ms[0], g['i'], ldK, g['i_ld'], ms[0],
+                               a_mode=L.MODE_COL, b_mode=L.MODE_ROW, accum=True, dbias=self.gref(bc))
+                self.gemm_op(p0, side=True)
 
-                def marked(into, fn):
-                    n0 = len(self._ops)
-                    fn()
-                    if d16:
-                        into.extend(self._ops[n0:])
+    def _bwd_w2_plane_mode(self, bb):
+        """D3 backward: d_u = (d_tiles . W2sub) * (u > 0)   -- all groups, one launch.  The reduction runs over
+        the o*i columns of a group (up to C^2 = 147456) while M x N is only rows x 8C, so the K range is
+        split into chunks to fill the 256 CUs; the ReLU mask is applied afterwards in place.  This stage decides how the chunks are
+        summed (bb.planes16 / bb.planes32) and lists the 16-bit groups (bb.g16)."""
+        bb.bct = self.decoder_bwd_ctype
+        bb.g16 = [g for g in self.gemm_groups if g['op16']]
+        # planes: the K splits of the 16-bit dgrad write separate partial planes (plane 0 = d_u) that the DACT pass
+        # sums in a fixed order -- no atomics, no memset of d_u, deterministic gradients
+        bb.planes16 = bool(bb.g16) and bb.sw.dgrad_planes
+        # exact-fp32 mode (no 16-bit groups): the K chunks write partial planes as well (round 3; they used to add
+        # atomically into a zeroed d_u, the one non-deterministic reduction left on the path)
+        bb.planes32 = (not bb.g16) and bb.sw.dgrad_planes
+        if not bb.planes16 and not bb.planes32:
+            # (GHN3_DGRAD_PLANES=0: partial sums added atomically into the zeroed d_u)
+            self.op(L.OP_MEMSET0, refs=(bb.d_u,), ints=(4 * self.M * 8 * self.C,))
 
-                # the dgrad operand on the critical path; the wgrad operands (and the bias gradient) beside it
-                marked(self._d16_off, lambda: self.cast16((self.xbuf(self.X_WS), 0), items, amax=amax_t))
-                if d16:
-                    marked(self._d16_on, lambda: self.cast16((self.xbuf(self.X_WS), 0), items_d16, amax=amax_t))
-                    self._build_h16_table(g16, direct_member)
-                # decoder.conv.2.bias gradient = column sums of d_tiles: every 64-row tile of the transposed band copies
-                # leaves its partial sums in a slot (no atomics), GHN3_OP_ROWSET_COLSUM adds the slots of a bias entry
-                # (all row tiles of all row sets with o_r > o', i_r > i') in a fixed order: deterministic
-                parts = self.wsf('b2_parts', n_parts)
-                # The operand copies of the weight gradient are issued BEHIND the dgrad: the side stream starts them when
-                # the dgrad is done instead of beside it (GHN3_WGRAD_PREP_LATE=0).  Same step time, but the dgrad -- on the
-                # critical path -- no longer shares the fabric with a 0.8 GB copy: 1.12 -> 1.03 ms.
-                prep_late = os.environ.get('GHN3_WGRAD_PREP_LATE', '1') == '1'
-                main_ops = self._ops
-                if prep_late:
-                    self._ops = []
-                marked(self._d16_off, lambda: self.cast16((self.xbuf(self.X_WS), 0), side_items + u_items, dbias=parts,
-                                                          flags=self.SIDE, amax=amax_t))
-                if d16:
-                    marked(self._d16_on, lambda: self.cast16((self.xbuf(self.X_WS), 0), side_d16 + u_items, dbias=parts,
-                                                             flags=self.SIDE, amax=amax_t))
-                sets = np.zeros(len(bias_sets), dtype=L.ROWSET_DT)
-                for k_, (off, n_rt, o_, bw_, ld_, i0_) in enumerate(bias_sets):
-                    sets[k_] = (off, n_rt, o_, bw_, ld_, i0_, 0)
-                self.op(L.OP_ROWSET_COLSUM, refs=(self.gref(b2), parts, self.idx(sets)),
-                        ints=(len(sets), ms[0], ms[1]), flags=self.SIDE)
-                late_ops, self._ops = (self._ops, main_ops) if prep_late else ([], main_ops)
+    def _w2_operand_items(self, bb):
+        """Layout of the 16-bit copies of the W2 backward operands and the GHN3_OP_CAST16 items that write them.
+        Per group d_tiles straight (dgrad A operand); for the wgrad
+        transposed copies of d_tiles (A) and u (B) + the column sums of d_tiles = the conv.2 bias gradient.
+        wgrad bands.  dW2 row (o', i') sums over every decoder row r with o_r > o' and i_r > i' (nn.py:749-750,
+        760: a row only consumes the W2 rows o' < o_r, i' < i_r).  The input-channel axis is cut at the distinct
+        group widths into BANDS [i_lo, i_hi): for i' in a band the contributing rows are exactly those with
+        i_r >= i_hi, whatever their family.  Per band these rows are concatenated along k in order of
+        decreasing o_r (transposed copy dthT_b [(o', i' - i_lo)][k], u copy uhT_b [8C][k]), so the W2 rows
+        with o' in [o_lo, o_hi) need exactly a k PREFIX: one GEMM problem per (band, o range), all in ONE
+        launch, and every dW2 row is written exactly once -- no accumulation into dW2 between families (was
+        2 GB read + 2 GB written per step at ghn3xlm16) and no memset of it when the bands cover it.
+        Returns the item lists: straight (all rows / the rows the direct route leaves to the fp32 route), band copies from
+        the fp32 tile gradient / from the 16-bit family matrix, u copies; the bias-gradient row sets and their slot count."""
+        C, bct, scaled = self.C, bb.bct, bb.scaled
+        d_tiles = self._ws_names['d_tiles'] // 4
+        it = SimpleNamespace(straight=[], straight_d16=[], band=[], band_d16=[], u=[], bias_sets=[], n_parts=0)
+        rowsets = []
+        for g in bb.g16:
+            g['dth_ld'] = round_up(g['cols'], 64) + 64        # (+64: rows never a power of two apart)
+            g['dth'] = self.ws16('dth%d' % g['row0'], g['rows'] * g['dth_ld'])
+            # (rows of a family with a smaller extent keep zeros beyond it: d_tiles is never written there)
+            it.straight.append(dict(src_off=d_tiles + g['tile_off'], rows=g['rows'], cols=g['cols'], ld_src=g['ld'],
+                                    straight=(g['dth'], g['dth_ld'], bct), scaled=scaled))
+            for m_ in g['members']:
+                if not self._direct_member(m_):
+                    r_ = m_['row0'] - g['row0']
+                    it.straight_d16.append(dict(src_off=d_tiles + g['tile_off'] + r_ * g['ld'], rows=m_['rows'],
+                                                cols=g['cols'], ld_src=g['ld'],
+                                                straight=(g['dth'] + r_ * g['dth_ld'], g['dth_ld'], bct), scaled=scaled))
+            for sb in g['subs']:
+                rowsets.append(dict(o=sb['o'], i=g['i_ld'], row0=sb['row0'], rows=sb['rows'], g=g))
+        i_lo = 0
+        for i_hi in sorted({rs['i'] for rs in rowsets}):
+            members = sorted((rs for rs in rowsets if rs['i'] >= i_hi), key=lambda rs: -rs['o'])
+            bw = i_hi - i_lo
+            k_off, mem = 0, []
+            for rs in members:
+                mem.append(dict(rs, k_off=k_off))
+                k_off += round_up(rs['rows'], 8)
+            ktot = round_up(k_off, 64)
+            band = dict(i_lo=i_lo, bw=bw, members=mem, ktot=ktot, o_max=mem[0]['o'])
+            band['dthT'] = self.ws16('dthT_b%d' % i_lo, band['o_max'] * bw * ktot)
+            band['uhT'] = self.ws16('uhT_b%d' % i_lo, 8 * C * ktot)
+            bb.bands.append(band)
+            for m_ in mem:
+                g = m_['g']
+                r_ = m_['row0'] - g['row0']
+                to_band = dict(rows=m_['rows'], cols=m_['o'] * bw, src_map=(bw, m_['i']),
+                               transposed=(band['dthT'] + m_['k_off'], ktot, bct), scaled=scaled, tight=True,
+                               colsum_parts=it.n_parts)
+                it.band.append(dict(to_band, src_off=d_tiles + g['tile_off'] + r_ * g['ld'] + i_lo, ld_src=g['ld']))
+                # (direct 16-bit tiles: the same band copy from the family's 16-bit matrix -- every row of it is
+                # complete once the straight cast of the fp32-route rows has run)
+                it.band_d16.append(dict(to_band, src_off=g['dth'] + r_ * g['dth_ld'] + i_lo, ld_src=g['dth_ld'], src16=True))
+                it.bias_sets.append((it.n_parts, (m_['rows'] + 63) // 64, m_['o'], bw, m_['o'] * bw, i_lo))
+                it.n_parts += ((m_['rows'] + 63) // 64) * m_['o'] * bw
+                it.u.append(dict(src_off=bb.u[1] // 4 + m_['row0'] * 8 * C, rows=m_['rows'], cols=8 * C,
+                                 ld_src=8 * C, transposed=(band['uhT'] + m_['k_off'], ktot, bct), tight=True))
+            i_lo = i_hi
+        return it
+
+    def _cut_ops(self, n0):
+        """Takes the ops emitted since op index n0 off the program and returns them: the caller issues them later."""
+        cut = self._ops[n0:]
+        del self._ops[n0:]
+        return cut
+
+    def _route_cast16(self, route_ops, items, **kw):
+        """One cast16 over workspace sources whose op (if any item gives it work) belongs to ONE route of the tile gradient:
+        route_ops = that route's op list, or None in a program without the direct route."""
+        n0 = len(self._ops)
+        self.cast16((self.xbuf(self.X_WS), 0), items, **kw)
+        if route_ops is not None:
+            route_ops.extend(self._ops[n0:])
+
+    def _bwd_w2_operands(self, bb):
+        """16-bit copies of the W2 backward operands (layout: _w2_operand_items), the decoder.conv.2.bias gradient and the
+        `late` op list.
+        Direct 16-bit tiles (round 4, GHN3_TILE_D16): with the fused norm loss alone the tile backward writes the
+        scaled 16-bit copy `dth` itself (scale from an a-priori bound, GHN3_OP_TILE_BWD) -- no fp32 d_tiles for
+        the rows it produces, no straight cast pass on the critical path, and the transposed wgrad operands are
+        re-laid out from the 16-bit copy.  Rows the tile backward does not produce (classifier-weight rows: head
+        dgrad; resized kernels: a GEMM over d_tiles) keep the fp32 route.  Both op sets are compiled; GHN3.
+        _run_backward switches per step (an upstream gradient `dout` has no bound: fp32 + measured maximum)."""
+        sw, ms = bb.sw, self.max_shape
+        d16 = bool(bb.scaled and self.tile_bwd_op is not None and sw.tile_d16)
+        on, off = (bb.d16_on, bb.d16_off) if d16 else (None, None)
+        it = self._w2_operand_items(bb)
+        self.wgrad_bands = bb.bands
+        # the dgrad operand on the critical path; the wgrad operands (and the bias gradient) beside it
+        self._route_cast16(off, it.straight, amax=bb.amax_t)
+        if d16:
+            self._route_cast16(on, it.straight_d16, amax=bb.amax_t)
+            self._build_h16_table(bb.g16)
+        # decoder.conv.2.bias gradient = column sums of d_tiles: every 64-row tile of the transposed band copies
+        # leaves its partial sums in a slot (no atomics), GHN3_OP_ROWSET_COLSUM adds the slots of a bias entry
+        # (all row tiles of all row sets with o_r > o', i_r > i') in a fixed order: deterministic
+        parts = self.wsf('b2_parts', it.n_parts)
+        # The operand copies of the weight gradient are issued BEHIND the dgrad: the side stream starts them when
+        # the dgrad is done instead of beside it (GHN3_WGRAD_PREP_LATE=0).  Same step time, but the dgrad -- on the
+        # critical path -- no longer shares the fabric with a 0.8 GB copy: 1.12 -> 1.03 ms.
+        n_chain = len(self._ops)
+        self._route_cast16(off, it.band + it.u, dbias=parts, flags=self.SIDE, amax=bb.amax_t)
+        if d16:
+            self._route_cast16(on, it.band_d16 + it.u, dbias=parts, flags=self.SIDE, amax=bb.amax_t)
+        sets = np.zeros(len(it.bias_sets), dtype=L.ROWSET_DT)
+        for k_, (off_, n_rt, o_, bw_, ld_, i0_) in enumerate(it.bias_sets):
+            sets[k_] = (off_, n_rt, o_, bw_, ld_, i0_, 0)
+        self.op(L.OP_ROWSET_COLSUM, refs=(self.gref('decoder.conv.2.bias'), parts, self.idx(sets)),
+                ints=(len(sets), ms[0], ms[1]), flags=self.SIDE)
+        if sw.wgrad_prep_late:
+            bb.late_ops = self._cut_ops(n_chain)         # (appended behind the dgrad launch by _bwd_w2_dgrad)
+
+    def _dgrad_ksplit(self, g, use_rect):
+        """K splits of a group's dgrad: until the launch offers ~512 tiles of 128 x 128 (two workgroups per CU;
+        measured best among 512 .. 3072: more splits only add traffic and tile-count quantisation); families with
+        >= 512 rows run on 256 x 128 three-stage tiles (tile code 20, one workgroup per CU) and are split to ~1.75
+        workgroups per CU (measured plateau 5 <= ks <= 8 for 768 rows: 1.1-1.2 ms against 1.45-1.55 ms)."""
+        C = self.C
+        tiles = ((g['rows'] + 127) // 128) * ((8 * C + 127) // 128)
+        tgt = 512 if g['op16'] else 2048       # (the fp32-operand kernel likes ~2048 tiles: 8.2 vs 9.8 ms)
+        ks = int(max(2, min(64, (tgt + tiles - 1) // tiles, g['cols'] // 1024)))
+        if g['op16'] and g['rows'] >= 512 and use_rect:
+            t20 = ((g['rows'] + 255) // 256) * ((8 * C + 127) // 128)
+            ks = int(max(2, min(16, round(448.0 / t20), g['cols'] // 1024)))
+        return ks
+
+    def _bwd_w2_dgrad_planes(self, bb, use_rect):
+        """Plane and chunk layout of the W2 dgrad: how many partial planes the launch writes (bb.n_planes, for the first
+        bb.rows16 decoder rows, into bb.d_up), the chunk count g['nc'] of every 16-bit group and the sub-split of a chunk."""
+        C, M, sw = self.C, self.M, bb.sw
+        bb.n_planes, bb.rows16, bb.pinned = 1, 0, False
+        if bb.planes32:
+            bb.n_planes = int(max(1, min(8, max(g['o'] for g in self.gemm_groups))))
+            bb.rows16 = M
+        if bb.planes16:
+            # every 16-bit group writes the same number of planes (its own chunk count <= 8, K = 0 problems -- zeros
+            # -- for the rest), so that one reduction pass serves all rows
+            # GHN3_DGRAD_PIN (default on): eight K chunks per family, chunk j on XCD j -- the chunk's slices of d_tiles and
+            # of W2^T are then fetched by one L2 instead of by all eight (4.1 GB of fetches per step without it)
+            for g in bb.g16:
+                g['nc'] = int(max(1, min(8, g['o']))) if sw.dgrad_pin else \
+                    int(max(1, min(8, self._dgrad_ksplit(g, use_rect), g['o'])))
+            nc_max = max(g['nc'] for g in bb.g16)
+            bb.pinned = sw.dgrad_pin and nc_max == 8
+            # Sub-chunks (round 3).  With one K chunk per XCD a family of two or three row tiles is 24 .. 36 output tiles on
+            # the XCD's 32 CUs: a quarter of the CUs idles, or a second round starts for a handful of tiles.  Each chunk is
+            # therefore cut again into parts `sub` (e.g. 3/4 + 1/4: the eight CUs the long parts leave free take three
+            # quarter parts each); every part writes its own partial plane.  The split is chosen by simulating the
+            # longest-first dispatch of one XCD's tiles (a plane costs ~7 us of extra traffic).
+            bb.sub = self._dgrad_sub_split(bb.g16, 8 * C) if (bb.pinned and self.use_p8) else (1,)
+            if sw.dgrad_sub:
+                bb.sub = tuple(int(v) for v in sw.dgrad_sub.split(','))
+            self.dgrad_sub = bb.sub                      # (reported: tools/p8_dump.py)
+            bb.n_planes = nc_max * len(bb.sub)
+            bb.rows16 = sum(g['rows'] for g in bb.g16)
+            assert all(g['row0'] < bb.rows16 for g in bb.g16), 'op16 groups first'
+        if bb.planes16 or bb.planes32:
+            bb.d_up = self.wsf('d_u_parts', max(bb.n_planes - 1, 1) * M * 8 * C)
+
+    def _dgrad_chunk_bounds(self, g, unit, equalise):
+        """Chunk boundaries of a 16-bit family's dgrad in W2 rows o' (multiples of `unit`: every part is whole 64-wide k tiles).
+        A family's narrow members only reach the first chunks, so equal chunks would give the first XCDs more work than
+        the last: the boundaries equalise the WORK (row tiles alive at o' x their cost) instead of the length."""
+        if g['p8'] and g['nc'] == 8 and equalise:
+            dens = np.zeros(g['o'])
+            for (m0_, mi_, ext_) in g['mtiles']:
+                dens[:min(g['o'], int(ext_) // g['i_ld'])] += self.p8_cost(mi_)
+            cw = np.concatenate([[0.0], np.cumsum(dens)])
+            bounds = [0]
+            for j in range(1, g['nc']):
+                b = int(np.searchsorted(cw, cw[-1] * j / g['nc']))
+                bounds.append(min(g['o'], max(bounds[-1], round_up(b, unit))))
+            return bounds + [round_up(g['o'], unit)]
+        oc = round_up((g['o'] + g['nc'] - 1) // g['nc'], unit)
+        return [min(j * oc, round_up(g['o'], unit)) for j in range(g['nc'])] + [round_up(g['o'], unit)]
+
+    def _dgrad_family_planes(self, bb, g):
+        """The dgrad problems of one 16-bit family: plane pl = part pl % len(sub) of K chunk pl // len(sub)."""
+        C, M, ms, sub = self.C, self.M, self.max_shape, bb.sub
+        # chunk j covers the W2 rows o' in [j * oc, (j + 1) * oc): k = o' * i + i' is contiguous in the copy
+        # of d_tiles and a multiple of the k-map period i, so A and B just start further in
+        # (the kernel consumes whole 64-wide k tiles: a chunk is a multiple of 64 so that the next chunk's
+        # data is never read as padding)
+        unit = 64 // math.gcd(g['i_ld'], 64)
+        bounds = self._dgrad_chunk_bounds(g, unit, bb.sw.dgrad_eq)
+        for pl in range(bb.n_planes):
+            j, sidx = pl // len(sub), pl % len(sub)
+            if j < g['nc']:
+                lo_, hi_ = bounds[j], bounds[j + 1]
+                cuts = [lo_ + min(hi_ - lo_, round_up(int(round((hi_ - lo_) * float(v) / sum(sub))), unit))
+                        for v in np.concatenate([[0], np.cumsum(sub)])]
+                cuts[-1] = hi_
+                o0, o1 = cuts[sidx], max(cuts[sidx], cuts[sidx + 1])
+            else:
+                o0 = o1 = round_up(g['o'], unit)
+            k0 = o0 * g['i_ld']
+            kc = max(0, min(g['cols'] - k0, (o1 - o0) * g['i_ld']))
+            dst = (bb.d_u[0], bb.d_u[1] + 4 * g['row0'] * 8 * C) if pl == 0 else \
+                (bb.d_up[0], bb.d_up[1] + 4 * ((pl - 1) * M + g['row0']) * 8 * C)
+            lim = None
+            if g['ragged'] or kc < g['cols']:
+                lim = self.idx(np.clip(g['lim128'] - k0, 0, kc).astype(np.int32))
+            mt = None
+            if g['p8']:
+                mt = g['mtiles'].copy()
+                mt[:, 2] = np.clip(mt[:, 2] - k0, 0, kc)
+                mt = (self.idx(mt), len(mt))
+            self.gemm(self.href(g['dth'] + min(k0, g['cols'])),
+                      self.sref(self.w2hT + min(o0, g['o']) * ms[1]), dst,
+                      g['rows'], 8 * C, kc, g['dth_ld'], self.w2hT_ld, 8 * C, op16=True,
+                      b_kmap=(g['i_ld'], ms[1]), lim=lim, lim_kind=2, alpha_amax=bb.amax_t,
+                      xcd=j if bb.pinned else None, mtiles=mt)
+
+    def _bwd_w2_dgrad(self, bb):
+        """W2 dgrad (one launch for all groups), the weight gradient's operand copies behind it, and the DACT pass that sums
+        the partial planes and applies the ReLU mask."""
+        C, M, ms = self.C, self.M, self.max_shape
+        W2 = 'decoder.conv.2.weight'
+        p0 = len(self._probs)
+        fl = 0.0
+        use_rect = bool(bb.g16) and all(g['op16'] for g in self.gemm_groups if g['rows'] >= 512) and \
+            any(g['op16'] and g['rows'] >= 512 for g in self.gemm_groups) and bb.sw.dgrad_rect
+        self._bwd_w2_dgrad_planes(bb, use_rect)
+        d_u, d_up = bb.d_u, bb.d_up
+        for g in self.gemm_groups:
+            fl += sum(2.0 * sb['rows'] * sb['cols'] * 8 * C for sb in g['subs'])
+            d_u_g = (d_u[0], d_u[1] + 4 * g['row0'] * 8 * C)
+            if bb.planes16 and g['op16']:
+                self._dgrad_family_planes(bb, g)
+            elif bb.planes32:
+                # chunk j = W2 rows o' in [j oc, (j + 1) oc): a multiple of the row-map period i, so A and B just start
+                # further in; chunks beyond a group's own o range are K = 0 problems (zeros)
+                oc = round_up((g['o'] + bb.n_planes - 1) // bb.n_planes, 4)      # (k0 * 4 bytes stays 16-byte aligned)
+                for j in range(bb.n_planes):
+                    o0 = min(j * oc, round_up(g['o'], 4))
+                    k0 = o0 * g['i_ld']
+                    kc = max(0, min(g['cols'] - k0, oc * g['i_ld']))
+                    dst = d_u_g if j == 0 else (d_up[0], d_up[1] + 4 * ((j - 1) * M + g['row0']) * 8 * C)
+                    self.gemm(self.wref('d_tiles', g['tile_off'] + k0), self.pref(W2, o0 * ms[1] * 8 * C),
+                              dst, g['rows'], 8 * C, kc, g['ld'], 8 * C, 8 * C, a_mode=L.MODE_ROW, b_mode=L.MODE_COL,
+                              b_qs=(g['i_ld'], ms[1]))
+            elif bb.planes16:
+                # (groups outside the 16-bit pipeline have i <= 4: a short reduction, one pass into plane 0)
+                self.gemm(self.wref('d_tiles', g['tile_off']), self.pref(W2), d_u_g,
+                          g['rows'], 8 * C, g['cols'], g['ld'], 8 * C, 8 * C, a_mode=L.MODE_ROW, b_mode=L.MODE_COL,
+                          b_qs=(g['i_ld'], ms[1]))
+            elif g['op16']:
+                # (atomic fallback) one problem per family; the K loop of a row tile stops at the largest extent of its rows
+                self.gemm(self.href(g['dth']), self.sref(self.w2hT), d_u_g,
+                          g['rows'], 8 * C, g['cols'], g['dth_ld'], self.w2hT_ld, 8 * C,
+                          ksplit=self._dgrad_ksplit(g, use_rect), op16=True,
+                          b_kmap=(g['i_ld'], ms[1]), lim=self.idx(g['lim128']) if g['ragged'] else None,
+                          lim_kind=2, alpha_amax=bb.amax_t)
+            else:
+                self.gemm(self.wref('d_tiles', g['tile_off']), self.pref(W2), d_u_g,
+                          g['rows'], 8 * C, g['cols'], g['ld'], 8 * C, 8 * C, a_mode=L.MODE_ROW, b_mode=L.MODE_COL,
+                          b_qs=(g['i_ld'], ms[1]), ksplit=self._dgrad_ksplit(g, use_rect))
+        p8_dgrad = bb.planes16 and any(g.get('p8') for g in bb.g16)
+        bb.i_dgrad = len(self._ops)               # (op indices the data-parallel order is cut at, see _schedule_backward)
+        self.gemm_op(p0, ctype=bb.bct if bb.g16 else None, tag=self.TAG_D3_DGRAD, flops=fl,
+                     tile=28 if p8_dgrad else 20 if use_rect else 0)
+        bb.i_late0 = len(self._ops)
+        self._ops.extend(bb.late_ops)
+        bb.i_late1 = len(self._ops)
+        if bb.n_planes > 1:
+            self.op(L.OP_DACT, refs=(d_u, bb.u, bb.amax_u if bb.amax_u is not None else self.NONE, d_up),
+                    ints=(M, 8 * C, 8 * C, L.DACT_RELU, bb.n_planes - 1, M * 8 * C, bb.rows16))
+        else:
+            self.op(L.OP_DACT, refs=(d_u, bb.u, bb.amax_u if bb.amax_u is not None else self.NONE),
+                    ints=(M, 8 * C, 8 * C, L.DACT_RELU))
+
+    def _bwd_w2_wgrad(self, bb):
+        """dW2 = d_tiles^T u.  16-bit bands first (one launch; every dW2 row they cover is written once, without
+        reading it), then the groups on the fp32-operand path accumulate; all on the side stream, in order."""
+        C, ms, sw, bands, u = self.C, self.max_shape, bb.sw, bb.bands, bb.u
+        W2, b2 = 'decoder.conv.2.weight', 'decoder.conv.2.bias'
+        if bands:
+            covered = all(b_['o_max'] == ms[0] for b_ in bands) and sum(b_['bw'] for b_ in bands) == ms[1]
+            if covered:
+                self.grad_no_memset.append(W2)      # every row of dW2 is written by the band problems
             p0 = len(self._probs)
             fl = 0.0
-            use_rect = bool(g16) and all(g['op16'] for g in self.gemm_groups if g['rows'] >= 512) and \
-                any(g['op16'] and g['rows'] >= 512 for g in self.gemm_groups) and \
-                os.environ.get('GHN3_DGRAD_RECT', '1') != '0'
-            def splits(g):
-                """K splits of a group's dgrad: until the launch offers ~512 tiles of 128 x 128 (two workgroups per CU;
-                measured best among 512 .. 3072: more splits only add traffic and tile-count quantisation); families with
-                >= 512 rows run on 256 x 128 three-stage tiles (tile code 20, one workgroup per CU) and are split to ~1.75
-                workgroups per CU (measured plateau 5 <= ks <= 8 for 768 rows: 1.1-1.2 ms against 1.45-1.55 ms)."""
-                tiles = ((g['rows'] + 127) // 128) * ((8 * C + 127) // 128)
-                tgt = 512 if g['op16'] else 2048       # (the fp32-operand kernel likes ~2048 tiles: 8.2 vs 9.8 ms)
-                ks = int(max(2, min(64, (tgt + tiles - 1) // tiles, g['cols'] // 1024)))
-                if g['op16'] and g['rows'] >= 512 and use_rect:
-                    t20 = ((g['rows'] + 255) // 256) * ((8 * C + 127) // 128)
-                    ks = int(max(2, min(16, round(448.0 / t20), g['cols'] // 1024)))
-                return ks
-
-            n_planes, rows16 = 1, 0
-            if planes32:
-                n_planes = int(max(1, min(8, max(g['o'] for g in self.gemm_groups))))
-                rows16 = M
-                d_up = self.wsf('d_u_parts', max(n_planes - 1, 1) * M * 8 * C)
-            if planes:
-                # every 16-bit group writes the same number of planes (its own chunk count <= 8, K = 0 problems -- zeros
-                # -- for the rest), so that one reduction pass serves all rows
-                # GHN3_DGRAD_PIN (default on): eight K chunks per family, chunk j on XCD j -- the chunk's slices of d_tiles and
-                # of W2^T are then fetched by one L2 instead of by all eight (4.1 GB of fetches per step without it)
-                pin = os.environ.get('GHN3_DGRAD_PIN', '1') != '0'
-                for g in g16:
-                    g['nc'] = int(max(1, min(8, g['o']))) if pin else int(max(1, min(8, splits(g), g['o'])))
-                nc_max = max(g['nc'] for g in g16)
-                # Sub-chunks (round 3).  With one K chunk per XCD a family of two or three row tiles is 24 .. 36 output tiles on
-                # the XCD's 32 CUs: a quarter of the CUs idles, or a second round starts for a handful of tiles.  Each chunk is
-                # therefore cut again into parts `sub` (e.g. 3/4 + 1/4: the eight CUs the long parts leave free take three
-                # quarter parts each); every part writes its own partial plane.  The split is chosen by simulating the
-                # longest-first dispatch of one XCD's tiles (a plane costs ~7 us of extra traffic).
-                sub = self._dgrad_sub_split(g16, 8 * C) if (pin and nc_max == 8 and self.use_p8) else (1,)
-                forced = os.environ.get('GHN3_DGRAD_SUB')
-                if forced:
-                    sub = tuple(int(v) for v in forced.split(','))
-                self.dgrad_sub = sub
-                n_planes = nc_max * len(sub)
-                rows16 = sum(g['rows'] for g in g16)
-                assert all(g['row0'] < rows16 for g in g16), 'op16 groups first'
-                d_up = self.wsf('d_u_parts', max(n_planes - 1, 1) * M * 8 * C)
-            for g in self.gemm_groups:
-                fl += sum(2.0 * sb['rows'] * sb['cols'] * 8 * C for sb in g['subs'])
-                if planes and g['op16']:
-                    # chunk j covers the W2 rows o' in [j * oc, (j + 1) * oc): k = o' * i + i' is contiguous in the copy
-                    # of d_tiles and a multiple of the k-map period i, so A and B just start further in
-                    # (the kernel consumes whole 64-wide k tiles: a chunk is a multiple of 64 so that the next chunk's
-                    # data is never read as padding)
-                    unit = 64 // math.gcd(g['i_ld'], 64)
-                    sub = self.dgrad_sub
-                    # chunk boundaries in W2 rows o' (multiples of `unit`: every part is whole 64-wide k tiles).  A family's
-                    # narrow members only reach the first chunks, so equal chunks would give the first XCDs more work than
-                    # the last: the boundaries equalise the WORK (row tiles alive at o' x their cost) instead of the length.
-                    if g['p8'] and g['nc'] == 8 and os.environ.get('GHN3_DGRAD_EQ', '1') != '0':
-                        dens = np.zeros(g['o'])
-                        for (m0_, mi_, ext_) in g['mtiles']:
-                            dens[:min(g['o'], int(ext_) // g['i_ld'])] += self.p8_cost(mi_)
-                        cw = np.concatenate([[0.0], np.cumsum(dens)])
-                        bounds = [0]
-                        for j in range(1, g['nc']):
-                            b = int(np.searchsorted(cw, cw[-1] * j / g['nc']))
-                            bounds.append(min(g['o'], max(bounds[-1], round_up(b, unit))))
-                        bounds.append(round_up(g['o'], unit))
-                    else:
-                        oc = round_up((g['o'] + g['nc'] - 1) // g['nc'], unit)
-                        bounds = [min(j * oc, round_up(g['o'], unit)) for j in range(g['nc'])] + [round_up(g['o'], unit)]
-                    for pl in range(n_planes):
-                        j, sidx = pl // len(sub), pl % len(sub)
-                        if j < g['nc']:
-                            lo_, hi_ = bounds[j], bounds[j + 1]
-                            cuts = [lo_ + min(hi_ - lo_, round_up(int(round((hi_ - lo_) * float(v) / sum(sub))), unit))
-                                    for v in np.concatenate([[0], np.cumsum(sub)])]
-                            cuts[-1] = hi_
-                            o0, o1 = cuts[sidx], max(cuts[sidx], cuts[sidx + 1])
-                        else:
-                            o0 = o1 = round_up(g['o'], unit)
-                        k0 = o0 * g['i_ld']
-                        kc = max(0, min(g['cols'] - k0, (o1 - o0) * g['i_ld']))
-                        dst = (d_u[0], d_u[1] + 4 * g['row0'] * 8 * C) if pl == 0 else \
-                            (d_up[0], d_up[1] + 4 * ((pl - 1) * M + g['row0']) * 8 * C)
-                        lim = None
-                        if g['ragged'] or kc < g['cols']:
-                            lim = self.idx(np.clip(g['lim128'] - k0, 0, kc).astype(np.int32))
-                        mt = None
-                        if g['p8']:
-                            mt = g['mtiles'].copy()
-                            mt[:, 2] = np.clip(mt[:, 2] - k0, 0, kc)
-                            mt = (self.idx(mt), len(mt))
-                        self.gemm(self.href(g['dth'] + min(k0, g['cols'])),
-                                  self.sref(self.w2hT + min(o0, g['o']) * ms[1]), dst,
-                                  g['rows'], 8 * C, kc, g['dth_ld'], self.w2hT_ld, 8 * C, op16=True,
-                                  b_kmap=(g['i_ld'], ms[1]), lim=lim, lim_kind=2, alpha_amax=amax_t,
-                                  xcd=j if (pin and nc_max == 8) else None, mtiles=mt)
-                    continue
-                if planes32:
-                    # chunk j = W2 rows o' in [j oc, (j + 1) oc): a multiple of the row-map period i, so A and B just start
-                    # further in; chunks beyond a group's own o range are K = 0 problems (zeros)
-                    oc = round_up((g['o'] + n_planes - 1) // n_planes, 4)      # (k0 * 4 bytes stays 16-byte aligned)
-                    for j in range(n_planes):
-                        k0 = min(j * oc, round_up(g['o'], 4)) * g['i_ld']
-                        kc = max(0, min(g['cols'] - k0, oc * g['i_ld']))
-                        dst = (d_u[0], d_u[1] + 4 * g['row0'] * 8 * C) if j == 0 else \
-                            (d_up[0], d_up[1] + 4 * ((j - 1) * M + g['row0']) * 8 * C)
-                        self.gemm(self.wref('d_tiles', g['tile_off'] + k0), self.pref(W2, min(j * oc, round_up(g['o'], 4)) * ms[1] * 8 * C),
-                                  dst, g['rows'], 8 * C, kc, g['ld'], 8 * C, 8 * C, a_mode=L.MODE_ROW, b_mode=L.MODE_COL,
-                                  b_qs=(g['i_ld'], ms[1]))
-                    continue
-                if planes:
-                    # (groups outside the 16-bit pipeline have i <= 4: a short reduction, one pass into plane 0)
-                    self.gemm(self.wref('d_tiles', g['tile_off']), self.pref(W2),
-                              (d_u[0], d_u[1] + 4 * g['row0'] * 8 * C),
-                              g['rows'], 8 * C, g['cols'], g['ld'], 8 * C, 8 * C, a_mode=L.MODE_ROW, b_mode=L.MODE_COL,
-                              b_qs=(g['i_ld'], ms[1]))
-                    continue
-                ks = splits(g)
-                if g['op16']:
-                    # one problem per family; the K loop of a row tile stops at the largest extent of its rows
-                    self.gemm(self.href(g['dth']), self.sref(self.w2hT), (d_u[0], d_u[1] + 4 * g['row0'] * 8 * C),
-                              g['rows'], 8 * C, g['cols'], g['dth_ld'], self.w2hT_ld, 8 * C, ksplit=ks, op16=True,
-                              b_kmap=(g['i_ld'], ms[1]), lim=self.idx(g['lim128']) if g['ragged'] else None,
-                              lim_kind=2, alpha_amax=amax_t)
-                    continue
-                self.gemm(self.wref('d_tiles', g['tile_off']), self.pref(W2),
-                          (d_u[0], d_u[1] + 4 * g['row0'] * 8 * C),
-                          g['rows'], 8 * C, g['cols'], g['ld'], 8 * C, 8 * C, a_mode=L.MODE_ROW, b_mode=L.MODE_COL,
-                          b_qs=(g['i_ld'], ms[1]), ksplit=ks)
-            p8_dgrad = planes and any(g.get('p8') for g in g16)
-            self._i_dgrad = len(self._ops)               # (op indices the data-parallel order is cut at, see bwd_parts)
-            self.gemm_op(p0, ctype=bct if g16 else None, tag=self.TAG_D3_DGRAD, flops=fl,
-                         tile=28 if p8_dgrad else 20 if use_rect else 0)
-            self._i_late0 = len(self._ops)
-            self._ops.extend(late_ops)
-            self._i_late1 = len(self._ops)
-            if (planes or planes32) and n_planes > 1:
-                self.op(L.OP_DACT, refs=(d_u, u, amax_u if amax_u is not None else self.NONE, d_up),
-                        ints=(M, 8 * C, 8 * C, L.DACT_RELU, n_planes - 1, M * 8 * C, rows16))
-            else:
-                self.op(L.OP_DACT, refs=(d_u, u, amax_u if amax_u is not None else self.NONE),
-                        ints=(M, 8 * C, 8 * C, L.DACT_RELU))
-            # dW2 = d_tiles^T u.  16-bit bands first (one launch; every dW2 row they cover is written once, without
-            # reading it), then the groups on the fp32-operand path accumulate; all on the side stream, in order.
-            bands = getattr(self, 'wgrad_bands', []) if g16 else []
-            if bands:
-                covered = all(b_['o_max'] == ms[0] for b_ in bands) and sum(b_['bw'] for b_ in bands) == ms[1]
-                if covered:
-                    self.grad_no_memset.append(W2)      # every row of dW2 is written by the band problems
-                p0 = len(self._probs)
-                fl = 0.0
-                # Sum of squares of dW2 from the weight-gradient kernel itself (GHN3_GEMM_SUMSQ: one slot per output tile and
-                # wave), when the band problems are its only writers: FusedAdamW's clip_grad_norm_ then skips the 1.8 GB.
-                # The table covers every tile id of the launch (the runtime numbers a problem's tiles XCD-blocked: at most
-                # tiles + 8 (tiles_m + tiles_n + 1) ids per problem); ids without a tile keep the zero of the memset.
-                wg_tile = int(os.environ.get('GHN3_WGRAD_TILE', '29'))
-                wg_tn = 128 if wg_tile == 30 else 256     # (column width of the kernel's tiles: its tile ids index the slots)
-                sq_on = covered and all(g_['op16'] for g_ in self.gemm_groups) and wg_tile in (29, 30) and \
-                    os.environ.get('GHN3_WGRAD_SUMSQ', '1') != '0'
-                sq_ids = 0
-                n_before = len(self._ops)               # (the zero-fill of the sum-of-squares slots belongs to the weight gradient:
-                if sq_on:                               #  it moves with it when the order of the backward changes)
-                    for b_ in bands:
-                        thr = sorted({m_['o'] for m_ in b_['members']}, reverse=True)
-                        for j, o_hi in enumerate(thr):
-                            o_lo = thr[j + 1] if j + 1 < len(thr) else 0
-                            tm, tn = ((o_hi - o_lo) * b_['bw'] + 255) // 256, (8 * C + wg_tn - 1) // wg_tn
-                            sq_ids += tm * tn + 8 * (tm + tn + 1)
-                    sq_ref = self.wsf('dw2_sq', 8 * sq_ids)
-                    self.op(L.OP_MEMSET0, refs=(sq_ref,), ints=(4 * 8 * sq_ids,))
-                    self.grad_sumsq = dict(name=W2, ws_off=sq_ref[1], count=8 * sq_ids)
+            # Sum of squares of dW2 from the weight-gradient kernel itself (GHN3_GEMM_SUMSQ: one slot per output tile and
+            # wave), when the band problems are its only writers: FusedAdamW's clip_grad_norm_ then skips the 1.8 GB.
+            # The table covers every tile id of the launch (the runtime numbers a problem's tiles XCD-blocked: at most
+            # tiles + 8 (tiles_m + tiles_n + 1) ids per problem); ids without a tile keep the zero of the memset.
+            wg_tn = 128 if sw.wgrad_tile == 30 else 256     # (column width of the kernel's tiles: its tile ids index the slots)
+            sq_on = covered and all(g_['op16'] for g_ in self.gemm_groups) and sw.wgrad_tile in (29, 30) and sw.wgrad_sumsq
+            sq_ids, sq_ref = 0, None
+            n_before = len(self._ops)               # (the zero-fill of the sum-of-squares slots belongs to the weight gradient:
+            if sq_on:                               #  it moves with it when the order of the backward changes)
                 for b_ in bands:
-                    mem = b_['members']
-                    fl += sum(2.0 * m_['rows'] * m_['o'] * b_['bw'] * 8 * C for m_ in mem)   # algorithmic
-                    thr = sorted({m_['o'] for m_ in mem}, reverse=True)
+                    thr = sorted({m_['o'] for m_ in b_['members']}, reverse=True)
                     for j, o_hi in enumerate(thr):
                         o_lo = thr[j + 1] if j + 1 < len(thr) else 0
-                        kpre = sum(round_up(m_['rows'], 8) for m_ in mem if m_['o'] >= o_hi)     # a prefix (sorted by o)
-                        # (columns of the last k tile beyond kpre belong to rows with o_r <= o_lo: zeros in these W2 rows)
-                        self.gemm(self.href(b_['dthT'] + o_lo * b_['bw'] * b_['ktot']), self.href(b_['uhT']),
-                                  self.gref(W2, (o_lo * ms[1] + b_['i_lo']) * 8 * C), (o_hi - o_lo) * b_['bw'], 8 * C,
-                                  kpre, b_['ktot'], b_['ktot'], 8 * C, c_qs=(b_['bw'], ms[1]), op16=True,
-                                  alpha_amax=amax_t, sumsq=sq_ref if sq_on else None)
-                # tile 25 = the persistent output-heavy kernel (K = the family's rows: 12 k-tiles per 256 KB of output):
-                # 1.44 -> 1.10 ms.  On the side stream it runs as 224 workgroups (GHN3_WGRAD_CAP), leaving 4 CUs per XCD
-                # to the dependent chain on the main stream, which the faster kernel otherwise slows down by what it
-                # gained (step 8.51 ms with the old kernel, 8.56 with tile 25 on every CU, 8.46 at 224, 8.38 at 192 --
-                # but there the weight gradient is back at 1.49 ms).
-                # Where the W2 weight gradient runs (round 5: the fastest step is the default; this paragraph is the model of
-                # GHN3_WGRAD_ORDER=late -- for the default order 'first', 128 workgroups, see the end of __init__).  The persistent kernel takes
-                # 128 KB of LDS and 256 VGPRs on every CU it sits on -- nothing co-resides with it -- so beside it the
-                # Graphormer backward chain only gets the CUs the launch leaves free, and it runs ~1.75x slower there
-                # whatever their number (memory-system contention: 1.12 -> 1.9-2.0 ms on 128 / 96 / 64 free CUs,
-                # profiles/r05a_ab_wgrad_schedule.txt).  With W = the kernel's full-chip time and Ch = the chain's own time
-                # the step pays max(W * 256 / c, 1.75 Ch) with c workgroups on the side stream against W + Ch serial: side
-                # stream when W >= 0.75 Ch, with c = 256 W / (1.75 Ch) (ghn3xlm16, one 256-node graph: 136; measured
-                # 5.82-5.84 ms at 128, 5.84-5.92 at 160, 5.93 at 192, 6.01-6.03 serial; two graphs: 160 -> 9.59-9.67 ms
-                # against 9.86-10.09 serial; four graphs: 184 -> 15.8-16.0 against 16.2-16.3).  The kernel's own rate
-                # (`roofline.frac`) is measured in a serialised pass (profile mode 3), where the cap is dropped.
-                # GHN3_WGRAD_MAIN=1 / 0 and GHN3_WGRAD_CAP override.
-                self.wgrad_cap = self._wgrad_schedule(fl, B * N)
-                wg_main = self.wgrad_cap == 0
-                self.gemm_op(p0, ctype=bct, tag=self.TAG_D3_WGRAD, side=not wg_main, flops=fl,
-                             tile=wg_tile,
-                             grid_cap=(self.wgrad_cap | (int(os.environ.get('GHN3_WGRAD_TPW', '0')) << 16))
-                             if (self.SIDE and not wg_main) else 0)
-                self.wgrad_op_range = (n_before, len(self._ops))
-            fam_list = bands
-            for gi, g in enumerate(self.gemm_groups):
-                if g['op16']:
-                    continue
-                # (fp32-operand path: one launch per group; without 16-bit families the first full-size group
-                # writes every dW2 row and needs neither the memset nor the accumulate)
-                full = (not fam_list and gi == 0 and g['o'] == ms[0] and g['i_ld'] == ms[1] and g['kind'] == 'conv')
-                if full:
-                    self.grad_no_memset.append(W2)
-                p0 = self.gemm(self.wref('d_tiles', g['tile_off']), (u[0], u[1] + 4 * g['row0'] * 8 * C),
-                               self.gref(W2), g['cols'], 8 * C, g['rows'], g['ld'], 8 * C, 8 * C,
-                               a_mode=L.MODE_COL, b_mode=L.MODE_COL, c_qs=(g['i_ld'], ms[1]),
-                               accum=not full, dbias=self.gref(b2))
-                # short reduction (K = rows of the group): 64x64 tiles beat 128x128 here (tools/diag/gemm_bench.py)
-                self.gemm_op(p0, tile=64 if g['rows'] <= 1024 else 0, ctype=bct if g16 else None,
-                             tag=self.TAG_D3_WGRAD, side=True)
-            self.bwd_cut_w2 = len(self._ops)             # every op that writes dW2 has been issued
-            if self.wgrad_op_range is not None:
-                # (the late order moves ALL of them: the fp32-operand groups accumulate into what the band problems write)
-                self.wgrad_op_range = (self.wgrad_op_range[0], self.bwd_cut_w2)
-            # D2 backward
-            if g16 and hasattr(self, 'w0hT'):
-                # 16-bit operands: d_u (straight for the dgrad on the chain; transposed + column sums = bias
-                # gradient for the wgrad beside it) and t^T
-                Mp = round_up(M, 64)
-                duh = self.ws16('duh', M * 8 * C)
-                duhT = self.ws16('duhT', 8 * C * Mp)
-                thT = self.ws16('thT', 4 * C * Mp)
-                self.cast16((self.xbuf(self.X_WS), 0),
-                            [dict(src_off=d_u[1] // 4, rows=M, cols=8 * C, ld_src=8 * C, straight=(duh, 8 * C, bct),
-                                  scaled=scaled)], amax=amax_u)
-                self.cast16((self.xbuf(self.X_WS), 0),
-                            [dict(src_off=d_u[1] // 4, rows=M, cols=8 * C, ld_src=8 * C, transposed=(duhT, Mp, bct),
-                                  scaled=scaled, colsum_parts=0),
-                             dict(src_off=t[1] // 4, rows=M, cols=4 * C, ld_src=4 * C, transposed=(thT, Mp, bct))],
-                            dbias=self.wsf('b0_parts', ((M + 63) // 64) * 8 * C), flags=self.SIDE, amax=amax_u)
-                set0 = np.zeros(1, dtype=L.ROWSET_DT)
-                set0[0] = (0, (M + 63) // 64, 1, 8 * C, 8 * C, 0, 0)
-                self.op(L.OP_ROWSET_COLSUM, refs=(self.gref(b0), self.wref('b0_parts'), self.idx(set0)),
-                        ints=(1, 1, 8 * C), flags=self.SIDE)
-                p0 = self.gemm(self.href(duhT), self.href(thT), self.gref(W0), 8 * C, 4 * C, Mp, Mp, Mp, 4 * C,
-                               accum=True, op16=True, alpha_amax=amax_u)
-                self.gemm_op(p0, ctype=bct, tag=self.TAG_D2_BWD, side=True, flops=2.0 * 8 * C * 4 * C * M)
-                # conv.0 dgrad: [M x 4C] output with K = 8C is 144 tiles of 128 x 128 at ghn3xlm16 -- half the CUs, 48 k-tiles
-                # each (154 us, 87 TF).  K chunks as separate problems writing partial planes (summed + masked by a DACT
-                # pass in plane order: deterministic) fill the chip.
-                d2_tile = int(os.environ.get('GHN3_D2_DGRAD_TILE', '0'))
-                ks = int(os.environ.get('GHN3_D2_DGRAD_KS', '0')) or \
-                    max(1, min(4, 320 // max(1, ((M + 127) // 128) * ((4 * C + 127) // 128))))
-                while ks > 1 and (8 * C) % (64 * ks):
-                    ks -= 1
-                if ks > 1:
-                    kc = 8 * C // ks
-                    planes = self.wsf('d_t_parts', (ks - 1) * M * 4 * C)
-                    p0 = len(self._probs)
-                    for j in range(ks):
-                        dst = d_t if j == 0 else (planes[0], planes[1] + 4 * (j - 1) * M * 4 * C)
-                        self.gemm(self.href(duh + j * kc), self.sref(self.w0hT + j * kc), dst, M, 4 * C, kc, 8 * C, 8 * C,
-                                  4 * C, op16=True, alpha_amax=amax_u)
-                    self.gemm_op(p0, ctype=bct, tag=self.TAG_D2_BWD, flops=2.0 * M * 4 * C * 8 * C, tile=d2_tile)
-                    self.op(L.OP_DACT, refs=(d_t, t, self.NONE, planes),
-                            ints=(M, 4 * C, 4 * C, L.DACT_RELU, ks - 1, M * 4 * C, M))
-                else:
-                    p0 = self.gemm(self.href(duh), self.sref(self.w0hT), d_t, M, 4 * C, 8 * C, 8 * C, 8 * C, 4 * C,
-                                   dact=L.DACT_RELU, aux_in=t, op16=True, alpha_amax=amax_u)
-                    self.gemm_op(p0, ctype=bct, tag=self.TAG_D2_BWD)
-            else:
-                p0 = self.gemm(d_u, t, self.gref(W0), 8 * C, 4 * C, M, 8 * C, 4 * C, 4 * C, a_mode=L.MODE_COL,
-                               b_mode=L.MODE_COL, accum=True, dbias=self.gref(b0))
-                self.gemm_op(p0, tag=self.TAG_D2_BWD, side=True)
-                p0 = self.gemm(d_u, self.pref(W0), d_t, M, 4 * C, 8 * C, 8 * C, 4 * C, 4 * C, a_mode=L.MODE_ROW,
-                               b_mode=L.MODE_COL, dact=L.DACT_RELU, aux_in=t)
-                self.gemm_op(p0, tag=self.TAG_D2_BWD)
-            # D1 backward (per used position)
+                        tm, tn = ((o_hi - o_lo) * b_['bw'] + 255) // 256, (8 * C + wg_tn - 1) // wg_tn
+                        sq_ids += tm * tn + 8 * (tm + tn + 1)
+                sq_ref = self.wsf('dw2_sq', 8 * sq_ids)
+                self.op(L.OP_MEMSET0, refs=(sq_ref,), ints=(4 * 8 * sq_ids,))
+                self.grad_sumsq = dict(name=W2, ws_off=sq_ref[1], count=8 * sq_ids)
+            for b_ in bands:
+                mem = b_['members']
+                fl += sum(2.0 * m_['rows'] * m_['o'] * b_['bw'] * 8 * C for m_ in mem)   # algorithmic
+                thr = sorted({m_['o'] for m_ in mem}, reverse=True)
+                for j, o_hi in enumerate(thr):
+                    o_lo = thr[j + 1] if j + 1 < len(thr) else 0
+                    kpre = sum(round_up(m_['rows'], 8) for m_ in mem if m_['o'] >= o_hi)     # a prefix (sorted by o)
+                    # (columns of the last k tile beyond kpre belong to rows with o_r <= o_lo: zeros in these W2 rows)
+                    self.gemm(self.href(b_['dthT'] + o_lo * b_['bw'] * b_['ktot']), self.href(b_['uhT']),
+                              self.gref(W2, (o_lo * ms[1] + b_['i_lo']) * 8 * C), (o_hi - o_lo) * b_['bw'], 8 * C,
+                              kpre, b_['ktot'], b_['ktot'], 8 * C, c_qs=(b_['bw'], ms[1]), op16=True,
+                              alpha_amax=bb.amax_t, sumsq=sq_ref)
+            # tile 25 = the persistent output-heavy kernel (K = the family's rows: 12 k-tiles per 256 KB of output):
+            # 1.44 -> 1.10 ms.  On the side stream it runs as 224 workgroups (GHN3_WGRAD_CAP), leaving 4 CUs per XCD
+            # to the dependent chain on the main stream, which the faster kernel otherwise slows down by what it
+            # gained (step 8.51 ms with the old kernel, 8.56 with tile 25 on every CU, 8.46 at 224, 8.38 at 192 --
+            # but there the weight gradient is back at 1.49 ms).
+            # Where the W2 weight gradient runs (round 5: the fastest step is the default; this paragraph is the model of
+            # GHN3_WGRAD_ORDER=late -- for the default order 'first', 128 workgroups, see _single_process_order).  The persistent kernel takes
+            # 128 KB of LDS and 256 VGPRs on every CU it sits on -- nothing co-resides with it -- so beside it the
+            # Graphormer backward chain only gets the CUs the launch leaves free, and it runs ~1.75x slower there
+            # whatever their number (memory-system contention: 1.12 -> 1.9-2.0 ms on 128 / 96 / 64 free CUs,
+            # profiles/r05a_ab_wgrad_schedule.txt).  With W = the kernel's full-chip time and Ch = the chain's own time
+            # the step pays max(W * 256 / c, 1.75 Ch) with c workgroups on the side stream against W + Ch serial: side
+            # stream when W >= 0.75 Ch, with c = 256 W / (1.75 Ch) (ghn3xlm16, one 256-node graph: 136; measured
+            # 5.82-5.84 ms at 128, 5.84-5.92 at 160, 5.93 at 192, 6.01-6.03 serial; two graphs: 160 -> 9.59-9.67 ms
+            # against 9.86-10.09 serial; four graphs: 184 -> 15.8-16.0 against 16.2-16.3).  The kernel's own rate
+            # (`roofline.frac`) is measured in a serialised pass (profile mode 3), where the cap is dropped.
+            # GHN3_WGRAD_MAIN=1 / 0 and GHN3_WGRAD_CAP override.
+            self.wgrad_cap = self._wgrad_schedule(sw, fl, self.B * self.N)
+            wg_main = self.wgrad_cap == 0
+            self.gemm_op(p0, ctype=bb.bct, tag=self.TAG_D3_WGRAD, side=not wg_main, flops=fl, tile=sw.wgrad_tile,
+                         grid_cap=(self.wgrad_cap | (sw.wgrad_tpw << 16)) if (self.SIDE and not wg_main) else 0)
+            self.wgrad_op_range = (n_before, len(self._ops))
+        for gi, g in enumerate(self.gemm_groups):
+            if g['op16']:
+                continue
+            # (fp32-operand path: one launch per group; without 16-bit families the first full-size group
+            # writes every dW2 row and needs neither the memset nor the accumulate)
+            full = (not bands and gi == 0 and g['o'] == ms[0] and g['i_ld'] == ms[1] and g['kind'] == 'conv')
+            if full:
+                self.grad_no_memset.append(W2)
+            p0 = self.gemm(self.wref('d_tiles', g['tile_off']), (u[0], u[1] + 4 * g['row0'] * 8 * C),
+                           self.gref(W2), g['cols'], 8 * C, g['rows'], g['ld'], 8 * C, 8 * C,
+                           a_mode=L.MODE_COL, b_mode=L.MODE_COL, c_qs=(g['i_ld'], ms[1]),
+                           accum=not full, dbias=self.gref(b2))
+            # short reduction (K = rows of the group): 64x64 tiles beat 128x128 here (tools/diag/gemm_bench.py)
+            self.gemm_op(p0, tile=64 if g['rows'] <= 1024 else 0, ctype=bb.bct if bb.g16 else None,
+                         tag=self.TAG_D3_WGRAD, side=True)
+        self.bwd_cut_w2 = len(self._ops)             # every op that writes dW2 has been issued
+        if self.wgrad_op_range is not None:
+            # (the late order moves ALL of them: the fp32-operand groups accumulate into what the band problems write)
+            self.wgrad_op_range = (self.wgrad_op_range[0], self.bwd_cut_w2)
+
+    def _bwd_conv0(self, bb):
+        """decoder.conv.0 backward (D2): weight gradient on the side stream, dgrad (+ ReLU mask of t) on the chain."""
+        C, M, sw, bct = self.C, self.M, bb.sw, bb.bct
+        t, d_t, d_u, amax_u = bb.t, bb.d_t, bb.d_u, bb.amax_u
+        W0, b0 = 'decoder.conv.0.weight', 'decoder.conv.0.bias'
+        if not (bb.g16 and self.w0hT is not None):
+            p0 = self.gemm(d_u, t, self.gref(W0), 8 * C, 4 * C, M, 8 * C, 4 * C, 4 * C, a_mode=L.MODE_COL,
+                           b_mode=L.MODE_COL, accum=True, dbias=self.gref(b0))
+            self.gemm_op(p0, tag=self.TAG_D2_BWD, side=True)
+            p0 = self.gemm(d_u, self.pref(W0), d_t, M, 4 * C, 8 * C, 8 * C, 4 * C, 4 * C, a_mode=L.MODE_ROW,
+                           b_mode=L.MODE_COL, dact=L.DACT_RELU, aux_in=t)
+            self.gemm_op(p0, tag=self.TAG_D2_BWD)
+            return
+        # 16-bit operands: d_u (straight for the dgrad on the chain; transposed + column sums = bias
+        # gradient for the wgrad beside it) and t^T
+        Mp = round_up(M, 64)
+        duh = self.ws16('duh', M * 8 * C)
+        duhT = self.ws16('duhT', 8 * C * Mp)
+        thT = self.ws16('thT', 4 * C * Mp)
+        self.cast16((self.xbuf(self.X_WS), 0),
+                    [dict(src_off=d_u[1] // 4, rows=M, cols=8 * C, ld_src=8 * C, straight=(duh, 8 * C, bct),
+                          scaled=bb.scaled)], amax=amax_u)
+        self.cast16((self.xbuf(self.X_WS), 0),
+                    [dict(src_off=d_u[1] // 4, rows=M, cols=8 * C, ld_src=8 * C, transposed=(duhT, Mp, bct),
+                          scaled=bb.scaled, colsum_parts=0),
+                     dict(src_off=t[1] // 4, rows=M, cols=4 * C, ld_src=4 * C, transposed=(thT, Mp, bct))],
+                    dbias=self.wsf('b0_parts', ((M + 63) // 64) * 8 * C), flags=self.SIDE, amax=amax_u)
+        set0 = np.zeros(1, dtype=L.ROWSET_DT)
+        set0[0] = (0, (M + 63) // 64, 1, 8 * C, 8 * C, 0, 0)
+        self.op(L.OP_ROWSET_COLSUM, refs=(self.gref(b0), self.wref('b0_parts'), self.idx(set0)),
+                ints=(1, 1, 8 * C), flags=self.SIDE)
+        p0 = self.gemm(self.href(duhT), self.href(thT), self.gref(W0), 8 * C, 4 * C, Mp, Mp, Mp, 4 * C,
+                       accum=True, op16=True, alpha_amax=amax_u)
+        self.gemm_op(p0, ctype=bct, tag=self.TAG_D2_BWD, side=True, flops=2.0 * 8 * C * 4 * C * M)
+        # conv.0 dgrad: [M x 4C] output with K = 8C is 144 tiles of 128 x 128 at ghn3xlm16 -- half the CUs, 48 k-tiles
+        # each (154 us, 87 TF).  K chunks as separate problems writing partial planes (summed + masked by a DACT
+        # pass in plane order: deterministic) fill the chip.
+        ks = sw.d2_dgrad_ks or max(1, min(4, 320 // max(1, ((M + 127) // 128) * ((4 * C + 127) // 128))))
+        while ks > 1 and (8 * C) % (64 * ks):
+            ks -= 1
+        if ks > 1:
+            kc = 8 * C // ks
+            d_t_parts = self.wsf('d_t_parts', (ks - 1) * M * 4 * C)
             p0 = len(self._probs)
-            for (p, cnt, r_rows, r_src) in self.d1:
-                self.gemm(d_t, self.pref(Wfc, p * C), d_rows, cnt, C, 4 * C, 4 * C, S2 * C, C, a_mode=L.MODE_ROW,
-                          b_mode=L.MODE_COL, a_gather=r_rows, c_gather=r_rows)
-            self.gemm_op(p0, tag=self.TAG_D1_BWD, ctype=self.d1_bwd_ctype, tile=int(os.environ.get('GHN3_D1_DGRAD_TILE', '0')))
-            p0 = len(self._probs)
-            for (p, cnt, r_rows, r_src) in self.d1:
-                self.gemm(d_t, xe, self.gref(Wfc, p * C), 4 * C, C, cnt, 4 * C, C, S2 * C, a_mode=L.MODE_COL,
-                          b_mode=L.MODE_COL, a_gather=r_rows, b_gather=r_src, accum=True,
-                          dbias=self.gref(bfc, p), dbias_stride=S2)
-            self.gemm_op(p0, tag=self.TAG_D1_BWD, side=True, ctype=self.d1_bwd_ctype)
-        if not early_1d:
-            decoder_1d_bwd(False)
-        # Everything above produces the decoder gradients (93 % of the gradient bytes at XL); a data-parallel caller
-        # may run the program in two parts (bwd_ops[:bwd_split] + DETACH, then the rest) and start their all-reduce here.
-        self.bwd_split = len(self._ops)
-        # ---- d_xe[row] = sum of the decoder rows that read it (deterministic gather-sum) -----------------
-        all_src = np.concatenate([self.row_src, self.oned_src]) if (M + n1) else np.zeros(0, dtype=np.int32)
+            for j in range(ks):
+                dst = d_t if j == 0 else (d_t_parts[0], d_t_parts[1] + 4 * (j - 1) * M * 4 * C)
+                self.gemm(self.href(duh + j * kc), self.sref(self.w0hT + j * kc), dst, M, 4 * C, kc, 8 * C, 8 * C,
+                          4 * C, op16=True, alpha_amax=amax_u)
+            self.gemm_op(p0, ctype=bct, tag=self.TAG_D2_BWD, flops=2.0 * M * 4 * C * 8 * C, tile=sw.d2_dgrad_tile)
+            self.op(L.OP_DACT, refs=(d_t, t, self.NONE, d_t_parts),
+                    ints=(M, 4 * C, 4 * C, L.DACT_RELU, ks - 1, M * 4 * C, M))
+        else:
+            p0 = self.gemm(self.href(duh), self.sref(self.w0hT), d_t, M, 4 * C, 8 * C, 8 * C, 8 * C, 4 * C,
+                           dact=L.DACT_RELU, aux_in=t, op16=True, alpha_amax=amax_u)
+            self.gemm_op(p0, ctype=bct, tag=self.TAG_D2_BWD)
+
+    def _bwd_fc(self, bb):
+        """decoder.fc backward (D1), one problem per used position of the decoder grid: dgrad into the node rows on the chain,
+        weight gradient on the side stream."""
+        C, S2, d_t, xe = self.C, self.S * self.S, bb.d_t, self.r_xe
+        Wfc, bfc = 'decoder.fc.0.weight', 'decoder.fc.0.bias'
+        p0 = len(self._probs)
+        for (p, cnt, r_rows, r_src) in self.d1:
+            self.gemm(d_t, self.pref(Wfc, p * C), bb.d_rows, cnt, C, 4 * C, 4 * C, S2 * C, C, a_mode=L.MODE_ROW,
+                      b_mode=L.MODE_COL, a_gather=r_rows, c_gather=r_rows)
+        self.gemm_op(p0, tag=self.TAG_D1_BWD, ctype=self.d1_bwd_ctype, tile=bb.sw.d1_dgrad_tile)
+        p0 = len(self._probs)
+        for (p, cnt, r_rows, r_src) in self.d1:
+            self.gemm(d_t, xe, self.gref(Wfc, p * C), 4 * C, C, cnt, 4 * C, C, S2 * C, a_mode=L.MODE_COL,
+                      b_mode=L.MODE_COL, a_gather=r_rows, b_gather=r_src, accum=True,
+                      dbias=self.gref(bfc, p), dbias_stride=S2)
+        self.gemm_op(p0, tag=self.TAG_D1_BWD, side=True, ctype=self.d1_bwd_ctype)
+
+    def _bwd_node_rows(self, bb, early_1d):
+        """d_xe[row] = sum of the decoder rows that read it (deterministic gather-sum).  Returns d_xe."""
+        C, rows = self.C, self.B * self.N
+        all_src = np.concatenate([self.row_src, self.oned_src]) if (self.M + self.n1) else np.zeros(0, dtype=np.int32)
         order = np.argsort(all_src, kind='stable').astype(np.int32)
         counts = np.bincount(all_src, minlength=rows)[:rows]
         seg_ptr = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
         d_xe = self.wsf('d_xe', rows * C)
         if early_1d:
             self.op(L.OP_JOIN, ints=(2, 0))              # wait for the mark only: the W2 weight gradient keeps running
-        self.op(L.OP_ROWSEG_SUM, refs=(d_xe, d_rows, self.idx(seg_ptr), self.idx(order)), ints=(rows, C, C, C, 0))
+        self.op(L.OP_ROWSEG_SUM, refs=(d_xe, bb.d_rows, self.idx(seg_ptr), self.idx(order)), ints=(rows, C, C, C, 0))
+        return d_xe
 
-        # ---- final LayerNorm ----------------------------------------------------------------------------
+    def _bwd_final_layernorm(self, bb, d_xe):
+        """Final LayerNorm backward, and the buffers all Graphormer layers share.  Returns the gradient of the last layer's output."""
+        C, B, H, N, V = self.C, self.B, self.H, self.N, self.V
+        rows = B * N
         dxa = self.wsf('dxa', rows * C)
-        do = self.wsf('do', rows * C)
+        bb.do = self.wsf('do', rows * C)
         # (the 64-bit fixed-point histogram of GHN3_OP_BIAS_HIST + its max |dBias| slot live right behind dBias: one zero-fill
         # for both, and the slot is ready when the last attention backward -- layer 0 -- reports the maximum of what it wrote)
         nb_ = round_up(4 * B * H * N * N, 16)
-        dBias = self.wsf('dBias', nb_ // 4 + 2 * V * V * H + 16)
-        hist = (dBias[0], dBias[1] + nb_)
-        hist_amax = (dBias[0], dBias[1] + nb_ + 8 * V * V * H)
-        self.op(L.OP_MEMSET0, refs=(dBias,), ints=(nb_ + 8 * V * V * H + 16,))
+        bb.dBias = self.wsf('dBias', nb_ // 4 + 2 * V * V * H + 16)
+        bb.hist = (bb.dBias[0], bb.dBias[1] + nb_)
+        bb.hist_amax = (bb.dBias[0], bb.dBias[1] + nb_ + 8 * V * V * H)
+        self.op(L.OP_MEMSET0, refs=(bb.dBias,), ints=(nb_ + 8 * V * V * H + 16,))
+        if not self.layernorm:
+            return d_xe
         xL = self.wref('x%d' % self.Lyr)
-        if self.layernorm:
-            self.op(L.OP_LAYERNORM_BWD, refs=(dxa, d_xe, xL, self.pref('ln.weight'), self.wref('mf'), self.wref('rf'),
-                                              self.NONE), ints=(rows, C))
-            self.op(L.OP_LN_PARAM_GRAD, refs=(self.gref('ln.weight'), self.gref('ln.bias'), d_xe, xL,
-                                              self.wref('mf'), self.wref('rf')), ints=(rows, C, 1), flags=self.SIDE)
-            g_cur = dxa
+        self.op(L.OP_LAYERNORM_BWD, refs=(dxa, d_xe, xL, self.pref('ln.weight'), self.wref('mf'), self.wref('rf'),
+                                          self.NONE), ints=(rows, C))
+        self.op(L.OP_LN_PARAM_GRAD, refs=(self.gref('ln.weight'), self.gref('ln.bias'), d_xe, xL,
+                                          self.wref('mf'), self.wref('rf')), ints=(rows, C, 1), flags=self.SIDE)
+        return dxa
+
+    def _layer_dgrad(self, A, wname, Cref, rows, N, K, plane=None, ln=None, **epi):
+        """One dgrad linear C = f(A) W (W [K][N]) of a Graphormer layer, on the program's route: the staged split-bf16 kernel
+        (f = the LayerNorm backward row prologue `ln`), the split-bf16 kernel, or exact fp32.  plane = name of a workspace
+        buffer: the linear may split K over workgroup sets, the extra parts going to planes that the LayerNorm backward
+        behind it sums.  Returns (planes ref or None, extra ints of that LayerNorm op)."""
+        if self.x3s:
+            self.x3s_linear(A, wname, True, Cref, rows, N, K, K, N, ln=ln, **epi)
+            return None, ()
+        assert ln is None
+        if self.x3:
+            np_, pl = self.x3_linear(A, wname, True, Cref, rows, N, K, K, N, split=plane is not None, planes=plane, **epi)
+            return pl, (np_, rows * N)
+        pl = None
+        if plane is not None and self.split_small(rows, N, K):
+            pl = self.wsf(plane, rows * N)
+            p0 = self.gemm_k2(A, self.pref(wname), Cref, pl, rows, N, K, K, N, N, L.MODE_COL, **epi)
         else:
-            g_cur = d_xe
-        # ---- Graphormer layers, reversed ----------------------------------------------------------------
-        bias = self.wref('bias')
-        pending_ln1 = None                  # staged route: (dy buffer, prologue refs) of the LayerNorm backward fused into the next GEMM
-        # Side-stream ops of `side_group` consecutive layers are issued together: every main -> side hand-off is an event
-        # record that stalls the main chain for 6-12 us, and the temporaries the side ops read are per layer anyway.
-        side_group = max(1, int(os.environ.get('GHN3_SIDE_GROUP', '4'))) if self.SIDE else 1
-        side_pending = []
-        layer_side = []
-        defer = bool(self.SIDE) and os.environ.get('GHN3_LAYER_WGRAD_DEFER', '1') != '0'
-        defer_group = int(os.environ.get('GHN3_LAYER_WGRAD_GROUP', '0'))     # 0: one launch behind the chain
-        side_done = 0
+            p0 = self.gemm(A, self.pref(wname), Cref, rows, N, K, K, N, N, a_mode=L.MODE_ROW, b_mode=L.MODE_COL, **epi)
+        self.gemm_op(p0)
+        return pl, ()
+
+    def _layernorm_bwd(self, dy, ln, plane, rows):
+        """LayerNorm backward as an op of its own: ln = [weight, x, mean, rstd, residual gradient added to the result, result]
+        (the refs of the staged kernels' row prologue), plane = what _layer_dgrad returned for the linear that wrote dy."""
+        w, x, mean, rstd, resid, out = ln
+        self.op(L.OP_LAYERNORM_BWD, refs=(out, dy, x, w, mean, rstd, resid, plane[0] or self.NONE),
+                ints=(rows, self.C) + plane[1])
+
+    def _bwd_layer(self, bb, l, g_cur, ln1_above):
+        """Backward of Graphormer layer l (autograd of graphormer.py:208-248) on the dependent chain: four dgrad linears, the
+        attention backward and the two LayerNorm backwards.  g_cur = gradient of the layer's output; ln1_above = on the staged
+        route, (dy, prologue refs) of the LayerNorm-1 backward of layer l + 1, which runs as the row prologue of this layer's
+        first linear (it writes g_cur).  Returns (gradient of the layer's input, the same pair for layer l - 1 or None, the
+        record of what the layer's side-stream work reads)."""
+        C, B, N, H = self.C, self.B, self.N, self.H
+        rows = B * N
+        pre, sfx = 'gnn.%d.' % l, '_%d' % l
+        x_in = self.wref('x%d' % l)
+        h1, qkv, Pm, o = self.wref('h1' + sfx), self.wref('qkv' + sfx), self.wref('P' + sfx), self.wref('o' + sfx)
+        xmid, h2, z, f = self.wref('xmid' + sfx), self.wref('h2' + sfx), self.wref('z' + sfx), self.wref('f' + sfx)
+        m1, r1, m2, r2 = self.wref('m1' + sfx), self.wref('r1' + sfx), self.wref('m2' + sfx), self.wref('r2' + sfx)
+        W3, W1f, Wo, Wq = pre + 'ff.net.3.weight', pre + 'ff.net.0.weight', pre + 'attn.to_out.0.weight', \
+            pre + 'attn.to_qkv.weight'
+        # The four dgrad GEMMs, the two LayerNorm backward passes and the attention backward form the dependent
+        # chain of the layer.  The four wgrad GEMMs (+ fused bias gradients, ONE grouped launch) and the two
+        # LayerNorm parameter gradients are off that chain: they run on the side stream, which is why every
+        # temporary they read (g_cur, dz, dhA, g_mid, dqkv, dhB) is a buffer of THIS layer -- the chain of the
+        # next layer may start while they are still being read.
+        lsfx = sfx if self.SIDE else ''
+        dz = self.wsf('dz' + lsfx, rows * 4 * C)
+        dhA, dhB = self.wsf('dhA' + lsfx, rows * C), self.wsf('dhB' + lsfx, rows * C)
+        g_mid = self.wsf('gmid' + lsfx, rows * C)
+        g_out = self.wsf(('gout' + sfx) if self.SIDE else 'gout%d' % (l & 1), rows * C)
+        dqkv = self.wsf('dqkv' + lsfx, rows * 3 * C)
+        # The routes differ in how a linear is emitted (_layer_dgrad) and in where the two LayerNorm backwards attach.  Staged
+        # split-bf16 kernels (x3s): they are row prologues -- LN2' (+ the residual gradient g_cur) of the to_out dgrad, which
+        # writes g_mid; LN1' (+ g_mid) of the ff.net.3 dgrad of the layer BELOW, which writes g_out = that layer's g_cur.
+        # Split-bf16 (x3) and exact fp32: ops of their own that also sum the K-split planes of the linear in front of them
+        # (and write the sums back for the LayerNorm parameter gradients on the side stream).
+        ln2 = [self.pref(pre + 'ln2.weight'), xmid, m2, r2, g_cur, g_mid]
+        ln1 = [self.pref(pre + 'ln1.weight'), x_in, m1, r1, g_mid, g_out]
+        # FFN second linear: x_out = xmid + f W3^T + b3
+        if ln1_above is None:
+            self._layer_dgrad(g_cur, W3, dz, rows, 4 * C, C, dact=L.DACT_GELU, aux_in=z)
+        else:
+            self._layer_dgrad(ln1_above[0], W3, dz, rows, 4 * C, C, ln=(2, ln1_above[1]), dact=L.DACT_GELU, aux_in=z)
+        # FFN first linear, LN2 (+ residual branch gradient g_cur), attention output projection: xmid = x_in + o Wo^T + bo
+        plane = self._layer_dgrad(dz, W1f, dhA, rows, C, 4 * C, plane='dhA_plane')
+        if self.x3s:
+            self._layer_dgrad(dhA, Wo, bb.do, rows, C, C, ln=(2, ln2))
+        else:
+            self._layernorm_bwd(dhA, ln2, plane, rows)
+            # (its output feeds the attention backward, which reads ONE matrix: no K split)
+            self._layer_dgrad(g_mid, Wo, bb.do, rows, C, C)
+        self.op(L.OP_ATTN_BWD, refs=(dqkv, bb.do, qkv, Pm, o, bb.hist_amax if l == 0 else self.NONE, bb.dBias, self.r_nn),
+                ints=(B, N, C, H))
+        plane = self._layer_dgrad(dqkv, Wq, dhB, rows, C, 3 * C, plane='dhB_plane')
+        ln1_below = None
+        if self.x3s and l > 0:
+            ln1_below = (dhB, ln1)
+        else:
+            self._layernorm_bwd(dhB, ln1, plane, rows)
+        side = dict(pre=pre, g_cur=g_cur, f=f, dz=dz, h2=h2, g_mid=g_mid, o=o, dqkv=dqkv, h1=h1, dhA=dhA,
+                    xmid=xmid, m2=m2, r2=r2, dhB=dhB, x_in=x_in, m1=m1, r1=r1)
+        return g_out, ln1_below, side
+
+    def _bwd_graphormer(self, bb, g_xl):
+        """Graphormer layers, reversed: the chain of every layer (_bwd_layer) and the side-stream work of the layers -- four weight
+        gradients (+ fused bias gradients) and the two LayerNorm parameter gradients each (_layer_side_ops).  Returns the
+        gradient of the node embeddings."""
+        sw, rows = bb.sw, self.B * self.N
+        # Round 4 (`defer`, side stream only): ALL layers' weight gradients are ONE grouped launch and all
+        # LayerNorm parameter gradients ONE batched launch behind the chain -- the 24 x 3 small side launches beside the
+        # chain cost 0.30 ms of step time (hand-off stalls, CU slots) for 0.56 ms of kernel time; every temporary they read
+        # is a per-layer buffer anyway.  Without a side stream (or GHN3_LAYER_WGRAD_DEFER=0) they follow their layer:
+        # the side-stream ops of `side_group` consecutive layers are then issued together -- every main -> side hand-off is an
+        # event record that stalls the main chain for 6-12 us, and the temporaries the side ops read are per layer anyway.
+        defer = bool(self.SIDE) and sw.layer_wgrad_defer
+        side_group = max(1, sw.side_group) if self.SIDE else 1
+        layer_side, side_done, side_pending = [], 0, []
+        g_cur, ln1_pending = g_xl, None
         for l in reversed(range(self.Lyr)):
-            pre = 'gnn.%d.' % l
-            sfx = '_%d' % l
-            x_in = self.wref('x%d' % l)
-            h1, qkv, Pm, o = self.wref('h1' + sfx), self.wref('qkv' + sfx), self.wref('P' + sfx), self.wref('o' + sfx)
-            xmid, h2, z, f = self.wref('xmid' + sfx), self.wref('h2' + sfx), self.wref('z' + sfx), self.wref('f' + sfx)
-            m1, r1, m2, r2 = self.wref('m1' + sfx), self.wref('r1' + sfx), self.wref('m2' + sfx), self.wref('r2' + sfx)
-            W3, W1f, Wo, Wq = pre + 'ff.net.3.weight', pre + 'ff.net.0.weight', pre + 'attn.to_out.0.weight', \
-                pre + 'attn.to_qkv.weight'
-            # The four dgrad GEMMs, the two LayerNorm backward passes and the attention backward form the dependent
-            # chain of the layer.  The four wgrad GEMMs (+ fused bias gradients, ONE grouped launch) and the two
-            # LayerNorm parameter gradients are off that chain: they run on the side stream, which is why every
-            # temporary they read (g_cur, dz, dhA, g_mid, dqkv, dhB) is a buffer of THIS layer -- the chain of the
-            # next layer may start while they are still being read.
-            lsfx = sfx if self.SIDE else ''
-            dz = self.wsf('dz' + lsfx, rows * 4 * C)
-            dhA, dhB = self.wsf('dhA' + lsfx, rows * C), self.wsf('dhB' + lsfx, rows * C)
-            g_mid = self.wsf('gmid' + lsfx, rows * C)
-            g_out = self.wsf(('gout' + sfx) if self.SIDE else 'gout%d' % (l & 1), rows * C)
-            dqkv = self.wsf('dqkv' + lsfx, rows * 3 * C)
-            if self.x3s:
-                # staged split-bf16 dgrads against the transposed (fragment-major) weight copies.  The two LayerNorm
-                # backward passes are row prologues: LN2' (+ the residual gradient g_cur) of the to_out dgrad, which writes
-                # g_mid; LN1' (+ g_mid) of the ff.net.3 dgrad of the layer BELOW, which writes g_out = that layer's g_cur.
-                self.x3s_linear(g_cur if pending_ln1 is None else pending_ln1[0], W3, True, dz, rows, 4 * C, C, C, 4 * C,
-                                ln=None if pending_ln1 is None else (2, pending_ln1[1]), dact=L.DACT_GELU, aux_in=z)
-                if pending_ln1 is not None:
-                    g_cur = pending_ln1[1][5]           # (written by the prologue: this layer's upstream gradient)
-                pending_ln1 = None
-                self.x3s_linear(dz, W1f, True, dhA, rows, C, 4 * C, 4 * C, C)
-                self.x3s_linear(dhA, Wo, True, do, rows, C, C, C, C,
-                                ln=(2, [self.pref(pre + 'ln2.weight'), xmid, m2, r2, g_cur, g_mid]))
-                self.op(L.OP_ATTN_BWD, refs=(dqkv, do, qkv, Pm, o, hist_amax if l == 0 else self.NONE, dBias, r_nn), ints=(B, N, C, H))
-                self.x3s_linear(dqkv, Wq, True, dhB, rows, C, 3 * C, 3 * C, C)
-                if l > 0:
-                    pending_ln1 = (dhB, [self.pref(pre + 'ln1.weight'), x_in, m1, r1, g_mid, g_out])
-                else:
-                    self.op(L.OP_LAYERNORM_BWD, refs=(g_out, dhB, x_in, self.pref(pre + 'ln1.weight'), m1, r1, g_mid,
-                                                      self.NONE), ints=(rows, C))
-            elif self.x3:
-                # split-bf16 dgrads against the transposed weight copies; K splits -> planes summed by the LayerNorm
-                # backward ops (which write the sums back for the LayerNorm parameter gradients on the side stream)
-                self.x3_linear(g_cur, W3, True, dz, rows, 4 * C, C, C, 4 * C, dact=L.DACT_GELU, aux_in=z)
-                np_, pl = self.x3_linear(dz, W1f, True, dhA, rows, C, 4 * C, 4 * C, C, split=True, planes='dhA_plane')
-                self.op(L.OP_LAYERNORM_BWD, refs=(g_mid, dhA, xmid, self.pref(pre + 'ln2.weight'), m2, r2, g_cur,
-                                                  pl if np_ else self.NONE), ints=(rows, C, np_, rows * C))
-                # (its output feeds the attention backward, which reads ONE matrix: no K split)
-                self.x3_linear(g_mid, Wo, True, do, rows, C, C, C, C)
-                self.op(L.OP_ATTN_BWD, refs=(dqkv, do, qkv, Pm, o, hist_amax if l == 0 else self.NONE, dBias, r_nn), ints=(B, N, C, H))
-                np_, pl = self.x3_linear(dqkv, Wq, True, dhB, rows, C, 3 * C, 3 * C, C, split=True, planes='dhB_plane')
-                self.op(L.OP_LAYERNORM_BWD, refs=(g_out, dhB, x_in, self.pref(pre + 'ln1.weight'), m1, r1, g_mid,
-                                                  pl if np_ else self.NONE), ints=(rows, C, np_, rows * C))
-            else:
-                # FFN second linear: x_out = xmid + f W3^T + b3
-                p0 = self.gemm(g_cur, self.pref(W3), dz, rows, 4 * C, C, C, 4 * C, 4 * C, a_mode=L.MODE_ROW, b_mode=L.MODE_COL,
-                               dact=L.DACT_GELU, aux_in=z)
-                self.gemm_op(p0)
-                # FFN first linear
-                dhA_p = None
-                if self.split_small(rows, C, 4 * C):
-                    dhA_p = self.wsf('dhA_plane', rows * C)
-                    p0 = self.gemm_k2(dz, self.pref(W1f), dhA, dhA_p, rows, C, 4 * C, 4 * C, C, C, L.MODE_COL)
-                else:
-                    p0 = self.gemm(dz, self.pref(W1f), dhA, rows, C, 4 * C, 4 * C, C, C, a_mode=L.MODE_ROW,
-                                   b_mode=L.MODE_COL)
-                self.gemm_op(p0)
-                # LN2 (+ residual branch gradient g_cur)
-                self.op(L.OP_LAYERNORM_BWD, refs=(g_mid, dhA, xmid, self.pref(pre + 'ln2.weight'), m2, r2, g_cur,
-                                                  dhA_p or self.NONE), ints=(rows, C))
-                # attention output projection: xmid = x_in + o Wo^T + bo
-                p0 = self.gemm(g_mid, self.pref(Wo), do, rows, C, C, C, C, C, a_mode=L.MODE_ROW, b_mode=L.MODE_COL)
-                self.gemm_op(p0)
-                self.op(L.OP_ATTN_BWD, refs=(dqkv, do, qkv, Pm, o, hist_amax if l == 0 else self.NONE, dBias, r_nn), ints=(B, N, C, H))
-                dhB_p = None
-                if self.split_small(rows, C, 3 * C):
-                    dhB_p = self.wsf('dhB_plane', rows * C)
-                    p0 = self.gemm_k2(dqkv, self.pref(Wq), dhB, dhB_p, rows, C, 3 * C, 3 * C, C, C, L.MODE_COL)
-                else:
-                    p0 = self.gemm(dqkv, self.pref(Wq), dhB, rows, C, 3 * C, 3 * C, C, C, a_mode=L.MODE_ROW,
-                                   b_mode=L.MODE_COL)
-                self.gemm_op(p0)
-                self.op(L.OP_LAYERNORM_BWD, refs=(g_out, dhB, x_in, self.pref(pre + 'ln1.weight'), m1, r1, g_mid,
-                                                  dhB_p or self.NONE), ints=(rows, C))
-            # Side-stream work of the layer: four weight gradients (+ fused bias gradients) and the two LayerNorm parameter
-            # gradients.  Round 4 (`defer`, side stream only): ALL layers' weight gradients are ONE grouped launch and all
-            # LayerNorm parameter gradients ONE batched launch behind the chain -- the 24 x 3 small side launches beside the
-            # chain cost 0.30 ms of step time (hand-off stalls, CU slots) for 0.56 ms of kernel time; every temporary they read
-            # is a per-layer buffer anyway.  Without a side stream (or GHN3_LAYER_WGRAD_DEFER=0) they follow their layer.
-            layer_side.append(dict(pre=pre, g_cur=g_cur, f=f, dz=dz, h2=h2, g_mid=g_mid, o=o, dqkv=dqkv, h1=h1, dhA=dhA,
-                                   xmid=xmid, m2=m2, r2=r2, dhB=dhB, x_in=x_in, m1=m1, r1=r1))
-            if defer and defer_group and len(layer_side) - side_done >= defer_group and l > 0:
-                self._layer_side_ops(layer_side[side_done:], rows)       # (a group of layers, beside the chain)
+            g_cur, ln1_pending, side = self._bwd_layer(bb, l, g_cur, ln1_pending)
+            layer_side.append(side)
+            if defer and sw.layer_wgrad_group and len(layer_side) - side_done >= sw.layer_wgrad_group and l > 0:
+                self._layer_side_ops(sw, layer_side[side_done:], rows)       # (a group of layers, beside the chain)
                 side_done = len(layer_side)
             if not defer:
-                main_ops, self._ops = self._ops, []
-                self._layer_side_ops([layer_side[-1]], rows)
-                side_pending, self._ops = side_pending + self._ops, main_ops
+                n_chain = len(self._ops)
+                self._layer_side_ops(sw, [side], rows)
+                side_pending += self._cut_ops(n_chain)
                 if (self.Lyr - l) % side_group == 0 or l == 0:
                     self._ops.extend(side_pending)
                     side_pending = []
-            g_cur = g_out                   # d x_l
         if defer and side_done < len(layer_side):
-            self._layer_side_ops(layer_side[side_done:], rows)
-        # ---- node embeddings (side stream: beside the edge-bias backward below, which does not depend on it) --------
+            self._layer_side_ops(sw, layer_side[side_done:], rows)
+        return g_cur
+
+    def _bwd_embed_and_edge_bias(self, bb, g_x0):
+        """Node-embedding backward and the layer-0 edge bias: histogram -> table MLP backward."""
+        C, H, B, N, V, ldT = self.C, self.H, self.B, self.N, self.V, self.ldT
+        (r_types, r_shape, r_nn, r_noff, deg_in, deg_out, dist0, pair) = self.r_graph
+        # (GHN3_EMBED_BWD_MAIN=0: on the side stream, beside the edge-bias backward below, which does not depend on it)
         self.op(L.OP_EMBED_BWD,
-                refs=(g_cur, r_types, r_shape, r_nn, r_noff, self.gref('embed.weight'),
+                refs=(g_x0, r_types, r_shape, r_nn, r_noff, self.gref('embed.weight'),
                       self.gref('shape_enc.embed_channel.weight'), self.gref('shape_enc.embed_spatial.weight'),
                       self.gref('gnn.0.centrality_embed_in.weight'), self.gref('gnn.0.centrality_embed_out.weight'),
                       self.gref('gnn.0.input_dist_embed.weight'), deg_in, deg_out, dist0),
                 ints=(B, N, C, len(bk.PRIMITIVES_DEEPNETS1M), self.vocab_rows[0], self.vocab_rows[1]),
-                flags=0 if os.environ.get('GHN3_EMBED_BWD_MAIN', '1') == '1' else self.SIDE)
-        # ---- layer-0 edge bias: histogram -> table MLP backward ------------------------------------------
+                flags=0 if bb.sw.embed_bwd_main else self.SIDE)
         E = 'gnn.0.attn.edge_embed.embed.weight'
         W0e, b0e = 'gnn.0.attn.proj_e.0.weight', 'gnn.0.attn.proj_e.0.bias'
         W2e, b2e = 'gnn.0.attn.proj_e.2.weight', 'gnn.0.attn.proj_e.2.bias'
@@ -2441,7 +2586,7 @@ class Program:
         dPfw, dPbw = self.wsf('dPfw', V * C), self.wsf('dPbw', V * C)
         hid = self.wref('hid')
         self.op(L.OP_MEMSET0, refs=(dT,), ints=(4 * V * V * ldT,))
-        self.op(L.OP_BIAS_HIST, refs=(dT, dBias, pair, hist), ints=(B, N, H, V, 1))
+        self.op(L.OP_BIAS_HIST, refs=(dT, bb.dBias, pair, bb.hist), ints=(B, N, H, V, 1))
         p0 = self.gemm(dT, hid, self.gref(W2e), H, C, V * V, ldT, C, C, a_mode=L.MODE_COL, b_mode=L.MODE_COL,
                        accum=True, dbias=self.gref(b2e))
         self.gemm_op(p0, side=True)                      # (weight gradient: off the chain)

@@ -44,4 +44,4 @@ with open(out, 'w') as fh:
             else:
                 flops += 2.0 * h * min(int(p['N']), max(int(ext), 0)) * int(p['K'])
 print(which, 'problems', len(sel), 'padded GFLOP', flops / 1e9, 'algorithmic GFLOP',
-      prog.tag_flops[prog.TAG_D3_DGRAD if which == 'dgrad' else prog.TAG_D3_FWD] / 1e9, 'sub', getattr(prog, 'dgrad_sub', None))
+      prog.tag_flops[prog.TAG_D3_DGRAD if which == 'dgrad' else prog.TAG_D3_FWD] / 1e9, 'sub', prog.dgrad_sub)
