@@ -775,27 +775,64 @@ Plan make_plan(const Desc& d) {
     return pl;
 }
 
-int check_desc(const ghn3_dwpw_desc* g, Desc& d) {
-    if (!g) { ghn3_set_error("dwpw: null descriptor"); return GHN3_E_ARG; }
+constexpr int DWPW_MAX_C = 512;     // the fused chain: all output columns of a pixel tile in one workgroup's accumulators
+constexpr int DW_MAX_C = 16384;     // the depthwise stage alone
+
+// The descriptor check of the family: `who` begins every message, max_c is the width limit, `alone` (the depthwise stage alone,
+// ghn3_dw_*) requires C_out == C_in.  The defaults are the fused chain's.
+int check_desc(const ghn3_dwpw_desc* g, Desc& d, const char* who = "dwpw", int max_c = DWPW_MAX_C, bool alone = false) {
+    if (!g) { ghn3_set_error("%s: null descriptor", who); return GHN3_E_ARG; }
     d = Desc{g->N, g->H, g->W, g->C_in, g->C_out, g->ks, g->stride, g->pad, g->dil, g->Ho, g->Wo, g->eps};
-    if (d.N <= 0 || d.H <= 0 || d.W <= 0 || d.C_in <= 0 || d.C_out <= 0 || d.ks <= 0 || d.stride <= 0 || d.dil <= 0 || d.pad < 0) {
-        ghn3_set_error("dwpw: non-positive size in the descriptor");
+    if (d.N <= 0 || d.H <= 0 || d.W <= 0 || d.C_in <= 0 || (alone ? d.C_out != d.C_in : d.C_out <= 0) || d.ks <= 0 || d.stride <= 0 ||
+        d.dil <= 0 || d.pad < 0) {
+        ghn3_set_error("%s: non-positive size in the descriptor%s", who, alone ? ", or C_out != C_in" : "");
         return GHN3_E_ARG;
     }
-    if ((d.C_in & 3) || (d.C_out & 3) || d.C_in > 512 || d.C_out > 512 || d.ks > 7) {
-        ghn3_set_error("dwpw: needs C_in, C_out multiples of 4 and <= 512, ks <= 7 (got %d -> %d, ks %d)", d.C_in, d.C_out, d.ks);
+    if ((d.C_in & 3) || (d.C_out & 3) || d.C_in > max_c || d.C_out > max_c || d.ks > 7) {
+        if (alone) ghn3_set_error("%s: needs C a multiple of 4 and <= %d, ks <= 7 (got %d, ks %d)", who, max_c, d.C_in, d.ks);
+        else ghn3_set_error("%s: needs C_in, C_out multiples of 4 and <= %d, ks <= 7 (got %d -> %d, ks %d)", who, max_c, d.C_in, d.C_out, d.ks);
         return GHN3_E_LIMIT;
     }
     const int ho = (d.H + 2 * d.pad - d.dil * (d.ks - 1) - 1) / d.stride + 1, wo = (d.W + 2 * d.pad - d.dil * (d.ks - 1) - 1) / d.stride + 1;
     if (ho != d.Ho || wo != d.Wo || ho <= 0 || wo <= 0) {
-        ghn3_set_error("dwpw: output size %d x %d does not match the convolution arithmetic (%d x %d)", d.Ho, d.Wo, ho, wo);
+        ghn3_set_error("%s: output size %d x %d does not match the convolution arithmetic (%d x %d)", who, d.Ho, d.Wo, ho, wo);
         return GHN3_E_ARG;
     }
     if ((int64_t)d.N * d.H * d.W * std::max(d.C_in, d.C_out) >= ((int64_t)1 << 31) ||
         (int64_t)d.N * d.Ho * d.Wo * std::max(d.C_in, d.C_out) >= ((int64_t)1 << 31)) {
-        ghn3_set_error("dwpw: activation tensors of 2^31 elements or more are not supported");
+        ghn3_set_error("%s: activation tensors of 2^31 elements or more are not supported", who);
         return GHN3_E_LIMIT;
     }
+    return GHN3_OK;
+}
+
+// ---- launch idioms ---------------------------------------------------------------------------------------------------------------
+// hipGetLastError after a launch, reported as "<what>: <HIP's text>" (TNET_LAUNCH_CHECK for a name that is not a literal)
+inline int launched(const char* what) {
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return GHN3_OK;
+    ghn3_set_error("%s: %s", what, hipGetErrorString(e));
+    return GHN3_E_HIP;
+}
+
+// the grid of a flat grid-stride kernel: one thread per item up to `cap` workgroups
+inline dim3 grid1d(int64_t items, int cap) { return dim3((int)std::min<int64_t>((items + 255) / 256, cap)); }
+
+// out = the fixed-order sum of the `rows` partial rows of `cols` floats (a, b: tnet_reduce_rows_kernel's transposition, 0, 0 = none)
+int reduce_rows(const float* part, int rows, int64_t cols, float* out, int a, int b, hipStream_t s, const char* what) {
+    hipLaunchKernelGGL(tnet_reduce_rows_kernel, dim3((int)((cols / 4 + 15) / 16)), dim3(256), 0, s, part, rows, cols, out, a, b);
+    return launched(what);
+}
+
+// mean | rstd of the batch from the forward's per-tile (mean, M2), then out = (z - mean) rstd gamma + beta: the two launches
+// behind the forward kernel of a member with batch statistics
+int bn_apply_launch(const float* part, int n_tiles, int P, int C, float eps, const float* z, const float* gamma, const float* beta,
+                    float* stats, float* out, hipStream_t s) {
+    hipLaunchKernelGGL(tnet_bn_finalize_kernel, dim3((C + 15) / 16), dim3(256), 0, s, part, n_tiles, P, C, eps, stats);
+    TNET_LAUNCH_CHECK("bn finalize")
+    const int64_t total4 = (int64_t)P * C / 4;
+    hipLaunchKernelGGL(tnet_bn_apply_kernel, grid1d(total4, 4096), dim3(256), 0, s, z, stats, gamma, beta, out, total4, C);
+    TNET_LAUNCH_CHECK("bn apply")
     return GHN3_OK;
 }
 
@@ -821,8 +858,8 @@ int bn_param_grads(const float* dout, const float* z, const float* stats, float*
     hipLaunchKernelGGL(tnet_bn_bwd_partial_kernel, dim3(n_tiles), dim3(256), nq > 256 ? 0 : (size_t)ng * 2 * C * 4, s, dout, z, stats,
                        part12, P, C);
     TNET_LAUNCH_CHECK("bn bwd partial")
-    hipLaunchKernelGGL(tnet_reduce_rows_kernel, dim3((2 * C / 4 + 15) / 16), dim3(256), 0, s, part12, n_tiles, (int64_t)2 * C, s12, 0, 0);
-    TNET_LAUNCH_CHECK("bn bwd reduce")
+    const int rc = reduce_rows(part12, n_tiles, (int64_t)2 * C, s12, 0, 0, s, "bn bwd reduce");
+    if (rc) return rc;
     if (!in_place) {
         (void)hipMemcpyAsync(dbeta, s12, (size_t)C * 4, hipMemcpyDeviceToDevice, s);
         (void)hipMemcpyAsync(dgamma, s12 + C, (size_t)C * 4, hipMemcpyDeviceToDevice, s);
@@ -839,10 +876,14 @@ int dw_wgrad(const Desc& d, const Plan& pl, const float* dy, const float* x, flo
     hipLaunchKernelGGL(tnet_dw_wgrad_kernel, dim3(pl.dw_chunks, (nq + 255) / 256), dim3(256), lds, s, dy, x, part_dw, d, pl.P,
                        pl.dw_chunk_px);
     TNET_LAUNCH_CHECK("dw wgrad")
-    const int64_t cols = (int64_t)taps * d.C_in;
-    hipLaunchKernelGGL(tnet_reduce_rows_kernel, dim3((int)((cols / 4 + 15) / 16)), dim3(256), 0, s, part_dw, pl.dw_chunks, cols, dw_dw,
-                       d.C_in, taps);
-    TNET_LAUNCH_CHECK("dw wgrad reduce")
+    return reduce_rows(part_dw, pl.dw_chunks, (int64_t)taps * d.C_in, dw_dw, d.C_in, taps, s, "dw wgrad reduce");
+}
+
+// dx = 1[x > 0] . transposed depthwise taps of dy (w_dw == nullptr: the ReLU mask alone)
+int dw_bwd_data(const Desc& d, const float* dy, const float* x, const float* w_dw, float* dx, hipStream_t s) {
+    const int64_t total4 = (int64_t)d.N * d.H * d.W * d.C_in / 4;
+    hipLaunchKernelGGL(tnet_dw_bwd_data_kernel, grid1d(total4, 8192), dim3(256), 0, s, dy, x, w_dw, dx, d, total4);
+    TNET_LAUNCH_CHECK("dw bwd data")
     return GHN3_OK;
 }
 
@@ -867,134 +908,171 @@ int dwpw_bwd_products(const Desc& d, const Plan& pl, const float* dout, const fl
     hipLaunchKernelGGL(tnet_pw_wgrad_kernel<NORM>, dim3(pl.pw_chunks, (d.C_out + 63) / 64, (d.C_in + 63) / 64), dim3(256), 0, s, dout, z, stats,
                        gamma, s12, x, w_dw, part_pw, d, pl.P, pl.pw_chunk_px);
     TNET_LAUNCH_CHECK("pw wgrad")
-    {
-        const int64_t cols = (int64_t)d.C_out * d.C_in;
-        hipLaunchKernelGGL(tnet_reduce_rows_kernel, dim3((int)((cols / 4 + 15) / 16)), dim3(256), 0, s, part_pw, pl.pw_chunks, cols, dw_pw, 0, 0);
-        TNET_LAUNCH_CHECK("pw wgrad reduce")
-    }
+    rc = reduce_rows(part_pw, pl.pw_chunks, (int64_t)d.C_out * d.C_in, dw_pw, 0, 0, s, "pw wgrad reduce");
+    if (rc) return rc;
     // 4. dx and dW_dw
-    {
-        const int64_t total4 = (int64_t)d.N * d.H * d.W * d.C_in / 4;
-        hipLaunchKernelGGL(tnet_dw_bwd_data_kernel, dim3((int)std::min<int64_t>((total4 + 255) / 256, 8192)), dim3(256), 0, s, dy, x, w_dw,
-                           dx, d, total4);
-        TNET_LAUNCH_CHECK("dw bwd data")
-        if (w_dw) {
-            rc = dw_wgrad(d, pl, dy, x, part_dw, dw_dw, s);
-            if (rc) return rc;
-        }
-    }
+    rc = dw_bwd_data(d, dy, x, w_dw, dx, s);
+    if (rc || !w_dw) return rc;
+    return dw_wgrad(d, pl, dy, x, part_dw, dw_dw, s);
+}
+
+// (mean, var) of a frozen norm layer -> (mean, rstd) in `stats` [2 C]
+int frozen_stats(const float* mean, const float* var, float eps, int C, float* stats, hipStream_t s) {
+    hipLaunchKernelGGL(tnet_bn_frozen_stats_kernel, dim3((C + 255) / 256), dim3(256), 0, s, mean, var, eps, C, stats);
+    TNET_LAUNCH_CHECK("bn frozen stats")
     return GHN3_OK;
+}
+
+// The scratch buffer of a member of the dwpw family (`norm` = NORM_NONE, NORM_BATCH or NORM_FROZEN) in one direction: where each
+// area starts, in floats, and the size the caller allocates.  THE one description of the layout: the size functions return
+// `total`, the entry points read the offsets; an area a member does not have stays at 0 and is not used.
+//   forward   batch: part12 = per tile (mean, M2); the other members need no scratch (total 0)
+//   backward  part12 = per tile (sum dout, sum dout xhat), s12 = their reduction when dbeta / dgamma cannot take it in place
+//             (members with a norm layer); stats = (mean, rstd) of the frozen statistics; dy; the two weight gradients' partials
+struct DwpwScratch { int64_t part12, s12, stats, dy, part_pw, part_dw, total; };
+
+inline int64_t part_dw_floats(const Desc& d, const Plan& pl) { return (int64_t)pl.dw_chunks * d.ks * d.ks * d.C_in; }
+
+DwpwScratch dwpw_scratch(const Desc& d, const Plan& pl, int norm, bool backward) {
+    DwpwScratch sc = {};
+    int64_t at = 0;
+    auto take = [&at](int64_t n) { const int64_t o = at; at += n; return o; };
+    if (!backward) {
+        if (norm != NORM_BATCH) return sc;
+        sc.part12 = take((int64_t)pl.n_tiles * 2 * d.C_out);
+        sc.total = at + 64;
+        return sc;
+    }
+    if (norm != NORM_NONE) {
+        sc.part12 = take((int64_t)pl.n_tiles * 2 * d.C_out);
+        sc.s12 = take(2 * d.C_out);
+    }
+    if (norm == NORM_FROZEN) sc.stats = take(2 * d.C_out);
+    sc.dy = take((int64_t)pl.P * d.C_in);
+    sc.part_pw = take((int64_t)pl.pw_chunks * d.C_out * d.C_in);
+    sc.part_dw = take(part_dw_floats(d, pl));
+    sc.total = at + 256;
+    return sc;
+}
+
+// what the three size functions of the fused chain answer: -1 for every descriptor the op refuses (ghn3_last_error has the reason)
+int64_t dwpw_scratch_floats(const ghn3_dwpw_desc* g, int norm, int backward) {
+    Desc d;
+    if (check_desc(g, d)) return -1;
+    return dwpw_scratch(d, make_plan(d), norm, backward != 0).total;
+}
+
+// without depthwise weights the chain is ReLU -> 1x1 convolution: `op` = how the message of the entry point words that
+int check_w_dw(const Desc& d, const float* w_dw, const char* op) {
+    if (w_dw || (d.ks == 1 && d.pad == 0)) return GHN3_OK;
+    ghn3_set_error("dwpw: without depthwise weights %sks = 1, pad = 0", op);
+    return GHN3_E_ARG;
+}
+
+// The forward kernel of the family -- its only launch.  NORM_BATCH: pre-norm activations to z, per-tile statistics to `part`.
+// NORM_NONE: the accumulators are the result, stored to `out`.  NORM_FROZEN: the affine map of (gamma, beta, mean, var) in the
+// epilogue, the result to `out`, z beside it when non-null.  What a member does not have is not passed on.
+template <int NORM>
+int dwpw_fwd_launch(const Desc& d, const Plan& pl, const float* x, const float* w_dw, const float* w_pw, const float* gamma,
+                    const float* beta, const float* mean, const float* var, float* z, float* out, float* part, hipStream_t s,
+                    const char* what) {
+    const int NT = nt_of(d.C_out);
+    const size_t lds = fwd_lds(NT, NORM == NORM_BATCH);
+    float* const dst = NORM == NORM_NONE ? out : z;
+    float* const tiles = NORM == NORM_BATCH ? part : nullptr;
+    const Frozen fz = NORM == NORM_FROZEN ? Frozen{gamma, beta, mean, var, out} : Frozen{};
+    int rc;
+#define FWD_CASE(n) case n: rc = tnet_raise_lds(tnet_dwpw_fwd_kernel<n, NORM>, lds); if (rc) return rc; \
+        hipLaunchKernelGGL((tnet_dwpw_fwd_kernel<n, NORM>), dim3(pl.n_tiles), dim3(256), lds, s, x, w_dw, w_pw, dst, tiles, d, pl.P, fz); break;
+    switch (NT) { FWD_CASE(4) FWD_CASE(8) FWD_CASE(16) FWD_CASE(32) }
+#undef FWD_CASE
+    return launched(what);
+}
+
+// The forward of a member: `who` names it in the messages, `required` = none of the pointers it needs is null (w_dw is optional
+// for every member; the norm's arguments are null for the members without them).
+template <int NORM>
+int dwpw_fwd_core(const ghn3_dwpw_desc* g, const char* who, bool required, const float* x, const float* w_dw, const float* w_pw,
+                  const float* gamma, const float* beta, const float* mean, const float* var, float* z, float* out, float* stats,
+                  float* scratch, void* stream_) {
+    Desc d;
+    int rc = check_desc(g, d);
+    if (rc) return rc;
+    if (!required) { ghn3_set_error("%s: null pointer", who); return GHN3_E_ARG; }
+    rc = check_w_dw(d, w_dw, NORM == NORM_NONE ? "the op is ReLU -> 1x1 conv: " : "the op is ReLU -> 1x1 conv -> norm: ");
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream_;
+    const Plan pl = make_plan(d);
+    float* const part = NORM == NORM_BATCH ? scratch + dwpw_scratch(d, pl, NORM, false).part12 : nullptr;
+    rc = dwpw_fwd_launch<NORM>(d, pl, x, w_dw, w_pw, gamma, beta, mean, var, z, out, part, s, who);
+    if (rc || NORM != NORM_BATCH) return rc;
+    return bn_apply_launch(part, pl.n_tiles, pl.P, d.C_out, d.eps, z, gamma, beta, stats, out, s);
+}
+
+// The backward of a member.  Batch statistics: `stats` is the forward's; frozen: (mean, var) -> (mean, rstd) in scratch first.
+// Then 1. dgamma / dbeta (members with a norm layer) and 2 - 4. dwpw_bwd_products.
+template <int NORM>
+int dwpw_bwd_core(const ghn3_dwpw_desc* g, const char* who, bool required, const float* dout, const float* x, const float* z,
+                  const float* stats, const float* w_dw, const float* w_pw, const float* gamma, const float* mean, const float* var,
+                  float* dx, float* dw_dw, float* dw_pw, float* dgamma, float* dbeta, float* scratch, void* stream_) {
+    Desc d;
+    int rc = check_desc(g, d);
+    if (rc) return rc;
+    if (!required || (w_dw && !dw_dw)) { ghn3_set_error("%s: null pointer", who); return GHN3_E_ARG; }
+    rc = check_w_dw(d, w_dw, "");
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream_;
+    const Plan pl = make_plan(d);
+    const DwpwScratch sc = dwpw_scratch(d, pl, NORM, true);
+    const float* s12 = nullptr;
+    if (NORM == NORM_FROZEN) {
+        rc = frozen_stats(mean, var, d.eps, d.C_out, scratch + sc.stats, s);
+        if (rc) return rc;
+        stats = scratch + sc.stats;
+    }
+    if (NORM != NORM_NONE) {
+        rc = bn_param_grads(dout, z, stats, scratch + sc.part12, scratch + sc.s12, dgamma, dbeta, pl.n_tiles, pl.P, d.C_out, s, &s12);
+        if (rc) return rc;
+    }
+    // (dz: batch statistics read z and the reduced pair, frozen ones neither)
+    return dwpw_bwd_products<NORM>(d, pl, dout, NORM == NORM_BATCH ? z : nullptr, stats, gamma, NORM == NORM_BATCH ? s12 : nullptr, x, w_dw,
+                                   w_pw, dx, dw_dw, dw_pw, scratch + sc.dy, scratch + sc.part_pw, scratch + sc.part_dw, s);
 }
 
 }  // namespace
 
-extern "C" int64_t ghn3_dwpw_scratch_floats(const ghn3_dwpw_desc* g, int backward) {
-    Desc d;
-    if (check_desc(g, d)) return -1;
-    const Plan pl = make_plan(d);
-    if (!backward) return (int64_t)pl.n_tiles * 2 * d.C_out + 64;
-    const int taps = d.ks * d.ks;
-    return (int64_t)pl.n_tiles * 2 * d.C_out + 2 * d.C_out + (int64_t)pl.P * d.C_in +
-           (int64_t)pl.pw_chunks * d.C_out * d.C_in + (int64_t)pl.dw_chunks * taps * d.C_in + 256;
-}
+// The three size functions of the fused chain answer -1 (= GHN3_E_ARG) for EVERY refusal, a limit included; ghn3_dw_scratch_floats
+// and the dense-convolution pair answer the GHN3_E_* code of the refusal.
+extern "C" int64_t ghn3_dwpw_scratch_floats(const ghn3_dwpw_desc* g, int backward) { return dwpw_scratch_floats(g, NORM_BATCH, backward); }
 
 extern "C" int ghn3_dwpw_bn_fwd(const ghn3_dwpw_desc* g, const float* x, const float* w_dw, const float* w_pw, const float* gamma,
                                 const float* beta, float* z, float* out, float* stats, float* scratch, void* stream_) {
-    Desc d;
-    int rc = check_desc(g, d);
-    if (rc) return rc;
-    if (!x || !w_pw || !gamma || !beta || !z || !out || !stats || !scratch) { ghn3_set_error("dwpw fwd: null pointer"); return GHN3_E_ARG; }
-    if (!w_dw && (d.ks != 1 || d.pad != 0)) { ghn3_set_error("dwpw: without depthwise weights the op is ReLU -> 1x1 conv -> norm: ks = 1, pad = 0"); return GHN3_E_ARG; }
-    hipStream_t s = (hipStream_t)stream_;
-    const Plan pl = make_plan(d);
-    const int NT = nt_of(d.C_out);
-    const size_t lds = fwd_lds(NT);
-#define FWD_CASE(n) case n: rc = tnet_raise_lds(tnet_dwpw_fwd_kernel<n>, lds); if (rc) return rc; \
-        hipLaunchKernelGGL((tnet_dwpw_fwd_kernel<n>), dim3(pl.n_tiles), dim3(256), lds, s, x, w_dw, w_pw, z, scratch, d, pl.P, Frozen{}); break;
-    switch (NT) { FWD_CASE(4) FWD_CASE(8) FWD_CASE(16) FWD_CASE(32) }
-#undef FWD_CASE
-    TNET_LAUNCH_CHECK("dwpw fwd")
-    hipLaunchKernelGGL(tnet_bn_finalize_kernel, dim3((d.C_out + 15) / 16), dim3(256), 0, s, scratch, pl.n_tiles, pl.P, d.C_out, d.eps, stats);
-    TNET_LAUNCH_CHECK("bn finalize")
-    const int64_t total4 = (int64_t)pl.P * d.C_out / 4;
-    hipLaunchKernelGGL(tnet_bn_apply_kernel, dim3((int)std::min<int64_t>((total4 + 255) / 256, 4096)), dim3(256), 0, s, z, stats, gamma,
-                       beta, out, total4, d.C_out);
-    TNET_LAUNCH_CHECK("bn apply")
-    return GHN3_OK;
+    return dwpw_fwd_core<NORM_BATCH>(g, "dwpw fwd", x && w_pw && gamma && beta && z && out && stats && scratch, x, w_dw, w_pw, gamma, beta,
+                                     nullptr, nullptr, z, out, stats, scratch, stream_);
 }
 
 extern "C" int ghn3_dwpw_bn_bwd(const ghn3_dwpw_desc* g, const float* dout, const float* x, const float* z, const float* stats,
                                 const float* w_dw, const float* w_pw, const float* gamma, float* dx, float* dw_dw, float* dw_pw,
                                 float* dgamma, float* dbeta, float* scratch, void* stream_) {
-    Desc d;
-    int rc = check_desc(g, d);
-    if (rc) return rc;
-    if (!dout || !x || !z || !stats || !w_pw || !gamma || !dx || !dw_pw || !dgamma || !dbeta || !scratch || (w_dw && !dw_dw)) {
-        ghn3_set_error("dwpw bwd: null pointer");
-        return GHN3_E_ARG;
-    }
-    if (!w_dw && (d.ks != 1 || d.pad != 0)) { ghn3_set_error("dwpw: without depthwise weights ks = 1, pad = 0"); return GHN3_E_ARG; }
-    hipStream_t s = (hipStream_t)stream_;
-    const Plan pl = make_plan(d);
-    float* part12 = scratch;
-    float* const s12_scratch = part12 + (int64_t)pl.n_tiles * 2 * d.C_out;
-    float* dy = s12_scratch + 2 * d.C_out;
-    float* part_pw = dy + (int64_t)pl.P * d.C_in;
-    float* part_dw = part_pw + (int64_t)pl.pw_chunks * d.C_out * d.C_in;
-    // 1. dgamma / dbeta
-    const float* s12;
-    rc = bn_param_grads(dout, z, stats, part12, s12_scratch, dgamma, dbeta, pl.n_tiles, pl.P, d.C_out, s, &s12);
-    if (rc) return rc;
-    return dwpw_bwd_products<NORM_BATCH>(d, pl, dout, z, stats, gamma, s12, x, w_dw, w_pw, dx, dw_dw, dw_pw, dy, part_pw, part_dw, s);
+    return dwpw_bwd_core<NORM_BATCH>(g, "dwpw bwd", dout && x && z && stats && w_pw && gamma && dx && dw_pw && dgamma && dbeta && scratch,
+                                     dout, x, z, stats, w_dw, w_pw, gamma, nullptr, nullptr, dx, dw_dw, dw_pw, dgamma, dbeta, scratch, stream_);
 }
 
 // ---- the same family without a norm layer: out = pw(dw(relu(x))) -- the blocks of a norm=None network (ops.py:91-96) -----------
 // Forward: the forward kernel alone, its accumulators stored straight to `out` (no z, no statistics, no scratch).  Backward: dz IS
 // dout, so steps 2 - 4 of the backward above run on dout directly; nothing of activation size but x is kept between the two.
-extern "C" int64_t ghn3_dwpw_plain_scratch_floats(const ghn3_dwpw_desc* g, int backward) {
-    Desc d;
-    if (check_desc(g, d)) return -1;
-    if (!backward) return 0;
-    const Plan pl = make_plan(d);
-    return (int64_t)pl.P * d.C_in + (int64_t)pl.pw_chunks * d.C_out * d.C_in + (int64_t)pl.dw_chunks * d.ks * d.ks * d.C_in + 256;
-}
+extern "C" int64_t ghn3_dwpw_plain_scratch_floats(const ghn3_dwpw_desc* g, int backward) { return dwpw_scratch_floats(g, NORM_NONE, backward); }
 
 extern "C" int ghn3_dwpw_plain_fwd(const ghn3_dwpw_desc* g, const float* x, const float* w_dw, const float* w_pw, float* out,
                                    void* stream_) {
-    Desc d;
-    int rc = check_desc(g, d);
-    if (rc) return rc;
-    if (!x || !w_pw || !out) { ghn3_set_error("dwpw plain fwd: null pointer"); return GHN3_E_ARG; }
-    if (!w_dw && (d.ks != 1 || d.pad != 0)) { ghn3_set_error("dwpw: without depthwise weights the op is ReLU -> 1x1 conv: ks = 1, pad = 0"); return GHN3_E_ARG; }
-    hipStream_t s = (hipStream_t)stream_;
-    const Plan pl = make_plan(d);
-    const int NT = nt_of(d.C_out);
-    const size_t lds = fwd_lds(NT, false);
-    float* const no_part = nullptr;
-#define FWD_CASE(n) case n: rc = tnet_raise_lds(tnet_dwpw_fwd_kernel<n, NORM_NONE>, lds); if (rc) return rc; \
-        hipLaunchKernelGGL((tnet_dwpw_fwd_kernel<n, NORM_NONE>), dim3(pl.n_tiles), dim3(256), lds, s, x, w_dw, w_pw, out, no_part, d, pl.P, Frozen{}); break;
-    switch (NT) { FWD_CASE(4) FWD_CASE(8) FWD_CASE(16) FWD_CASE(32) }
-#undef FWD_CASE
-    TNET_LAUNCH_CHECK("dwpw plain fwd")
-    return GHN3_OK;
+    return dwpw_fwd_core<NORM_NONE>(g, "dwpw plain fwd", x && w_pw && out, x, w_dw, w_pw, nullptr, nullptr, nullptr, nullptr, nullptr, out,
+                                    nullptr, nullptr, stream_);
 }
 
 extern "C" int ghn3_dwpw_plain_bwd(const ghn3_dwpw_desc* g, const float* dout, const float* x, const float* w_dw, const float* w_pw,
                                    float* dx, float* dw_dw, float* dw_pw, float* scratch, void* stream_) {
-    Desc d;
-    int rc = check_desc(g, d);
-    if (rc) return rc;
-    if (!dout || !x || !w_pw || !dx || !dw_pw || !scratch || (w_dw && !dw_dw)) {
-        ghn3_set_error("dwpw plain bwd: null pointer");
-        return GHN3_E_ARG;
-    }
-    if (!w_dw && (d.ks != 1 || d.pad != 0)) { ghn3_set_error("dwpw: without depthwise weights ks = 1, pad = 0"); return GHN3_E_ARG; }
-    const Plan pl = make_plan(d);
-    float* dy = scratch;
-    float* part_pw = dy + (int64_t)pl.P * d.C_in;
-    float* part_dw = part_pw + (int64_t)pl.pw_chunks * d.C_out * d.C_in;
-    return dwpw_bwd_products<NORM_NONE>(d, pl, dout, nullptr, nullptr, nullptr, nullptr, x, w_dw, w_pw, dx, dw_dw, dw_pw, dy, part_pw,
-                                    part_dw, (hipStream_t)stream_);
+    return dwpw_bwd_core<NORM_NONE>(g, "dwpw plain bwd", dout && x && w_pw && dx && dw_pw && scratch, dout, x, nullptr, nullptr, w_dw, w_pw,
+                                    nullptr, nullptr, nullptr, dx, dw_dw, dw_pw, nullptr, nullptr, scratch, stream_);
 }
 
 // ---- the same family behind a norm layer with FROZEN statistics: out = (pw(dw(relu(x))) - mean) rstd gamma + beta, rstd = 1 /
@@ -1002,63 +1080,20 @@ extern "C" int ghn3_dwpw_plain_bwd(const ghn3_dwpw_desc* g, const float* dout, c
 // Forward: the forward kernel alone (NORM_FROZEN): the affine map in its epilogue, z stored beside out only when the caller
 // wants a backward.  Backward: (mean, var) -> (mean, rstd) once, dgamma / dbeta as with batch statistics, then steps 2 - 4 on
 // dz = dout gamma rstd formed on the fly.  The statistics are read only.
-extern "C" int64_t ghn3_dwpw_frozen_scratch_floats(const ghn3_dwpw_desc* g, int backward) {
-    Desc d;
-    if (check_desc(g, d)) return -1;
-    if (!backward) return 0;
-    const Plan pl = make_plan(d);
-    return (int64_t)pl.n_tiles * 2 * d.C_out + 4 * d.C_out + (int64_t)pl.P * d.C_in + (int64_t)pl.pw_chunks * d.C_out * d.C_in +
-           (int64_t)pl.dw_chunks * d.ks * d.ks * d.C_in + 256;
-}
+extern "C" int64_t ghn3_dwpw_frozen_scratch_floats(const ghn3_dwpw_desc* g, int backward) { return dwpw_scratch_floats(g, NORM_FROZEN, backward); }
 
 extern "C" int ghn3_dwpw_frozen_fwd(const ghn3_dwpw_desc* g, const float* x, const float* w_dw, const float* w_pw, const float* gamma,
                                     const float* beta, const float* mean, const float* var, float* z, float* out, void* stream_) {
-    Desc d;
-    int rc = check_desc(g, d);
-    if (rc) return rc;
-    if (!x || !w_pw || !gamma || !beta || !mean || !var || !out) { ghn3_set_error("dwpw frozen fwd: null pointer"); return GHN3_E_ARG; }
-    if (!w_dw && (d.ks != 1 || d.pad != 0)) { ghn3_set_error("dwpw: without depthwise weights the op is ReLU -> 1x1 conv -> norm: ks = 1, pad = 0"); return GHN3_E_ARG; }
-    hipStream_t s = (hipStream_t)stream_;
-    const Plan pl = make_plan(d);
-    const int NT = nt_of(d.C_out);
-    const size_t lds = fwd_lds(NT, false);
-    float* const no_part = nullptr;
-    const Frozen fz = {gamma, beta, mean, var, out};
-#define FWD_CASE(n) case n: rc = tnet_raise_lds(tnet_dwpw_fwd_kernel<n, NORM_FROZEN>, lds); if (rc) return rc; \
-        hipLaunchKernelGGL((tnet_dwpw_fwd_kernel<n, NORM_FROZEN>), dim3(pl.n_tiles), dim3(256), lds, s, x, w_dw, w_pw, z, no_part, d, pl.P, fz); break;
-    switch (NT) { FWD_CASE(4) FWD_CASE(8) FWD_CASE(16) FWD_CASE(32) }
-#undef FWD_CASE
-    TNET_LAUNCH_CHECK("dwpw frozen fwd")
-    return GHN3_OK;
+    return dwpw_fwd_core<NORM_FROZEN>(g, "dwpw frozen fwd", x && w_pw && gamma && beta && mean && var && out, x, w_dw, w_pw, gamma, beta, mean,
+                                      var, z, out, nullptr, nullptr, stream_);
 }
 
 extern "C" int ghn3_dwpw_frozen_bwd(const ghn3_dwpw_desc* g, const float* dout, const float* x, const float* z, const float* w_dw,
                                     const float* w_pw, const float* gamma, const float* mean, const float* var, float* dx, float* dw_dw,
                                     float* dw_pw, float* dgamma, float* dbeta, float* scratch, void* stream_) {
-    Desc d;
-    int rc = check_desc(g, d);
-    if (rc) return rc;
-    if (!dout || !x || !z || !w_pw || !gamma || !mean || !var || !dx || !dw_pw || !dgamma || !dbeta || !scratch || (w_dw && !dw_dw)) {
-        ghn3_set_error("dwpw frozen bwd: null pointer");
-        return GHN3_E_ARG;
-    }
-    if (!w_dw && (d.ks != 1 || d.pad != 0)) { ghn3_set_error("dwpw: without depthwise weights ks = 1, pad = 0"); return GHN3_E_ARG; }
-    hipStream_t s = (hipStream_t)stream_;
-    const Plan pl = make_plan(d);
-    float* part12 = scratch;
-    float* const s12_scratch = part12 + (int64_t)pl.n_tiles * 2 * d.C_out;
-    float* stats = s12_scratch + 2 * d.C_out;
-    float* dy = stats + 2 * d.C_out;
-    float* part_pw = dy + (int64_t)pl.P * d.C_in;
-    float* part_dw = part_pw + (int64_t)pl.pw_chunks * d.C_out * d.C_in;
-    hipLaunchKernelGGL(tnet_bn_frozen_stats_kernel, dim3((d.C_out + 255) / 256), dim3(256), 0, s, mean, var, d.eps, d.C_out, stats);
-    TNET_LAUNCH_CHECK("bn frozen stats")
-    // 1. dgamma / dbeta
-    const float* s12;
-    rc = bn_param_grads(dout, z, stats, part12, s12_scratch, dgamma, dbeta, pl.n_tiles, pl.P, d.C_out, s, &s12);
-    if (rc) return rc;
-    return dwpw_bwd_products<NORM_FROZEN>(d, pl, dout, nullptr, stats, gamma, nullptr, x, w_dw, w_pw, dx, dw_dw, dw_pw, dy, part_pw,
-                                          part_dw, s);
+    return dwpw_bwd_core<NORM_FROZEN>(g, "dwpw frozen bwd",
+                                      dout && x && z && w_pw && gamma && mean && var && dx && dw_pw && dgamma && dbeta && scratch, dout, x, z,
+                                      nullptr, w_dw, w_pw, gamma, mean, var, dx, dw_dw, dw_pw, dgamma, dbeta, scratch, stream_);
 }
 
 // ---- the depthwise stage ALONE: y = depthwise(relu(x)) -- the first of the two nodes a ReLU -> depthwise -> pointwise -> norm
@@ -1069,7 +1104,6 @@ extern "C" int ghn3_dwpw_frozen_bwd(const ghn3_dwpw_desc* g, const float* dout, 
 // dout directly: 3 launches; scratch = the weight gradient's partials.
 namespace {
 
-constexpr int DW_MAX_C = 16384;
 constexpr int DW_CS = 128;       // channels per workgroup of the forward (32 quads x 8 pixel lanes)
 constexpr int DW_PX = 32;        // output pixels per workgroup
 
@@ -1109,38 +1143,17 @@ __global__ __launch_bounds__(256) void tnet_dw_fwd_kernel(const float* __restric
     }
 }
 
-// check_desc's rules with the width limit of the stand-alone op
-int check_dw_desc(const ghn3_dwpw_desc* g, Desc& d) {
-    if (!g) { ghn3_set_error("dw: null descriptor"); return GHN3_E_ARG; }
-    d = Desc{g->N, g->H, g->W, g->C_in, g->C_out, g->ks, g->stride, g->pad, g->dil, g->Ho, g->Wo, g->eps};
-    if (d.N <= 0 || d.H <= 0 || d.W <= 0 || d.C_in <= 0 || d.C_out != d.C_in || d.ks <= 0 || d.stride <= 0 || d.dil <= 0 || d.pad < 0) {
-        ghn3_set_error("dw: non-positive size in the descriptor, or C_out != C_in");
-        return GHN3_E_ARG;
-    }
-    if ((d.C_in & 3) || d.C_in > DW_MAX_C || d.ks > 7) {
-        ghn3_set_error("dw: needs C a multiple of 4 and <= %d, ks <= 7 (got %d, ks %d)", DW_MAX_C, d.C_in, d.ks);
-        return GHN3_E_LIMIT;
-    }
-    const int ho = (d.H + 2 * d.pad - d.dil * (d.ks - 1) - 1) / d.stride + 1, wo = (d.W + 2 * d.pad - d.dil * (d.ks - 1) - 1) / d.stride + 1;
-    if (ho != d.Ho || wo != d.Wo || ho <= 0 || wo <= 0) {
-        ghn3_set_error("dw: output size %d x %d does not match the convolution arithmetic (%d x %d)", d.Ho, d.Wo, ho, wo);
-        return GHN3_E_ARG;
-    }
-    if ((int64_t)d.N * d.H * d.W * d.C_in >= ((int64_t)1 << 31) || (int64_t)d.N * d.Ho * d.Wo * d.C_in >= ((int64_t)1 << 31)) {
-        ghn3_set_error("dw: activation tensors of 2^31 elements or more are not supported");
-        return GHN3_E_LIMIT;
-    }
-    return GHN3_OK;
-}
+// check_desc with the rules of the stand-alone op
+inline int check_dw_desc(const ghn3_dwpw_desc* g, Desc& d) { return check_desc(g, d, "dw", DW_MAX_C, true); }
 
 }  // namespace
 
+// (scratch: the weight gradient's partials alone, at offset 0)
 extern "C" int64_t ghn3_dw_scratch_floats(const ghn3_dwpw_desc* g, int backward) {
     Desc d;
     const int rc = check_dw_desc(g, d);
-    if (rc) return rc;
-    if (!backward) return 0;
-    return (int64_t)make_plan(d).dw_chunks * d.ks * d.ks * d.C_in + 256;
+    if (rc) return rc;                                            // GHN3_E_ARG / GHN3_E_LIMIT
+    return backward ? part_dw_floats(d, make_plan(d)) + 256 : 0;
 }
 
 extern "C" int ghn3_dw_fwd(const ghn3_dwpw_desc* g, const float* x, const float* w_dw, float* y, void* stream_) {
@@ -1158,16 +1171,13 @@ extern "C" int ghn3_dw_fwd(const ghn3_dwpw_desc* g, const float* x, const float*
 extern "C" int ghn3_dw_bwd(const ghn3_dwpw_desc* g, const float* dout, const float* x, const float* w_dw, float* dx, float* dw_dw,
                            float* scratch, void* stream_) {
     Desc d;
-    const int rc = check_dw_desc(g, d);
+    int rc = check_dw_desc(g, d);
     if (rc) return rc;
     if (!dout || !x || !w_dw || !dx || !dw_dw || !scratch) { ghn3_set_error("dw bwd: null pointer"); return GHN3_E_ARG; }
     hipStream_t s = (hipStream_t)stream_;
-    const Plan pl = make_plan(d);
-    const int64_t total4 = (int64_t)d.N * d.H * d.W * d.C_in / 4;
-    hipLaunchKernelGGL(tnet_dw_bwd_data_kernel, dim3((int)std::min<int64_t>((total4 + 255) / 256, 8192)), dim3(256), 0, s, dout, x, w_dw, dx,
-                       d, total4);
-    TNET_LAUNCH_CHECK("dw bwd data")
-    return dw_wgrad(d, pl, dout, x, scratch, dw_dw, s);
+    rc = dw_bwd_data(d, dout, x, w_dw, dx, s);
+    if (rc) return rc;
+    return dw_wgrad(d, make_plan(d), dout, x, scratch, dw_dw, s);
 }
 
 // ---- dense convolution family: the forward / input-gradient kernel and the host side -------------------------------------------
@@ -1482,25 +1492,38 @@ inline int conv2_nt(int tiles, int cols) {
 inline size_t conv2_lds(int NT) { return 3 * TP * 4 + 2 * (3 * TP * LDK + 3 * 16 * NT * LDK) * 2; }
 
 // The scratch buffer of the conv op: where each area starts, in floats (every area a multiple of four), and the size the caller
-// allocates.  Forward: part, wp.  Backward: all of them; wp holds the transposed pack.
-struct CScratch { int64_t part, s12, wp, part_w, dz, total; };
+// allocates.  THE one description of the layout, for both members (`frozen`: behind a norm layer with frozen statistics; the
+// convolution alone, GHN3_CONV_NO_NORM, has the layout of the batch member).  Forward: part (not frozen: no statistics), wp.
+// Backward: all of them; wp holds the transposed pack; frozen: stats = (mean, rstd), behind the padded layout of the batch member.
+struct CScratch { int64_t part, s12, wp, part_w, dz, stats, total; };
 
-CScratch conv_scratch(const CDesc& d, const CPlan& pl, bool backward) {
+CScratch conv_scratch(const CDesc& d, const CPlan& pl, bool frozen, bool backward) {
     CScratch sc = {};
     int64_t at = 0;
     auto take = [&at](int64_t n) { const int64_t o = at; at += n; return o; };
-    sc.part = take((int64_t)pl.n_tiles * 2 * d.C_out);             // per tile: (mean, M2) forward, (sum dout, sum dout xhat) backward
     if (!backward) {
+        if (!frozen) sc.part = take((int64_t)pl.n_tiles * 2 * d.C_out);   // per tile: (mean, M2)
         sc.wp = take(pack_floats(pl.taps, d.C_out, d.C_in));
         sc.total = at + 64;
         return sc;
     }
+    sc.part = take((int64_t)pl.n_tiles * 2 * d.C_out);             // per tile: (sum dout, sum dout xhat)
     sc.s12 = take(2 * d.C_out);                                    // the reduced pair, when dbeta / dgamma cannot take it in place
     sc.wp = take(pack_floats(pl.taps, d.C_in, d.C_out));
     sc.part_w = take((int64_t)pl.w_chunks * pl.taps * d.C_out * d.C_in);
     sc.dz = take((int64_t)pl.P * d.C_out);
-    sc.total = at + 256;
+    take(256);
+    if (frozen) sc.stats = take(2 * d.C_out);
+    sc.total = at;
     return sc;
+}
+
+// what the two size functions answer: the GHN3_E_* code of the refusal for a descriptor the op does not take
+int64_t conv_scratch_floats(const ghn3_conv_desc* g, bool frozen, int backward) {
+    CDesc d;
+    const int rc = check_cdesc(g, d);
+    if (rc) return rc;                                            // GHN3_E_ARG / GHN3_E_LIMIT
+    return conv_scratch(d, make_cplan(d), frozen, backward != 0).total;
 }
 
 // Steps 3 and 4 of the backward, shared by every member of the family: dx by the transposed implicit GEMM and dW, both from a
@@ -1512,8 +1535,7 @@ int conv_bwd_products(const CDesc& d, const CPlan& pl, const CScratch& sc, const
     // 3. dx
     unsigned short* wp = reinterpret_cast<unsigned short*>(scratch + sc.wp);
     const int64_t plane = (int64_t)pl.taps * d.C_in * ((d.C_out + KC - 1) / KC * KC);
-    hipLaunchKernelGGL(tnet_conv_w_pack_kernel, dim3((int)std::min<int64_t>((plane + 255) / 256, 2048)), dim3(256), 0, s, w, wp, d.C_out,
-                       d.C_in, pl.taps, 1);
+    hipLaunchKernelGGL(tnet_conv_w_pack_kernel, grid1d(plane, 2048), dim3(256), 0, s, w, wp, d.C_out, d.C_in, pl.taps, 1);
     TNET_LAUNCH_CHECK("conv weight pack (transposed)")
     const int NT = conv2_nt(pl.n_tiles_in, d.C_in);
     const dim3 grid(pl.n_tiles_in, (d.C_in + 16 * NT - 1) / (16 * NT));
@@ -1528,20 +1550,73 @@ int conv_bwd_products(const CDesc& d, const CPlan& pl, const CScratch& sc, const
     hipLaunchKernelGGL(tnet_conv_wgrad_kernel, dim3(pl.w_chunks, (d.C_out + 63) / 64, ((d.C_in + 63) / 64) * pl.taps), dim3(256), 0, s, dz, x,
                        part_w, d, pl.P, pl.w_chunk_px);
     TNET_LAUNCH_CHECK("conv wgrad")
-    hipLaunchKernelGGL(tnet_reduce_rows_kernel, dim3((int)((wr / 4 + 15) / 16)), dim3(256), 0, s, part_w, pl.w_chunks, wr, dw,
-                       d.C_out * d.C_in, pl.taps);
-    TNET_LAUNCH_CHECK("conv wgrad reduce")
-    return GHN3_OK;
+    return reduce_rows(part_w, pl.w_chunks, wr, dw, d.C_out * d.C_in, pl.taps, s, "conv wgrad reduce");
+}
+
+// The forward convolution of both members: weight pack, then the implicit GEMM.  Not FROZEN: z = the convolution's result, the
+// per-tile statistics to the scratch's `part`.  FROZEN: the affine map of `fz` in the epilogue (fz.out the result, z beside it when
+// non-null), no statistics.
+template <bool FROZEN>
+int conv_fwd_launch(const CDesc& d, const CPlan& pl, const CScratch& sc, const float* x, const float* w, float* z, const Frozen& fz,
+                    float* scratch, hipStream_t s, const char* what) {
+    float* const part = FROZEN ? nullptr : scratch + sc.part;
+    unsigned short* wp = reinterpret_cast<unsigned short*>(scratch + sc.wp);
+    const int64_t plane = (int64_t)pl.taps * d.C_out * ((d.C_in + KC - 1) / KC * KC);
+    hipLaunchKernelGGL(tnet_conv_w_pack_kernel, grid1d(plane, 2048), dim3(256), 0, s, w, wp, d.C_out, d.C_in, pl.taps, 0);
+    TNET_LAUNCH_CHECK("conv weight pack")
+    const int NT = conv2_nt(pl.n_tiles, d.C_out);
+    const dim3 grid(pl.n_tiles, (d.C_out + 16 * NT - 1) / (16 * NT));
+    const size_t lds = conv2_lds(NT);
+    int rc;
+#define C2F_CASE(n) case n: rc = tnet_raise_lds(tnet_conv2_kernel<n, false, FROZEN>, lds); if (rc) return rc; \
+    hipLaunchKernelGGL((tnet_conv2_kernel<n, false, FROZEN>), grid, dim3(256), lds, s, x, wp, z, part, (const float*)nullptr, d, pl.P, pl.P_in, fz); break;
+    switch (NT) { C2F_CASE(2) C2F_CASE(4) C2F_CASE(8) }
+#undef C2F_CASE
+    return launched(what);
+}
+
+// The backward of every member.  The convolution alone (GHN3_CONV_NO_NORM, not `frozen`): dz = dout.  Batch statistics: dgamma /
+// dbeta, then dz written once for the two kernels that read it.  `frozen`: (mean, var) -> (mean, rstd) first, dz = dout gamma rstd.
+// `required` = none of the pointers every member needs is null, `norm_required` = nor of those of the norm layer.
+int conv_bwd_core(const ghn3_conv_desc* g, bool frozen, const char* who, bool required, bool norm_required, const float* dout, const float* x,
+                  const float* z, const float* stats, const float* w, const float* gamma, const float* mean, const float* var, float* dx,
+                  float* dw, float* dgamma, float* dbeta, float* scratch, void* stream_) {
+    CDesc d;
+    int rc = check_cdesc(g, d);
+    if (rc) return rc;
+    const bool no_norm = (g->relu & GHN3_CONV_NO_NORM) != 0;       // dout IS the gradient of the convolution's result
+    if (frozen && no_norm) { ghn3_set_error("conv frozen: GHN3_CONV_NO_NORM has no meaning here"); return GHN3_E_ARG; }
+    if (!required || (!no_norm && !norm_required)) { ghn3_set_error("%s: null pointer", who); return GHN3_E_ARG; }
+    hipStream_t s = (hipStream_t)stream_;
+    const CPlan pl = make_cplan(d);
+    const CScratch sc = conv_scratch(d, pl, frozen, true);
+    if (no_norm) return conv_bwd_products(d, pl, sc, dout, x, w, dx, dw, scratch, s);
+    if (frozen) {
+        rc = frozen_stats(mean, var, d.eps, d.C_out, scratch + sc.stats, s);
+        if (rc) return rc;
+        stats = scratch + sc.stats;
+    }
+    // 1. dgamma / dbeta
+    const float* s12;
+    rc = bn_param_grads(dout, z, stats, scratch + sc.part, scratch + sc.s12, dgamma, dbeta, pl.n_tiles, pl.P, d.C_out, s, &s12);
+    if (rc) return rc;
+    // 2. dz [P][C_out], written once for the two kernels that read it (frozen: dout gamma rstd, which reads neither z nor the pair)
+    const int64_t total4 = (int64_t)pl.P * d.C_out / 4;
+    float* const dz = scratch + sc.dz;
+    if (frozen) {
+        hipLaunchKernelGGL(tnet_dz_kernel<false>, grid1d(total4, 4096), dim3(256), 0, s, dout, (const float*)nullptr, stats, gamma,
+                           (const float*)nullptr, dz, total4, d.C_out, pl.P);
+        TNET_LAUNCH_CHECK("conv frozen bwd dz")
+    } else {
+        hipLaunchKernelGGL(tnet_dz_kernel<true>, grid1d(total4, 4096), dim3(256), 0, s, dout, z, stats, gamma, s12, dz, total4, d.C_out, pl.P);
+        TNET_LAUNCH_CHECK("conv bwd dz")
+    }
+    return conv_bwd_products(d, pl, sc, dz, x, w, dx, dw, scratch, s);
 }
 
 }  // namespace
 
-extern "C" int64_t ghn3_conv_scratch_floats(const ghn3_conv_desc* g, int backward) {
-    CDesc d;
-    const int rc = check_cdesc(g, d);
-    if (rc) return rc;                                            // GHN3_E_ARG / GHN3_E_LIMIT
-    return conv_scratch(d, make_cplan(d), backward != 0).total;
-}
+extern "C" int64_t ghn3_conv_scratch_floats(const ghn3_conv_desc* g, int backward) { return conv_scratch_floats(g, false, backward); }
 
 extern "C" int ghn3_conv_bn_fwd(const ghn3_conv_desc* g, const float* x, const float* w, const float* gamma, const float* beta, float* z,
                                 float* out, float* stats, float* scratch, void* stream_) {
@@ -1555,59 +1630,17 @@ extern "C" int ghn3_conv_bn_fwd(const ghn3_conv_desc* g, const float* x, const f
     }
     hipStream_t s = (hipStream_t)stream_;
     const CPlan pl = make_cplan(d);
-    const CScratch sc = conv_scratch(d, pl, false);
-    float* part = scratch + sc.part;
-    unsigned short* wp = reinterpret_cast<unsigned short*>(scratch + sc.wp);
-    const int64_t plane = (int64_t)pl.taps * d.C_out * ((d.C_in + KC - 1) / KC * KC);
-    hipLaunchKernelGGL(tnet_conv_w_pack_kernel, dim3((int)std::min<int64_t>((plane + 255) / 256, 2048)), dim3(256), 0, s, w, wp, d.C_out,
-                       d.C_in, pl.taps, 0);
-    TNET_LAUNCH_CHECK("conv weight pack")
-    const int NT = conv2_nt(pl.n_tiles, d.C_out);
-    const dim3 grid(pl.n_tiles, (d.C_out + 16 * NT - 1) / (16 * NT));
-    const size_t lds = conv2_lds(NT);
-#define C2F_CASE(n) case n: rc = tnet_raise_lds(tnet_conv2_kernel<n, false>, lds); if (rc) return rc; \
-    hipLaunchKernelGGL((tnet_conv2_kernel<n, false>), grid, dim3(256), lds, s, x, wp, z, part, (const float*)nullptr, d, pl.P, pl.P_in, Frozen{}); break;
-    switch (NT) { C2F_CASE(2) C2F_CASE(4) C2F_CASE(8) }
-#undef C2F_CASE
-    TNET_LAUNCH_CHECK("conv fwd")
-    if (no_norm) return GHN3_OK;
-    hipLaunchKernelGGL(tnet_bn_finalize_kernel, dim3((d.C_out + 15) / 16), dim3(256), 0, s, part, pl.n_tiles, pl.P, d.C_out, d.eps, stats);
-    TNET_LAUNCH_CHECK("bn finalize")
-    const int64_t total4 = (int64_t)pl.P * d.C_out / 4;
-    hipLaunchKernelGGL(tnet_bn_apply_kernel, dim3((int)std::min<int64_t>((total4 + 255) / 256, 4096)), dim3(256), 0, s, z, stats, gamma,
-                       beta, out, total4, d.C_out);
-    TNET_LAUNCH_CHECK("bn apply")
-    return GHN3_OK;
+    const CScratch sc = conv_scratch(d, pl, false, false);
+    rc = conv_fwd_launch<false>(d, pl, sc, x, w, z, Frozen{}, scratch, s, "conv fwd");
+    if (rc || no_norm) return rc;
+    return bn_apply_launch(scratch + sc.part, pl.n_tiles, pl.P, d.C_out, d.eps, z, gamma, beta, stats, out, s);
 }
 
 extern "C" int ghn3_conv_bn_bwd(const ghn3_conv_desc* g, const float* dout, const float* x, const float* z, const float* stats,
                                 const float* w, const float* gamma, float* dx, float* dw, float* dgamma, float* dbeta, float* scratch,
                                 void* stream_) {
-    CDesc d;
-    int rc = check_cdesc(g, d);
-    if (rc) return rc;
-    const bool no_norm = (g->relu & GHN3_CONV_NO_NORM) != 0;       // dout IS the gradient of the convolution's result
-    if (!dout || !x || !w || !dx || !dw || !scratch || (!no_norm && (!z || !stats || !gamma || !dgamma || !dbeta))) {
-        ghn3_set_error("conv bwd: null pointer");
-        return GHN3_E_ARG;
-    }
-    hipStream_t s = (hipStream_t)stream_;
-    const CPlan pl = make_cplan(d);
-    const CScratch sc = conv_scratch(d, pl, true);
-    const float* dz = dout;
-    if (!no_norm) {
-        // 1. dgamma / dbeta
-        const float* s12;
-        rc = bn_param_grads(dout, z, stats, scratch + sc.part, scratch + sc.s12, dgamma, dbeta, pl.n_tiles, pl.P, d.C_out, s, &s12);
-        if (rc) return rc;
-        // 2. dz [P][C_out], written once for the two kernels that read it
-        const int64_t total4 = (int64_t)pl.P * d.C_out / 4;
-        hipLaunchKernelGGL(tnet_dz_kernel<true>, dim3((int)std::min<int64_t>((total4 + 255) / 256, 4096)), dim3(256), 0, s, dout, z, stats,
-                           gamma, s12, scratch + sc.dz, total4, d.C_out, pl.P);
-        TNET_LAUNCH_CHECK("conv bwd dz")
-        dz = scratch + sc.dz;
-    }
-    return conv_bwd_products(d, pl, sc, dz, x, w, dx, dw, scratch, s);
+    return conv_bwd_core(g, false, "conv bwd", dout && x && w && dx && dw && scratch, z && stats && gamma && dgamma && dbeta, dout, x, z, stats,
+                         w, gamma, nullptr, nullptr, dx, dw, dgamma, dbeta, scratch, stream_);
 }
 
 // ---- the same family behind a norm layer with FROZEN statistics (a BatchNorm in eval mode; see ghn3_dwpw_frozen_fwd) ------------
@@ -1615,14 +1648,7 @@ extern "C" int ghn3_conv_bn_bwd(const ghn3_conv_desc* g, const float* dout, cons
 // caller wants a backward.  Backward: (mean, var) -> (mean, rstd), dgamma / dbeta as with batch statistics, dz = dout gamma rstd
 // written once (tnet_dz_kernel<false>: the two kernels that read it take a plain buffer), then dx and dW unchanged.
 // Scratch: forward = the weight pack; backward = that of ghn3_conv_bn_bwd followed by the (mean, rstd) pair.
-extern "C" int64_t ghn3_conv_frozen_scratch_floats(const ghn3_conv_desc* g, int backward) {
-    CDesc d;
-    const int rc = check_cdesc(g, d);
-    if (rc) return rc;
-    const CPlan pl = make_cplan(d);
-    if (!backward) return pack_floats(pl.taps, d.C_out, d.C_in) + 64;
-    return conv_scratch(d, pl, true).total + 2 * d.C_out;
-}
+extern "C" int64_t ghn3_conv_frozen_scratch_floats(const ghn3_conv_desc* g, int backward) { return conv_scratch_floats(g, true, backward); }
 
 extern "C" int ghn3_conv_frozen_fwd(const ghn3_conv_desc* g, const float* x, const float* w, const float* gamma, const float* beta,
                                     const float* mean, const float* var, float* z, float* out, float* scratch, void* stream_) {
@@ -1631,52 +1657,16 @@ extern "C" int ghn3_conv_frozen_fwd(const ghn3_conv_desc* g, const float* x, con
     if (rc) return rc;
     if (g->relu & GHN3_CONV_NO_NORM) { ghn3_set_error("conv frozen: GHN3_CONV_NO_NORM has no meaning here"); return GHN3_E_ARG; }
     if (!x || !w || !gamma || !beta || !mean || !var || !out || !scratch) { ghn3_set_error("conv frozen fwd: null pointer"); return GHN3_E_ARG; }
-    hipStream_t s = (hipStream_t)stream_;
     const CPlan pl = make_cplan(d);
-    unsigned short* wp = reinterpret_cast<unsigned short*>(scratch);
-    const int64_t plane = (int64_t)pl.taps * d.C_out * ((d.C_in + KC - 1) / KC * KC);
-    hipLaunchKernelGGL(tnet_conv_w_pack_kernel, dim3((int)std::min<int64_t>((plane + 255) / 256, 2048)), dim3(256), 0, s, w, wp, d.C_out,
-                       d.C_in, pl.taps, 0);
-    TNET_LAUNCH_CHECK("conv weight pack")
-    const int NT = conv2_nt(pl.n_tiles, d.C_out);
-    const dim3 grid(pl.n_tiles, (d.C_out + 16 * NT - 1) / (16 * NT));
-    const size_t lds = conv2_lds(NT);
-    const Frozen fz = {gamma, beta, mean, var, out};
-#define C2F_CASE(n) case n: rc = tnet_raise_lds(tnet_conv2_kernel<n, false, true>, lds); if (rc) return rc; \
-    hipLaunchKernelGGL((tnet_conv2_kernel<n, false, true>), grid, dim3(256), lds, s, x, wp, z, (float*)nullptr, (const float*)nullptr, d, pl.P, pl.P_in, fz); break;
-    switch (NT) { C2F_CASE(2) C2F_CASE(4) C2F_CASE(8) }
-#undef C2F_CASE
-    TNET_LAUNCH_CHECK("conv frozen fwd")
-    return GHN3_OK;
+    return conv_fwd_launch<true>(d, pl, conv_scratch(d, pl, true, false), x, w, z, Frozen{gamma, beta, mean, var, out}, scratch,
+                                 (hipStream_t)stream_, "conv frozen fwd");
 }
 
 extern "C" int ghn3_conv_frozen_bwd(const ghn3_conv_desc* g, const float* dout, const float* x, const float* z, const float* w,
                                     const float* gamma, const float* mean, const float* var, float* dx, float* dw, float* dgamma,
                                     float* dbeta, float* scratch, void* stream_) {
-    CDesc d;
-    int rc = check_cdesc(g, d);
-    if (rc) return rc;
-    if (g->relu & GHN3_CONV_NO_NORM) { ghn3_set_error("conv frozen: GHN3_CONV_NO_NORM has no meaning here"); return GHN3_E_ARG; }
-    if (!dout || !x || !z || !w || !gamma || !mean || !var || !dx || !dw || !dgamma || !dbeta || !scratch) {
-        ghn3_set_error("conv frozen bwd: null pointer");
-        return GHN3_E_ARG;
-    }
-    hipStream_t s = (hipStream_t)stream_;
-    const CPlan pl = make_cplan(d);
-    const CScratch sc = conv_scratch(d, pl, true);
-    float* stats = scratch + sc.total;
-    hipLaunchKernelGGL(tnet_bn_frozen_stats_kernel, dim3((d.C_out + 255) / 256), dim3(256), 0, s, mean, var, d.eps, d.C_out, stats);
-    TNET_LAUNCH_CHECK("bn frozen stats")
-    // 1. dgamma / dbeta
-    const float* s12;
-    rc = bn_param_grads(dout, z, stats, scratch + sc.part, scratch + sc.s12, dgamma, dbeta, pl.n_tiles, pl.P, d.C_out, s, &s12);
-    if (rc) return rc;
-    // 2. dz [P][C_out] = dout gamma rstd
-    const int64_t total4 = (int64_t)pl.P * d.C_out / 4;
-    hipLaunchKernelGGL(tnet_dz_kernel<false>, dim3((int)std::min<int64_t>((total4 + 255) / 256, 4096)), dim3(256), 0, s, dout,
-                       (const float*)nullptr, stats, gamma, (const float*)nullptr, scratch + sc.dz, total4, d.C_out, pl.P);
-    TNET_LAUNCH_CHECK("conv frozen bwd dz")
-    return conv_bwd_products(d, pl, sc, scratch + sc.dz, x, w, dx, dw, scratch, s);
+    return conv_bwd_core(g, true, "conv frozen bwd", dout && x && w && dx && dw && scratch, z && gamma && mean && var && dgamma && dbeta, dout,
+                         x, z, nullptr, w, gamma, mean, var, dx, dw, dgamma, dbeta, scratch, stream_);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -548,12 +548,15 @@ int ghn3_profile_read_tags(ghn3_ctx* ctx, double* ms_per_tag /* [256] */, int64_
  * `scratch` = ghn3_dwpw_scratch_floats(desc, backward) floats of device memory owned by the caller (no allocation, no
  * synchronisation inside).  Limits: C_in, C_out multiples of 4 and <= 512, ks <= 7, tensors below 2^31 elements
  * (GHN3_E_LIMIT otherwise: the caller keeps its stock path for such layers).  Deterministic.
+ * ghn3_dwpw_scratch_floats, ghn3_dwpw_plain_scratch_floats and ghn3_dwpw_frozen_scratch_floats answer -1 for EVERY descriptor
+ * the op refuses, whether the entry points would answer GHN3_E_ARG or GHN3_E_LIMIT (the reason is in ghn3_last_error);
+ * ghn3_dw_scratch_floats and the size functions of the dense-convolution family answer the GHN3_E_* code itself.
  */
 typedef struct ghn3_dwpw_desc {
     int32_t N, H, W, C_in, C_out, ks, stride, pad, dil, Ho, Wo;
     float eps;
 } ghn3_dwpw_desc;
-int64_t ghn3_dwpw_scratch_floats(const ghn3_dwpw_desc* desc, int backward);     /* < 0: bad descriptor (ghn3_last_error) */
+int64_t ghn3_dwpw_scratch_floats(const ghn3_dwpw_desc* desc, int backward);     /* -1: descriptor refused (ghn3_last_error) */
 int ghn3_dwpw_bn_fwd(const ghn3_dwpw_desc* desc, const float* x, const float* w_dw, const float* w_pw, const float* gamma,
                      const float* beta, float* z, float* out, float* stats, float* scratch, void* stream);
 int ghn3_dwpw_bn_bwd(const ghn3_dwpw_desc* desc, const float* dout, const float* x, const float* z, const float* stats,

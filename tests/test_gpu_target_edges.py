@@ -339,3 +339,56 @@ def test_pooling_edge_rows_with_ties(row, mode, buffers):
         _measure('pool', 'out', out, ref, E.ACT_AXES, POOL_TOL, worst)
     _measure('pool', 'dx', dx, ref_dx, E.ACT_AXES, POOL_TOL, worst)
     _report('max_pool' if mode else 'avg_pool', row, worst)
+
+
+# ---- the backward's reduced (sum dout, sum dout xhat) pair when dgamma does not follow dbeta -------------------------------------
+# target_ops.py always lays dgamma directly behind dbeta, where the C side reduces the pair in place; any other caller gets it
+# reduced into the scratch's s12 area and copied out.  Both ways must give the same bits: same kernels, same order.
+APART_SHAPES = [(2, 9, 7, 2), (3, 9, 9, 1)]        # (N, H, W, stride), 8 -> 12 channels, 3 x 3, pad 1: P = 40 (one partial
+#                                                     tile) and 243 (four tiles, the last partial)
+
+
+@pytest.mark.parametrize('shape', APART_SHAPES, ids=str)
+@pytest.mark.parametrize('fn', ['ghn3_dwpw_bn_bwd', 'ghn3_dwpw_frozen_bwd', 'ghn3_conv_bn_bwd', 'ghn3_conv_frozen_bwd'])
+def test_backward_with_dgamma_apart_from_dbeta(fn, shape):
+    import ctypes
+    from ghn3_amd import _lib as L, target_ops as T
+    (N, H, W, st), Ci, Co, ks, pad = shape, 8, 12, 3, 1
+    Ho, Wo = (H + 2 * pad - ks) // st + 1, (W + 2 * pad - ks) // st + 1
+    P = N * Ho * Wo
+    dwpw, frozen = fn.startswith('ghn3_dwpw'), '_frozen_' in fn
+    lib = L.load()
+    if dwpw:
+        d = T._Desc(N, H, W, Ci, Co, ks, st, pad, 1, Ho, Wo, 1e-5)
+    else:
+        d = T._ConvDesc(N, H, W, Ci, Co, ks, ks, st, st, pad, pad, 1, Ho, Wo, 1, 1e-5)
+    size = getattr(lib, fn.replace('_bn_bwd', '_scratch_floats').replace('_bwd', '_scratch_floats'))
+    n_scratch = int(size(ctypes.byref(d), 1))
+    assert n_scratch > 0
+    g = torch.Generator().manual_seed(P)
+    rnd = lambda *s: torch.randn(*s, generator=g).cuda()
+    dout, x, z, gamma = rnd(P, Co), rnd(N, H, W, Ci), rnd(P, Co), rnd(Co)
+    weights = [rnd(Ci, ks, ks), rnd(Co, Ci)] if dwpw else [rnd(Co, Ci, ks, ks)]
+    mean, var = z.mean(0), z.var(0, unbiased=False)
+    stats = torch.cat([mean, (var + 1e-5).rsqrt(), var])
+    norm_in = [mean, var] if frozen else []
+    runs = []
+    for apart in (False, True):
+        nan = lambda *s: torch.full(s, float('nan'), device='cuda')
+        dx, grads, scratch = nan(N, H, W, Ci), [nan(*w.shape) for w in weights], nan(n_scratch)
+        if apart:
+            dgamma, dbeta = nan(Co), nan(Co)
+        else:
+            pair = nan(2 * Co)
+            dbeta, dgamma = pair[:Co], pair[Co:]
+        assert (dgamma.data_ptr() == dbeta.data_ptr() + 4 * Co) != apart
+        if frozen:
+            args = [dout, x, z] + weights + [gamma] + norm_in
+        else:
+            args = [dout, x, z, stats] + weights + [gamma]
+        args += [dx] + grads + [dgamma, dbeta, scratch]
+        L._check(getattr(lib, fn)(ctypes.byref(d), *[t.data_ptr() for t in args], T._stream()), fn)
+        torch.cuda.synchronize()
+        runs.append([t.cpu() for t in [dx] + grads + [dgamma, dbeta]])
+    for a, b in zip(*runs):
+        assert torch.isfinite(a).all() and torch.equal(a, b)
