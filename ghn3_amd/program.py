@@ -75,6 +75,60 @@ class _Backward:
         self.i_dgrad = self.i_late0 = self.i_late1 = self.d_up = None
 
 
+def tile_work_tables(descs):
+    """Tile descriptors (dst_off, src_off, S, T, E, R, src_buf, mode, scale) -> (descriptor array with `_pad` = input channels
+    per row block (0: element blocks), forward work blocks, backward work blocks, first forward block of every descriptor,
+    [forward, backward] LDS bytes of the row blocks).  A work-block table holds (descriptor id or ~id, word) rows, see
+    `tables` below.  Built column-wise (one numpy call per field, not per descriptor)."""
+    nd = len(descs)
+    CH = 2048
+    tile_lds = [0, 0]
+    desc_arr = np.zeros(max(nd, 1), dtype=L.TILE_DT)
+    fb = bb = np.zeros((0, 2), dtype=np.int64)
+    fwd_first = np.zeros(0, dtype=np.int64)
+    if nd:
+        cols = list(zip(*descs))
+        desc_arr['dst_off'], desc_arr['src_off'] = cols[0], cols[1]
+        S = np.asarray(cols[2], dtype=np.int64).reshape(nd, 4)
+        T = np.asarray(cols[3], dtype=np.int64).reshape(nd, 4)
+        E = np.asarray(cols[4], dtype=np.int64).reshape(nd, 4)
+        R = np.asarray(cols[5], dtype=np.int64).reshape(nd, 4)
+        desc_arr['S'], desc_arr['T'], desc_arr['E'], desc_arr['R'] = S, T, E, R
+        desc_arr['src_buf'], desc_arr['mode'], desc_arr['scale'] = cols[6], cols[7], cols[8]
+        mode = np.asarray(cols[7], dtype=np.int64)
+        hw = T[:, 2] * T[:, 3]
+        # convolution kernels with kh * kw > 1: LDS-transposed row blocks (see tile_fwd_kernel), one per o and
+        # chunk of `ich` input channels (<= 16 KB of LDS, so that many blocks share a CU)
+        row_ok = (mode == 0) & (hw > 1) & (S[:, 1] == 1) & (E[:, 2] == T[:, 2]) & (T[:, 2] == R[:, 2]) & \
+            (E[:, 3] == T[:, 3]) & (T[:, 3] == R[:, 3]) & (hw <= 1024)
+        # (a multiple of 16 channels unless the tensor has fewer: the row blocks move 16 bytes per lane when the chunk is
+        # a multiple of 4 floats)
+        ich = np.maximum(16, np.minimum(np.maximum(T[:, 1], R[:, 1]), (4096 // np.maximum(hw, 1)) // 16 * 16))
+        desc_arr['_pad'] = np.where(row_ok, ich, 0)
+        if row_ok.any():
+            lds = int((4 * ich * hw)[row_ok].max())
+            tile_lds = [lds, lds]
+        ids = np.arange(nd, dtype=np.int64)
+
+        def tables(n0, n1, numel):
+            """(descriptor id or ~id, start / packed (o, first i)) rows: element blocks of CH elements, row blocks
+            of one o and `ich` input channels; descriptors in order, blocks of a descriptor in order."""
+            n_i = (n1 + ich - 1) // ich                                   # i chunks per o (row blocks)
+            cnt = np.where(row_ok, n0 * n_i, (numel + CH - 1) // CH)
+            total = int(cnt.sum())
+            first = np.cumsum(cnt) - cnt
+            d_of = np.repeat(ids, cnt)
+            j = np.arange(total, dtype=np.int64) - np.repeat(first, cnt)     # block index inside its descriptor
+            rb = row_ok[d_of]
+            ni_b = np.maximum(n_i[d_of], 1)
+            word = np.where(rb, (j // ni_b) | (((j % ni_b) * ich[d_of]) << 24), j * CH)
+            return np.stack([np.where(rb, ~d_of, d_of), word], axis=1), first
+
+        fb, fwd_first = tables(T[:, 0], T[:, 1], T.prod(axis=1))
+        bb, _ = tables(R[:, 0], R[:, 1], R.prod(axis=1))
+    return desc_arr, fb, bb, fwd_first, tile_lds
+
+
 class Program:
     """See module docstring.  cfg: dict(hid, heads, layers, num_classes, max_shape)."""
 
@@ -1517,51 +1571,8 @@ class Program:
         self.out_numel = max(out_off, 16)
         self.tok_floats = max(tok_off, 4)
         self.n_desc = nd = len(descs)
-        CH = 2048
-        self.tile_lds = [0, 0]
-        # descriptor table and work-block tables, built column-wise (one numpy call per field, not per descriptor)
-        desc_arr = np.zeros(max(nd, 1), dtype=L.TILE_DT)
-        fb = bb = np.zeros((0, 2), dtype=np.int64)
-        if nd:
-            cols = list(zip(*descs))
-            desc_arr['dst_off'], desc_arr['src_off'] = cols[0], cols[1]
-            S = np.asarray(cols[2], dtype=np.int64).reshape(nd, 4)
-            T = np.asarray(cols[3], dtype=np.int64).reshape(nd, 4)
-            E = np.asarray(cols[4], dtype=np.int64).reshape(nd, 4)
-            R = np.asarray(cols[5], dtype=np.int64).reshape(nd, 4)
-            desc_arr['S'], desc_arr['T'], desc_arr['E'], desc_arr['R'] = S, T, E, R
-            desc_arr['src_buf'], desc_arr['mode'], desc_arr['scale'] = cols[6], cols[7], cols[8]
-            mode = np.asarray(cols[7], dtype=np.int64)
-            hw = T[:, 2] * T[:, 3]
-            # convolution kernels with kh * kw > 1: LDS-transposed row blocks (see tile_fwd_kernel), one per o and
-            # chunk of `ich` input channels (<= 16 KB of LDS, so that many blocks share a CU)
-            row_ok = (mode == 0) & (hw > 1) & (S[:, 1] == 1) & (E[:, 2] == T[:, 2]) & (T[:, 2] == R[:, 2]) & \
-                (E[:, 3] == T[:, 3]) & (T[:, 3] == R[:, 3]) & (hw <= 1024)
-            # (a multiple of 16 channels unless the tensor has fewer: the row blocks move 16 bytes per lane when the chunk is
-            # a multiple of 4 floats)
-            ich = np.maximum(16, np.minimum(np.maximum(T[:, 1], R[:, 1]), (4096 // np.maximum(hw, 1)) // 16 * 16))
-            desc_arr['_pad'] = np.where(row_ok, ich, 0)
-            if row_ok.any():
-                lds = int((4 * ich * hw)[row_ok].max())
-                self.tile_lds = [lds, lds]
-            ids = np.arange(nd, dtype=np.int64)
-
-            def tables(n0, n1, numel):
-                """(descriptor id or ~id, start / packed (o, first i)) rows: element blocks of CH elements, row blocks
-                of one o and `ich` input channels; descriptors in order, blocks of a descriptor in order."""
-                n_i = (n1 + ich - 1) // ich                                   # i chunks per o (row blocks)
-                cnt = np.where(row_ok, n0 * n_i, (numel + CH - 1) // CH)
-                total = int(cnt.sum())
-                first = np.cumsum(cnt) - cnt
-                d_of = np.repeat(ids, cnt)
-                j = np.arange(total, dtype=np.int64) - np.repeat(first, cnt)     # block index inside its descriptor
-                rb = row_ok[d_of]
-                ni_b = np.maximum(n_i[d_of], 1)
-                word = np.where(rb, (j // ni_b) | (((j % ni_b) * ich[d_of]) << 24), j * CH)
-                return np.stack([np.where(rb, ~d_of, d_of), word], axis=1), first
-
-            fb, fwd_first = tables(T[:, 0], T[:, 1], T.prod(axis=1))
-            bb, _ = tables(R[:, 0], R[:, 1], R.prod(axis=1))
+        # descriptor table and work-block tables
+        desc_arr, fb, bb, fwd_first, self.tile_lds = tile_work_tables(descs)
         dseg = np.asarray(desc_seg if nd else [0], dtype=np.int32)
         raw = np.concatenate([desc_arr.view(np.uint8).reshape(-1), fb.view(np.uint8).reshape(-1),
                               bb.view(np.uint8).reshape(-1), dseg.view(np.uint8).reshape(-1)])

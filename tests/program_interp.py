@@ -679,16 +679,25 @@ class Interp:
             n = int(np.prod(T))
             val = self._norm(v, int(D['mode']), float(D['scale']))
             flat[int(D['dst_off']):int(D['dst_off']) + n] = val
-            if parts is not None:                       # r8: per-work-block sums of squares (here: all in the first block)
-                blk = np.nonzero(desc_of_block == kd)[0]
-                parts[blk] = 0.0
-                parts[blk[0]] = np.float32((val.astype(np.float32).astype(np.float64) ** 2).sum())
-                if bparts is not None:                  # r9: max |value| * replicas * |scale| (mode 0, source 0)
-                    bparts[blk] = 0.0
-                    if int(D['src_buf']) == 0 and int(D['mode']) == 0 and val.size:
-                        reps = np.prod((T + E - 1) // E)
-                        bparts[blk[0]] = np.float32(np.abs(val.astype(np.float32)).max()) * np.float32(abs(float(D['scale']))) * \
-                            np.float32(reps)
+            if parts is not None:
+                # r8: slot k = sum of squares of what work block k wrote -- a contiguous range of the descriptor's target:
+                # CHUNK elements from `word` (element blocks), or the `_pad` input channels from i0 = word >> 24 of
+                # row a0 = word & 0xffffff (row blocks);  r9: max |value| * replicas * |scale| (mode 0, source 0; else 0)
+                v32 = val.astype(np.float32)
+                hw = int(T[2] * T[3])
+                bound_desc = int(D['src_buf']) == 0 and int(D['mode']) == 0
+                f = np.float32(abs(float(D['scale']))) * np.float32(np.prod((T + E - 1) // E))
+                for k in np.nonzero(desc_of_block == kd)[0]:
+                    word = int(tab[k, 1])
+                    if tab[k, 0] < 0:
+                        a0, i0 = word & 0xffffff, word >> 24
+                        lo = (a0 * int(T[1]) + i0) * hw
+                        hi = lo + min(int(D['_pad']), int(T[1]) - i0) * hw
+                    else:
+                        lo, hi = word, min(word + 2048, n)
+                    parts[k] = np.float32((v32[lo:hi].astype(np.float64) ** 2).sum())
+                    if bparts is not None:
+                        bparts[k] = np.float32(np.abs(v32[lo:hi]).max()) * f if (bound_desc and hi > lo) else 0.0
             kd += 1
 
     def op_tile_bwd(self, o, problems):
@@ -794,8 +803,8 @@ class Interp:
         assert int(o['i'][1]) >= seg[-1, 1] and np.all(seg[1:, 0] >= seg[:-1, 1]), 'sorted disjoint segments + extent'
         norms = self.fview(o['r'][3], n)
         for s in range(n):
-            k = float(o['f'][0]) / norms[s] if norms[s] > 0 else 0.0
-            dflat[seg[s, 0]:seg[s, 1]] = flat[seg[s, 0]:seg[s, 1]] * k
+            k = float(o['f'][0]) / float(norms[s]) if norms[s] > 0 else 0.0          # (float64: a numpy float32 scalar would keep the product in float32)
+            dflat[seg[s, 0]:seg[s, 1]] = flat[seg[s, 0]:seg[s, 1]].astype(np.float64) * k
 
     def op_colsum(self, o, problems):
         M, N, ld, q, s, stride, accum = (int(v) for v in o['i'][:7])
