@@ -80,7 +80,8 @@ EXPORTS = ['ghn3_abi_version', 'ghn3_last_error', 'ghn3_ctx_create', 'ghn3_ctx_d
            'ghn3_msa_scratch_floats', 'ghn3_msa_fwd', 'ghn3_msa_bwd', 'ghn3_head_scratch_floats', 'ghn3_head_fwd',
            'ghn3_head_bwd', 'ghn3_xent_fwd', 'ghn3_xent_bwd', 'ghn3_join_fwd', 'ghn3_join_bwd', 'ghn3_posenc_bwd',
            'ghn3_attn_lean_fwd', 'ghn3_attn_lean_bwd', 'ghn3_msa_lean_scratch_floats', 'ghn3_msa_lean_fwd', 'ghn3_msa_lean_bwd',
-           'ghn3_dw_scratch_floats', 'ghn3_dw_fwd', 'ghn3_dw_bwd', 'ghn3_patch_scratch_floats', 'ghn3_patch_fwd', 'ghn3_patch_bwd']
+           'ghn3_dw_scratch_floats', 'ghn3_dw_fwd', 'ghn3_dw_bwd', 'ghn3_patch_scratch_floats', 'ghn3_patch_fwd', 'ghn3_patch_bwd',
+           'ghn3_attn_wide_fwd', 'ghn3_attn_wide_bwd', 'ghn3_msa_wide_scratch_floats', 'ghn3_msa_wide_fwd', 'ghn3_msa_wide_bwd']
 OPFLAG_TIMED = 0x100
 OPFLAG_SIDE = 0x200
 
@@ -165,6 +166,12 @@ def load():
         lib.ghn3_msa_lean_scratch_floats.restype = ctypes.c_int64
         lib.ghn3_msa_lean_fwd.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int, ctypes.c_void_p]
         lib.ghn3_msa_lean_bwd.argtypes = [ctypes.c_void_p] * 9
+        lib.ghn3_attn_wide_fwd.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 4 + [ctypes.c_void_p]
+        lib.ghn3_attn_wide_bwd.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int] * 4 + [ctypes.c_void_p]
+        lib.ghn3_msa_wide_scratch_floats.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        lib.ghn3_msa_wide_scratch_floats.restype = ctypes.c_int64
+        lib.ghn3_msa_wide_fwd.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int, ctypes.c_void_p]
+        lib.ghn3_msa_wide_bwd.argtypes = [ctypes.c_void_p] * 9
         lib.ghn3_head_scratch_floats.argtypes = [ctypes.c_void_p, ctypes.c_int]
         lib.ghn3_head_scratch_floats.restype = ctypes.c_int64
         lib.ghn3_head_fwd.argtypes = [ctypes.c_void_p] * 6

@@ -36,7 +36,9 @@ preprocessing layer): the fused depthwise + pointwise kernels keep all output co
 ReLU + depthwise taps alone, C <= 16384) and the 1 x 1 member of the dense-convolution family that fits the norm slot (``ConvBn``,
 ``ConvOnly``, ``ConvBnEval`` with relu=False), which takes C_out <= 4096 and C_in <= 16384; ``SqueezeExcite`` takes C, J <= 4096.
 GHN3_NATIVE_WIDE=0 keeps every layer above the former limits (512 / 4096 -> 512 / 1024) on the stock layers.  The ``msa`` layers
-keep their limits (C <= 256, head dim <= 32): a wide ViT-style network runs them on the stock path.
+of ``MsaLayer`` keep their limits (C <= 256, head dim <= 32, hidden <= 1024); above them, up to C <= 1024, head dim <= 64 and
+hidden <= 4096, ``MsaWideLayer`` (ghn3_msa_wide_*, ghn3_amd/csrc/tnet_msa_wide.hip) takes the layer when GHN3_NATIVE_MSA_WIDE=1
+-- opt-in: by default a wide ViT-style network still runs its msa layers on the stock path.
 
 The patch embedding of the ViT-style networks (``run_conv_layer``): 3 x 3 / stride 3 on CIFAR-sized inputs runs on ``ConvOnly``;
 16 x 16 / stride 16 on ImageNet-sized inputs -- a kernel the dense-convolution op refuses -- on ``PatchEmbed`` / ``patch_embed``
@@ -1178,6 +1180,85 @@ def lean_attention(qkv, heads):
     return LeanAttention.apply(qkv, int(heads))
 
 
+class WideAttention(torch.autograd.Function):
+    """`LeanAttention` for head dims up to 64, on ghn3_attn_wide_fwd / _bwd (ghn3_amd/csrc/tnet_msa_wide.hip): the same qkv
+    (B, N, 3 C) -> (B, N, C), one saved float per query row, the probabilities recomputed in the backward.  d <= 32 runs the
+    kernels of `LeanAttention` (bit-equal results).  fp32 CUDA tensors, C % 4 == 0, d = C / heads <= 64, N <= 4096."""
+
+    @staticmethod
+    def forward(ctx, qkv, heads):
+        if not (_f32_cuda(qkv) and qkv.dim() == 3 and qkv.shape[2] % 3 == 0):
+            raise L.Ghn3Error('wide_attention takes a float32 CUDA tensor (B, N, 3 C); there is no other implementation')
+        lib = L.load()
+        q = _aligned(qkv.contiguous())
+        B, N, C = q.shape[0], q.shape[1], q.shape[2] // 3
+        out = torch.empty((B, N, C), dtype=torch.float32, device=q.device)
+        lse = torch.empty((B, heads, N), dtype=torch.float32, device=q.device) if ctx.needs_input_grad[0] else None
+        L._check(lib.ghn3_attn_wide_fwd(_ptr(out), _ptr(lse), _ptr(q), B, N, C, heads, _stream()),
+                 'ghn3_attn_wide_fwd')
+        if lse is not None:
+            ctx.save_for_backward(q, lse, out)
+            ctx.heads = heads
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, lse, out = ctx.saved_tensors
+        B, N, C = out.shape
+        do = _aligned(dout.contiguous())
+        dqkv = torch.empty_like(q)
+        L._check(L.load().ghn3_attn_wide_bwd(_ptr(dqkv), _ptr(do), _ptr(q), _ptr(lse), _ptr(out), B, N, C, ctx.heads, _stream()),
+                 'ghn3_attn_wide_bwd')
+        return dqkv, None
+
+
+def wide_attention(qkv, heads):
+    """WideAttention as a function: qkv (B, N, 3 C) -> (B, N, C)."""
+    return WideAttention.apply(qkv, int(heads))
+
+
+def _msa_layer_dims(layer, x):
+    """(B, C, H, W, heads, hidden) of an msa layer that meets every condition of the native msa ops except the size limits of
+    C, the head dim and hidden, which differ between `MsaLayer` and `MsaWideLayer`; else None.  The conditions: x a 4-d fp32 CUDA
+    tensor below 2^31 elements, GHN3_NATIVE_MSA / GHN3_NATIVE_OPS / GHN3_NATIVE_AMP, the module structure of the `msa` op without
+    edge features, an integer stride, C % heads == 0, C % 4 == 0, at most 4096 tokens, inactive dropout, exact GELU, one LayerNorm
+    eps, fp32 CUDA parameters of the expected shapes, hidden % 4 == 0, B N 3C and B N hidden below 2^31."""
+    if not (_native_input(x, 'GHN3_NATIVE_MSA') and x.numel() < 2 ** 31):
+        return None
+    mods = _msa_modules(layer)
+    if mods is None or getattr(layer, 'edge_dim', 0) != 0:
+        return None
+    ln1, qkv, out, ln2, ff1, ff2, drops, act = mods
+    B, C, H, W = x.shape
+    heads = int(getattr(layer.attn, 'num_heads', 0))
+    stride = getattr(layer, 'stride', 1)
+    if not (isinstance(stride, int) and stride >= 1 and heads > 0 and C % heads == 0 and C % 4 == 0 and H * W <= 4096):
+        return None
+    if not (all(_no_dropout(m) for m in drops) and _is_kind(act, 'GELU') and getattr(act, 'approximate', 'none') == 'none'):
+        return None
+    if not (tuple(getattr(ln1, 'normalized_shape', ())) == (C,) and tuple(getattr(ln2, 'normalized_shape', ())) == (C,) and
+            getattr(ln1, 'eps', None) == getattr(ln2, 'eps', None)):
+        return None
+    w = [getattr(m, a, None) for m in (ln1, qkv, out, ln2, ff1, ff2) for a in ('weight', 'bias')]
+    if w[3] is None:                                   # (to_qkv without a bias, the search space's default)
+        w = w[:3] + w[4:]
+    if not _f32_cuda(*w):
+        return None
+    hidden = int(ff1.weight.shape[0])
+    want = [(ln1.weight, (C,)), (ln1.bias, (C,)), (qkv.weight, (3 * C, C)), (out.weight, (C, C)), (out.bias, (C,)),
+            (ln2.weight, (C,)), (ln2.bias, (C,)), (ff1.weight, (hidden, C)), (ff1.bias, (hidden,)), (ff2.weight, (C, hidden)),
+            (ff2.bias, (C,))] + ([] if qkv.bias is None else [(qkv.bias, (3 * C,))])
+    if not (all(tuple(t.shape) == s for t, s in want) and hidden % 4 == 0 and B * H * W * 3 * C < 2 ** 31 and
+            B * H * W * hidden < 2 ** 31):
+        return None
+    return B, C, H, W, heads, hidden
+
+
+def _msa_narrow(C, heads, hidden):
+    """The size limits of `MsaLayer` (ghn3_msa_* / ghn3_msa_lean_*); above them `MsaWideLayer` has limits of its own."""
+    return C <= 256 and C // heads <= 32 and hidden <= 1024
+
+
 class MsaLayer(torch.autograd.Function):
     """The pre-LN transformer layer of the ViT-style target networks -- the `msa` op, ops._TransformerLayer with edge_dim = 0
     (graphormer.py:144-248) -- as ONE autograd node on ghn3_msa_fwd / _bwd (ghn3_amd/csrc/tnet_msa.hip): x (B, C, H, W) in NCHW or
@@ -1187,34 +1268,11 @@ class MsaLayer(torch.autograd.Function):
 
     @staticmethod
     def applicable(layer, x):
-        if not (_native_input(x, 'GHN3_NATIVE_MSA') and x.numel() < 2 ** 31):
+        dims = _msa_layer_dims(layer, x)
+        if dims is None:
             return False
-        mods = _msa_modules(layer)
-        if mods is None or getattr(layer, 'edge_dim', 0) != 0:
-            return False
-        ln1, qkv, out, ln2, ff1, ff2, drops, act = mods
-        B, C, H, W = x.shape
-        heads = int(getattr(layer.attn, 'num_heads', 0))
-        stride = getattr(layer, 'stride', 1)
-        if not (isinstance(stride, int) and stride >= 1 and heads > 0 and C % heads == 0 and C // heads <= 32 and C % 4 == 0 and
-                C <= 256 and H * W <= 4096):
-            return False
-        if not (all(_no_dropout(m) for m in drops) and _is_kind(act, 'GELU') and getattr(act, 'approximate', 'none') == 'none'):
-            return False
-        if not (tuple(getattr(ln1, 'normalized_shape', ())) == (C,) and tuple(getattr(ln2, 'normalized_shape', ())) == (C,) and
-                getattr(ln1, 'eps', None) == getattr(ln2, 'eps', None)):
-            return False
-        w = [getattr(m, a, None) for m in (ln1, qkv, out, ln2, ff1, ff2) for a in ('weight', 'bias')]
-        if w[3] is None:                                   # (to_qkv without a bias, the search space's default)
-            w = w[:3] + w[4:]
-        if not _f32_cuda(*w):
-            return False
-        hidden = int(ff1.weight.shape[0])
-        want = [(ln1.weight, (C,)), (ln1.bias, (C,)), (qkv.weight, (3 * C, C)), (out.weight, (C, C)), (out.bias, (C,)),
-                (ln2.weight, (C,)), (ln2.bias, (C,)), (ff1.weight, (hidden, C)), (ff1.bias, (hidden,)), (ff2.weight, (C, hidden)),
-                (ff2.bias, (C,))] + ([] if qkv.bias is None else [(qkv.bias, (3 * C,))])
-        return all(tuple(t.shape) == s for t, s in want) and hidden % 4 == 0 and hidden <= 1024 and \
-            B * H * W * 3 * C < 2 ** 31 and B * H * W * hidden < 2 ** 31 and \
+        B, C, H, W, heads, hidden = dims
+        return _msa_narrow(C, heads, hidden) and \
             (B <= 65535 if msa_lean(B, heads, H * W) else B * heads * (H * W) ** 2 < 2 ** 31)
 
     @staticmethod
@@ -1267,6 +1325,69 @@ class MsaLayer(torch.autograd.Function):
         return (dx, None) + tuple(grads)
 
 
+MSA_WIDE_MAX_C, MSA_WIDE_MAX_D, MSA_WIDE_MAX_HIDDEN = 1024, 64, 4096        # (tnet_msa_wide.hip check_wide)
+
+
+def msa_wide_enabled():
+    """GHN3_NATIVE_MSA_WIDE=1 sends msa layers above `MsaLayer`'s limits to `MsaWideLayer`.  The default is 0: an existing GPU
+    test (tests/test_gpu_target_msa.py, the TransformerLayer(512) case) pins the default routing of such a layer to the stock
+    path, bit for bit, so the wide op is opt-in."""
+    return os.environ.get('GHN3_NATIVE_MSA_WIDE', '0') == '1'
+
+
+class MsaWideLayer(torch.autograd.Function):
+    """`MsaLayer` for the layers above its limits -- C <= 1024, head dim <= 64, hidden <= 4096 -- as ONE autograd node on
+    ghn3_msa_wide_fwd / _bwd (ghn3_amd/csrc/tnet_msa_wide.hip): the same layer, arguments, layouts and gradients; attention
+    always without a saved P.  A class of its own, so that `MsaLayer.apply` and the node name `MsaLayerBackward` keep meaning
+    the narrow op."""
+
+    @staticmethod
+    def applicable(layer, x):
+        """Every condition of `MsaLayer.applicable` but its limits of C, head dim and hidden, which must be EXCEEDED (narrow
+        layers never come here), inside the limits of the C check (ghn3_msa_wide_scratch_floats: every one is mirrored here, so
+        that GHN3_E_LIMIT cannot surface in the middle of a network), and GHN3_NATIVE_MSA_WIDE=1."""
+        if not msa_wide_enabled():
+            return False
+        dims = _msa_layer_dims(layer, x)
+        if dims is None:
+            return False
+        B, C, H, W, heads, hidden = dims
+        return not _msa_narrow(C, heads, hidden) and C <= MSA_WIDE_MAX_C and C // heads <= MSA_WIDE_MAX_D and \
+            hidden <= MSA_WIDE_MAX_HIDDEN and B <= 65535
+
+    @staticmethod
+    def forward(ctx, x, cfg, *params):
+        heads, stride, eps, train = cfg
+        lib = L.load()
+        layout = 1 if (x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous()) else 0
+        xc = _aligned(x.contiguous(memory_format=torch.channels_last) if layout else x.contiguous())
+        ps = [None if t is None else _aligned(t.contiguous()) for t in params]
+        B, C, H, W = xc.shape
+        Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+        d = _MsaDesc(B, H, W, C, heads, int(ps[8].shape[0]), stride, Ho, Wo, layout, float(eps), int(ps[3] is not None))
+        out = torch.empty((B, C, Ho, Wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+        scratch = torch.empty(_scratch_floats('ghn3_msa_wide_scratch_floats', d, 0), dtype=torch.float32, device=x.device)
+        L._check(lib.ghn3_msa_wide_fwd(ctypes.byref(d), _ptr(xc), ctypes.byref(_msa_ptrs(ps)), _ptr(out), _ptr(scratch),
+                                       int(train), _stream()), 'ghn3_msa_wide_fwd')
+        if train:                                          # (else nothing is kept: the scratch goes back to the allocator)
+            ctx.save_for_backward(xc, scratch, *ps)
+            ctx.desc = d
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        xc, scratch, *ps = ctx.saved_tensors
+        d = ctx.desc
+        do = _aligned(dout.contiguous(memory_format=torch.channels_last))
+        dx = torch.empty_like(xc)
+        grads = [None if t is None else torch.empty_like(t, memory_format=torch.contiguous_format) for t in ps]
+        bscratch = torch.empty(_scratch_floats('ghn3_msa_wide_scratch_floats', d, 1), dtype=torch.float32, device=xc.device)
+        L._check(L.load().ghn3_msa_wide_bwd(ctypes.byref(d), _ptr(do), _ptr(xc), ctypes.byref(_msa_ptrs(ps)), _ptr(scratch),
+                                            _ptr(dx), ctypes.byref(_msa_ptrs(grads)), _ptr(bscratch), _stream()),
+                 'ghn3_msa_wide_bwd')
+        return (dx, None) + tuple(grads)
+
+
 def msa_params(layer):
     """The twelve tensors of a `_TransformerLayer` in MSA_PARAM_NAMES order (b_qkv None without a QKV bias)."""
     ln1, qkv, out, ln2, ff1, ff2, _, _ = _msa_modules(layer)
@@ -1278,12 +1399,16 @@ def run_msa_layer(layer, x):
     """`_TransformerLayer.forward` of a (B, C, H, W) input (tokens, pre-LN attention and feed-forward blocks, stride slicing) on
     the fused op where it applies; None otherwise (the caller keeps its stock layers).  Under torch.no_grad (or with nothing to
     differentiate) the op saves nothing for a backward."""
-    if not MsaLayer.applicable(layer, x):
+    if MsaLayer.applicable(layer, x):
+        node = MsaLayer
+    elif MsaWideLayer.applicable(layer, x):
+        node = MsaWideLayer
+    else:
         return None
     params = msa_params(layer)
     train = torch.is_grad_enabled() and (x.requires_grad or any(t is not None and t.requires_grad for t in params))
     cfg = (int(layer.attn.num_heads), int(layer.stride), float(layer.ln1.eps), bool(train))
-    y = MsaLayer.apply(x, cfg, *params)
+    y = node.apply(x, cfg, *params)
     return _hand_on(y, False, layer.ln1, layer.attn.to_qkv)
 
 

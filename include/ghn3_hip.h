@@ -753,6 +753,25 @@ int ghn3_msa_lean_fwd(const ghn3_msa_desc* desc, const float* x, const ghn3_msa_
 int ghn3_msa_lean_bwd(const ghn3_msa_desc* desc, const float* dout, const float* x, const ghn3_msa_params* params,
                       const float* fwd_scratch, float* dx, const ghn3_msa_grads* grads, float* scratch, void* stream);
 
+/* ---- wide msa layers (tnet_msa_wide.hip; entry points added without an ABI version step) ------------------------------------
+ * ghn3_attn_wide_*: ghn3_attn_lean_* for d = C / heads <= 64 -- same qkv layout, lse contract, limits otherwise (C % 4 == 0,
+ * C % heads == 0, 1 <= N <= 4096, B and heads <= 65535), every element of dqkv written, no float atomics.  d <= 32 launches the
+ * kernels of ghn3_attn_lean_* (bit-equal results); 32 < d <= 64 has kernels of its own.
+ * ghn3_msa_wide_*: the layer of ghn3_msa_lean_* -- same descriptor, parameters, gradients, layouts and argument lists -- built
+ * from tiled products instead of row blocks held in LDS.  Limits (GHN3_E_LIMIT): C % 4 == 0, C <= 1024, C % heads == 0,
+ * C / heads <= 64, hidden % 4 == 0 and <= 4096, H W <= 4096, B <= 65535, B N 3C and B N hidden < 2^31 (narrower shapes are taken
+ * too).  Attention always runs on ghn3_attn_wide_*; no [B][heads][N][N] tensor exists.  x, out, dout, dx, the scratches and the
+ * four weight matrices 16-byte aligned (GHN3_E_ARG otherwise).  The forward scratch holds all the backward reads; `save` does not
+ * change what the forward computes or launches (save == 0: the caller may drop the scratch).  Deterministic. */
+int ghn3_attn_wide_fwd(float* out, float* lse, const float* qkv, int B, int N, int C, int heads, void* stream);
+int ghn3_attn_wide_bwd(float* dqkv, const float* dO, const float* qkv, const float* lse, const float* O, int B, int N, int C,
+                       int heads, void* stream);
+int64_t ghn3_msa_wide_scratch_floats(const ghn3_msa_desc* desc, int backward); /* host only; < 0: outside the limits */
+int ghn3_msa_wide_fwd(const ghn3_msa_desc* desc, const float* x, const ghn3_msa_params* params, float* out, float* scratch,
+                      int save, void* stream);
+int ghn3_msa_wide_bwd(const ghn3_msa_desc* desc, const float* dout, const float* x, const ghn3_msa_params* params,
+                      const float* fwd_scratch, float* dx, const ghn3_msa_grads* grads, float* scratch, void* stream);
+
 /* ---- target-network end (ABI v21): the classifier head and the meta-batch cross-entropy ------------------------------------
  * The head of every network (ghn3/ops.py:565-569; global pooling + `classifier`, built at ops.py:489-494), forward and backward:
  *   f = mean_{h,w} x (glob_avg = 1) or x flattened in logical NCHW order, feature c H W + h W + w (glob_avg = 0);
