@@ -1,0 +1,120 @@
+#!/usr/bin/env python3
+"""
+Counterpart of the reference's train_ddp.py without the image files (none are available offline): one plain network, its initial
+parameters predicted by a GHN-3 checkpoint (--ckpt) plus a little noise (--beta), fine-tuned with SGD through
+``ghn3_amd.Trainer`` -- the same call sequence (``update`` / ``log`` / ``save`` / ``scheduler_step``) -- on seeded random images.
+
+    python examples/train_ddp.py --ckpt ghn3xlm16.pt [--lr 0.025] [--wd 3e-5] [--momentum 0.9] [--label_smooth 0.1]
+                                 [--beta 1e-5] [--amp] [--arch resnet|genotype] [--steps 30] [--epochs 2] [--save DIR]
+
+Without --ckpt the network keeps its own initialisation.  The optimizer step is the fused multi-tensor SGD (ghn3_amd.FusedSGD);
+GHN3_FUSED_SGD=0 runs stock clip_grad_norm_ + torch.optim.SGD instead.  One GPU: the plain branch has no data-parallel path yet.
+"""
+import argparse
+import os
+import sys
+import time
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+class Block(nn.Module):
+    def __init__(self, cin, cout, stride):
+        super().__init__()
+        self.conv1 = nn.Conv2d(cin, cout, 3, stride, 1, bias=False)
+        self.bn1 = nn.BatchNorm2d(cout)
+        self.conv2 = nn.Conv2d(cout, cout, 3, 1, 1, bias=False)
+        self.bn2 = nn.BatchNorm2d(cout)
+        self.downsample = None
+        if stride != 1 or cin != cout:
+            self.downsample = nn.Sequential(nn.Conv2d(cin, cout, 1, stride, bias=False), nn.BatchNorm2d(cout))
+
+    def forward(self, x):
+        y = self.bn2(self.conv2(F.relu(self.bn1(self.conv1(x)))))
+        return F.relu(y + (x if self.downsample is None else self.downsample(x)))
+
+
+class SmallResNet(nn.Module):
+    """A ResNet-18-shaped network for 32 x 32 images at a quarter of the width."""
+
+    def __init__(self, num_classes=10, width=16):
+        super().__init__()
+        self.conv1 = nn.Conv2d(3, width, 3, 1, 1, bias=False)
+        self.bn1 = nn.BatchNorm2d(width)
+        layers, cin = [], width
+        for i, cout in enumerate((width, 2 * width, 4 * width, 8 * width)):
+            layers += [Block(cin, cout, 1 if i == 0 else 2), Block(cout, cout, 1)]
+            cin = cout
+        self.layers = nn.Sequential(*layers)
+        self.fc = nn.Linear(cin, num_classes)
+
+    def forward(self, x):
+        x = self.layers(F.relu(self.bn1(self.conv1(x))))
+        return self.fc(torch.flatten(F.adaptive_avg_pool2d(x, 1), 1))
+
+
+def genotype_network(num_classes):
+    """A DARTS-style network of the DeepNets-1M search space on the native layers (ghn3_amd.ops.Network)."""
+    from ghn3_amd import ops
+    geno = ops.Genotype(normal=[('sep_conv_3x3', 0), ('sep_conv_3x3', 1), ('skip_connect', 0), ('conv_1x1', 2)],
+                        normal_concat=[2, 3],
+                        reduce=[('max_pool_3x3', 0), ('sep_conv_3x3', 1), ('skip_connect', 2), ('avg_pool_3x3', 0)],
+                        reduce_concat=[2, 3])
+    return ops.Network(genotype=geno, C=16, num_classes=num_classes, n_cells=5, is_imagenet_input=False)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--ckpt', default=None, help='GHN-3 checkpoint that predicts the initial parameters')
+    ap.add_argument('--arch', choices=('resnet', 'genotype'), default='resnet')
+    ap.add_argument('--lr', type=float, default=0.025)
+    ap.add_argument('--wd', type=float, default=3e-5)
+    ap.add_argument('--momentum', type=float, default=0.9)
+    ap.add_argument('--label_smooth', type=float, default=0.1)
+    ap.add_argument('--beta', type=float, default=1e-5, help='standard deviation of the noise added to the predicted parameters')
+    ap.add_argument('--amp', action='store_true')
+    ap.add_argument('--batch-size', type=int, default=64)
+    ap.add_argument('--steps', type=int, default=30, help='steps per epoch')
+    ap.add_argument('--epochs', type=int, default=2)
+    ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--save', default=None)
+    args = ap.parse_args()
+
+    from ghn3_amd import Trainer, log
+    torch.manual_seed(args.seed)
+    num_classes = 10
+    model = SmallResNet(num_classes) if args.arch == 'resnet' else genotype_network(num_classes)
+    trainer = Trainer(model, opt='sgd', opt_args={'lr': args.lr, 'weight_decay': args.wd, 'momentum': args.momentum},
+                      scheduler='cosine', n_batches=args.steps, grad_clip=5, device='cuda', log_interval=10,
+                      label_smoothing=args.label_smooth, save_dir=args.save, ckpt=args.ckpt, epochs=args.epochs, amp=args.amp,
+                      beta=args.beta)
+    log('training %s (%d parameters in %d tensors), %d x %d images per step'
+        % (type(model).__name__, sum(p.numel() for p in model.parameters()), len(list(model.parameters())), args.batch_size, 32))
+    gen = torch.Generator().manual_seed(args.seed + 1)
+    images = torch.randn(args.batch_size, 3, 32, 32, generator=gen).cuda()
+    targets = torch.randint(0, num_classes, (args.batch_size,), generator=gen).cuda()
+    t0, n_timed = None, 0
+    for epoch in range(trainer.start_epoch, args.epochs):
+        trainer.reset_metrics(epoch)
+        for step in range(trainer.start_step, args.steps):
+            if t0 is None and step == min(3, args.steps - 1):
+                torch.cuda.synchronize()
+                t0, n_timed = time.perf_counter(), 0
+            trainer.update(images, targets)
+            trainer.log(step)
+            n_timed += 1
+            if args.save:
+                trainer.save(epoch, step, {})
+        trainer.scheduler_step()
+    torch.cuda.synchronize()
+    if t0 is not None and n_timed:
+        log('%.2f ms per step over %d steps; %d updates skipped'
+            % (1e3 * (time.perf_counter() - t0) / n_timed, n_timed, trainer.skipped_updates))
+
+
+if __name__ == '__main__':
+    main()

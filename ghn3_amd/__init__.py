@@ -11,7 +11,7 @@ from .nn import from_pretrained, GHN3, ConvDecoder3, SequentialMultipleInOut, no
 from .utils import log, Logger, print_grads
 from .ddp_utils import (setup_ddp, is_ddp, get_ddp_rank, clean_ddp, avg_ddp_metric, all_reduce_flat_grads,
                         sync_parameters)
-from .optim import FusedAdamW, save_checkpoint
+from .optim import FusedAdamW, FusedSGD, save_checkpoint
 from .trainer import Trainer
 from .ops import Network, NetworkLight
 from .deepnets1m import DeepNets1MDDP, NetBatchSamplerDDP

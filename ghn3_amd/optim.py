@@ -5,14 +5,19 @@ Replaces, for a ghn3_amd.GHN3 whose parameters and gradients live in one flat fp
     nn.utils.clip_grad_norm_(parameters, grad_clip)      /root/reference/ghn3/trainer.py:356-360
     optimizer.step()   (torch.optim.AdamW)               /root/reference/ghn3/trainer.py:165-175,379
 by two kernels over the flat buffers (GHN3_OP_SUMSQ + GHN3_OP_ADAMW) -- no per-tensor launches.
+
+For a plain network (separate parameter tensors, the train_ddp.py recipe) FusedSGD does the same for clip_grad_norm_ +
+torch.optim.SGD with a multi-tensor kernel pair (ghn3_mt_sumsq + ghn3_mt_sgd).
 """
 
+import ctypes
 import os
 
 import numpy as np
 import torch
 
 from . import _lib as L
+from .nn import pinned_ring
 
 
 def _dbits(x):
@@ -436,6 +441,252 @@ class ShardedAdamW:
             for (s, main), (lo, hi) in zip(reducer.chunks, reducer.owned):
                 dist.all_gather_into_tensor(flat[s:s + main], flat[lo:hi].clone())
         return total.sqrt() * inv_scale
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Plain networks (train_ddp.py): clip_grad_norm_ + torch.optim.SGD over separate parameter tensors
+# ---------------------------------------------------------------------------------------------------------------------
+MT_CHUNK = 8192                       # include/ghn3_hip.h GHN3_MT_CHUNK
+
+
+class _MtTensor(ctypes.Structure):
+    _fields_ = [('p', ctypes.c_void_p), ('m', ctypes.c_void_p), ('n', ctypes.c_int64)]
+
+
+class _MtChunk(ctypes.Structure):
+    _fields_ = [('tensor', ctypes.c_int32), ('_pad', ctypes.c_int32), ('first', ctypes.c_int64)]
+
+
+class _MtSgdArgs(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_float) for n in ('lr', 'momentum', 'weight_decay', 'max_norm', 'inv_scale')] + \
+        [('nesterov', ctypes.c_int32)]
+
+
+_MT_TENSOR_DT = np.dtype([('p', '<u8'), ('m', '<u8'), ('n', '<i8')])
+_MT_CHUNK_DT = np.dtype([('tensor', '<i4'), ('_pad', '<i4'), ('first', '<i8')])
+assert _MT_TENSOR_DT.itemsize == ctypes.sizeof(_MtTensor) == 24 and _MT_CHUNK_DT.itemsize == ctypes.sizeof(_MtChunk) == 16
+
+
+def sgd_reference_(params, grads, bufs, lr, momentum=0.0, weight_decay=0.0, nesterov=False, max_norm=0.0, inv_scale=1.0):
+    """torch restatement of one FusedSGD step (ghn3_mt_sumsq + ghn3_mt_sgd), in place on lists of tensors of any float type:
+    the gradients' global norm as clip_grad_norm_ takes it (the norm of the per-tensor norms), g / scale times the clip
+    coefficient, then torch.optim.SGD's update with dampening 0 on momentum buffers that start at zero.  `grads` are not
+    modified; bufs[i] is ignored when momentum == 0.  Returns the unscaled norm (0-d tensor); when it is not finite nothing was
+    touched.  In float64 this is the oracle of the GPU tests; on fp32 CPU tensors it is FusedSGD's step, operation for
+    operation what the stock pair computes."""
+    if not grads:
+        return torch.zeros(())
+    norm = torch.linalg.vector_norm(torch.stack([torch.linalg.vector_norm(g) for g in grads])) * inv_scale
+    if not bool(torch.isfinite(norm)):
+        return norm
+    coef = inv_scale * (min(1.0, max_norm / (float(norm) + 1e-6)) if max_norm > 0 else 1.0)
+    for p, g, m in zip(params, grads, bufs):
+        d = g * coef if coef != 1.0 else g
+        if weight_decay != 0:
+            d = d.add(p, alpha=weight_decay)
+        if momentum != 0:
+            m.mul_(momentum).add_(d)
+            d = d.add(m, alpha=momentum) if nesterov else m
+        p.add_(d, alpha=-lr)
+    return norm
+
+
+class FusedSGD:
+    """clip_grad_norm_ + torch.optim.SGD (same update rule, dampening 0) for a list of separate parameter tensors: two
+    launches over a table of tensors (ghn3_mt_sumsq, ghn3_mt_sgd), whatever their number, instead of some ten foreach
+    launches and five passes over the bytes.
+
+    The momentum of all parameters lives in ONE buffer of the optimizer (segments padded to 4 floats, so each starts on 16
+    bytes); state_dict() hands out views of it.  The buffers start at zero, which with dampening 0 is torch's first-step
+    `buf = clone(d)` bit for bit.  The chunk table and the parameter / momentum pointers go to the device once per set of
+    parameters that take part; the gradient pointers -- autograd allocates the gradients anew after zero_grad(set_to_none) --
+    go up once per step through the pinned ring.  CPU parameters take sgd_reference_ (host logic can be tested anywhere)."""
+
+    def __init__(self, params, lr, momentum=0, dampening=0, weight_decay=0, nesterov=False, max_grad_norm=0.0,
+                 nan_guard=True):
+        if dampening != 0:
+            raise ValueError('FusedSGD implements dampening = 0 only (momentum buffers start at zero and no first-step flag '
+                             'exists on the device), got %r' % (dampening,))
+        if lr < 0 or momentum < 0 or weight_decay < 0:
+            raise ValueError('lr, momentum and weight_decay must not be negative')
+        if nesterov and momentum <= 0:
+            raise ValueError('Nesterov momentum requires a momentum and zero dampening')
+        params = list(params)
+        if params and isinstance(params[0], dict):
+            if len(params) != 1:
+                raise ValueError('FusedSGD takes one parameter group')
+            params = list(params[0]['params'])
+        if not params:
+            raise ValueError('FusedSGD got an empty parameter list')
+        dev = params[0].device
+        for p in params:
+            if p.dtype != torch.float32 or p.device != dev or p.is_sparse or not p.is_contiguous():
+                raise ValueError('FusedSGD takes dense contiguous fp32 parameters on one device')
+        self.params, self.device = params, dev
+        self.lr, self.momentum, self.weight_decay, self.nesterov = lr, momentum, weight_decay, bool(nesterov)
+        self.max_grad_norm, self.nan_guard = max_grad_norm, nan_guard
+        self._offs = np.concatenate([[0], np.cumsum([(p.numel() + 3) // 4 * 4 for p in params])]).astype(np.int64)
+        self.momentum_buffer = torch.zeros(int(self._offs[-1]), dtype=torch.float32, device=dev) if momentum != 0 else None
+        self._stepped = set()           # parameters that had a gradient in some step: the ones torch keeps a state entry for
+        self._table = None
+        self.steps = 0
+
+    def _buf(self, i):
+        if self.momentum_buffer is None:
+            return None
+        o = int(self._offs[i])
+        return self.momentum_buffer[o:o + self.params[i].numel()].view(self.params[i].shape)
+
+    def zero_grad(self, set_to_none=True):
+        for p in self.params:
+            if p.grad is not None:
+                if set_to_none:
+                    p.grad = None
+                else:
+                    p.grad.detach_().zero_()
+
+    # ------------------------------------------------------------------ the step
+    def _build_table(self, active, pptr):
+        """Device tables for the parameters `active` (indices) at the addresses `pptr`: records, chunk list, scratch."""
+        mbase = self.momentum_buffer.data_ptr() if self.momentum_buffer is not None else 0
+        rec = np.zeros(len(active), dtype=_MT_TENSOR_DT)
+        chunks = []
+        for k, i in enumerate(active):
+            n = self.params[i].numel()
+            rec[k] = (pptr[k], mbase + 4 * int(self._offs[i]) if mbase else 0, n)
+            chunks += [(k, 0, first) for first in range(0, n, MT_CHUNK)]
+        ch = np.array(chunks, dtype=_MT_CHUNK_DT)
+        dev = self.device
+        return {'active': active, 'pptr': pptr, 'n_chunks': len(ch),
+                'rec': torch.from_numpy(rec.view(np.uint8)).to(dev), 'chunks': torch.from_numpy(ch.view(np.uint8)).to(dev),
+                'scal': torch.zeros(4 + len(ch), dtype=torch.float32, device=dev)}      # [norm^2, pad | one partial per chunk]
+
+    def step(self, grad_scale=1.0):
+        """One update from the parameters' .grad; grad_scale: the loss scale the gradients carry (they are divided by it inside
+        the kernel).  Returns the gradient norm (device scalar, like clip_grad_norm_) when clipping or the NaN guard is on, else
+        None; when it is not finite no parameter and no momentum buffer changed.  A parameter without a gradient or with
+        requires_grad=False does not take part, as in torch."""
+        active, grads = [], []
+        for i, p in enumerate(self.params):
+            g = p.grad
+            if g is None or not p.requires_grad:
+                continue
+            self._stepped.add(i)
+            if p.numel() == 0:                    # (torch keeps a state entry for it; there is nothing to update)
+                continue
+            if g.dtype != torch.float32 or g.is_sparse or g.device != p.device or not g.is_contiguous():
+                g = (g.to_dense() if g.is_sparse else g).to(device=p.device, dtype=torch.float32).contiguous()
+            active.append(i)
+            grads.append(g)
+        self.steps += 1
+        guard = bool(self.max_grad_norm and self.max_grad_norm > 0) or self.nan_guard
+        inv_scale = 1.0 / float(grad_scale)
+        if self.device.type != 'cuda':
+            with torch.no_grad():
+                norm = sgd_reference_([self.params[i] for i in active], grads, [self._buf(i) for i in active], self.lr,
+                                      self.momentum, self.weight_decay, self.nesterov,
+                                      float(self.max_grad_norm or 0.0) if guard else 0.0, inv_scale)
+            return norm if guard else None
+        active = tuple(active)
+        pptr = [self.params[i].data_ptr() for i in active]
+        tb = self._table
+        if tb is None or tb['active'] != active or tb['pptr'] != pptr:
+            tb = self._table = self._build_table(active, pptr)
+        if not active:
+            return torch.zeros((), device=self.device) if guard else None
+        lib = L.load()
+        with torch.cuda.device(self.device):
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            gptr = pinned_ring(self.device).upload(np.asarray([g.data_ptr() for g in grads], dtype=np.int64), self.device)
+            scal = tb['scal']
+            tables = (tb['rec'].data_ptr(), gptr.data_ptr(), tb['chunks'].data_ptr(), tb['n_chunks'])
+            if guard:
+                L._check(lib.ghn3_mt_sumsq(*tables, scal.data_ptr() + 16, scal.data_ptr(), stream), 'ghn3_mt_sumsq')
+            args = _MtSgdArgs(self.lr, self.momentum, self.weight_decay, float(self.max_grad_norm or 0.0), inv_scale,
+                              int(self.nesterov))
+            L._check(lib.ghn3_mt_sgd(*tables, scal.data_ptr() if guard else None, ctypes.byref(args), stream), 'ghn3_mt_sgd')
+        return scal[0].sqrt() * inv_scale if guard else None
+
+    # ------------------------------------------------------------------ checkpoints
+    def state_dict(self):
+        """State in the layout of ``torch.optim.SGD.state_dict()`` over the same parameter list: a checkpoint written by
+        either optimizer resumes in the other.  The momentum buffers are views of the optimizer's one buffer."""
+        state = {}
+        if self.momentum != 0:                    # (torch keeps no state entry at all without a momentum)
+            for i in sorted(self._stepped):
+                state[i] = {'momentum_buffer': self._buf(i)}
+        group = {'lr': self.lr, 'momentum': self.momentum, 'dampening': 0, 'weight_decay': self.weight_decay,
+                 'nesterov': self.nesterov, 'maximize': False, 'foreach': None, 'differentiable': False, 'fused': None,
+                 'params': list(range(len(self.params)))}
+        return {'state': state, 'param_groups': [group]}
+
+    def load_state_dict(self, sd):
+        """Accepts a ``torch.optim.SGD`` (or FusedSGD) state dict over the same parameter list."""
+        groups = sd['param_groups']
+        if len(groups) != 1 or len(groups[0]['params']) != len(self.params):
+            raise ValueError('one parameter group over the same %d parameters expected' % len(self.params))
+        g = groups[0]
+        if g.get('dampening', 0) != 0 or g.get('maximize', False):
+            raise ValueError('FusedSGD cannot resume a state with dampening or maximize')
+        if (float(g['momentum']) != 0) != (self.momentum != 0):
+            raise ValueError('momentum %r of the state does not fit an optimizer built with momentum %r'
+                             % (g['momentum'], self.momentum))
+        self.lr, self.momentum, self.weight_decay = float(g['lr']), float(g['momentum']), float(g['weight_decay'])
+        self.nesterov = bool(g['nesterov'])
+        if self.momentum_buffer is not None:
+            self.momentum_buffer.zero_()
+        self._stepped = set()
+        for k, idx in enumerate(g['params']):
+            st = sd['state'].get(idx)
+            if st is None:
+                continue
+            self._stepped.add(k)
+            buf = st.get('momentum_buffer')
+            if buf is not None and self.momentum_buffer is not None:
+                self._buf(k).copy_(buf)
+
+
+class StockSGD:
+    """nn.utils.clip_grad_norm_ + torch.optim.SGD (foreach) behind FusedSGD's interface: the other side of the Trainer's
+    GHN3_FUSED_SGD switch.  Unscale, norm, clip and update are separate torch passes, and skipping a step whose norm is not
+    finite costs one host read per step."""
+
+    def __init__(self, params, lr, momentum=0, dampening=0, weight_decay=0, nesterov=False, max_grad_norm=0.0):
+        self.params = list(params)
+        self.opt = torch.optim.SGD(self.params, lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
+                                   nesterov=nesterov)
+        self.max_grad_norm = max_grad_norm
+        self.steps = 0
+
+    @property
+    def lr(self):
+        return self.opt.param_groups[0]['lr']
+
+    @lr.setter
+    def lr(self, value):
+        self.opt.param_groups[0]['lr'] = value
+
+    def zero_grad(self, set_to_none=True):
+        self.opt.zero_grad(set_to_none=set_to_none)
+
+    def step(self, grad_scale=1.0):
+        with_grad = [p for p in self.params if p.grad is not None]
+        self.steps += 1
+        if not with_grad:
+            return torch.zeros((), device=self.params[0].device)
+        if float(grad_scale) != 1.0:
+            torch._foreach_mul_([p.grad for p in with_grad], 1.0 / float(grad_scale))
+        clip = self.max_grad_norm and self.max_grad_norm > 0
+        norm = torch.nn.utils.clip_grad_norm_(with_grad, self.max_grad_norm if clip else float('inf'))
+        if bool(torch.isfinite(norm)):
+            self.opt.step()
+        return norm
+
+    def state_dict(self):
+        return self.opt.state_dict()
+
+    def load_state_dict(self, sd):
+        self.opt.load_state_dict(sd)
 
 
 def save_checkpoint(path, ghn, optimizer, epoch, step, config=None):

@@ -28,6 +28,18 @@ What is different underneath (MI355X-first, same results):
     all-reduce of a 4-vector per step instead of 4-5 scalar all-gathers; they are read at log time only.
 Target networks run on stock torch ops with the predicted tensors; images may be None, in which case
 the step trains on the regulariser alone (the benchmark's loss).
+
+Any other nn.Module takes the plain-network branch, the reference's second entry point (train_ddp.py; constructor
+trainer.py:102-133):
+
+    trainer = Trainer(model, opt='sgd', opt_args={'lr': 0.025, 'momentum': 0.9, 'weight_decay': 3e-5}, scheduler='cosine',
+                      n_batches=len(queue), grad_clip=5, device=device, label_smoothing=0.1, ckpt='ghn3xlm16.pt', beta=1e-5, ...)
+    trainer.update(images, targets)
+
+`ckpt` names a GHN that predicts the initial parameters on the device (a checkpoint.pt in save_dir wins and resumes instead);
+norm, unscale, clip and the SGD update are one multi-tensor step (FusedSGD; GHN3_FUSED_SGD=0: the stock pair).  Metrics, loss
+scale, skipped steps, checkpoints and schedules are the GHN branch's code.  Refused for plain networks: other optimizers, bce,
+mixup, data-parallel runs.
 """
 
 import math
@@ -37,7 +49,7 @@ import torch
 
 from .ddp_utils import is_ddp, get_ddp_rank, sync_parameters, FlatGradReducer
 from . import target_ops
-from .optim import FusedAdamW, save_checkpoint
+from .optim import FusedAdamW, FusedSGD, StockSGD, save_checkpoint
 from .utils import log, Logger
 
 import torch.distributed as dist
@@ -95,12 +107,12 @@ class Trainer:
     def __init__(self, model, opt, opt_args, scheduler, n_batches, grad_clip=5, auxiliary=False, auxiliary_weight=0.4,
                  device='cuda', log_interval=100, label_smoothing=0, predparam_wd=0, scheduler_args=None, save_dir=None,
                  ckpt=None, epochs=None, verbose=False, amp=False, amp_min_scale=None, amp_growth_interval=2000,
-                 grad_compress=None, amp_init_scale=65536.0, **unused):
+                 grad_compress=None, amp_init_scale=65536.0, bce=False, mixup=False, compile_mode=None, beta=1e-5, **unused):
         from .nn import GHN3
-        if not isinstance(model, GHN3):
-            raise NotImplementedError('ghn3_amd.Trainer drives the GHN branch (train_ghn_ddp.py); plain networks '
-                                      '(train_ddp.py) train with stock PyTorch')
-        if opt.lower() != 'adamw':
+        self._plain = not isinstance(model, GHN3)
+        if self._plain:
+            self._check_plain(opt, bce, mixup, compile_mode)
+        elif opt.lower() != 'adamw':
             raise NotImplementedError('the fused optimizer step implements AdamW (the GHN-3 recipe); got %s' % opt)
         assert 'lr' in opt_args, 'learning rate must be specified in opt_args'
         self.n_batches, self.grad_clip, self.device = n_batches, grad_clip, device
@@ -131,22 +143,34 @@ class Trainer:
         if self.checkpoint_path is not None and os.path.exists(self.checkpoint_path):
             ckpt = self.checkpoint_path
             log('Found existing checkpoint %s: resuming.' % ckpt)
-        if ckpt is not None:
+        if self._plain:
+            # (trainer.py:102-133: a checkpoint of the run wins; else `ckpt` names a GHN that predicts the initial parameters)
+            if ckpt == self.checkpoint_path and ckpt is not None:
+                state = torch.load(ckpt, map_location='cpu')
+                model.load_state_dict(state['state_dict'])
+            elif ckpt is not None:
+                self._ghn_init(model, ckpt, float(beta))
+        elif ckpt is not None:
             if self.ddp:
                 dist.barrier()
             state = torch.load(ckpt, map_location='cpu')
             model.load_state_dict(state['state_dict'])
+        if state is not None:
             self.start_epoch, self.start_step = int(state.get('epoch', 0)), int(state.get('step', 0))
             if amp and 'amp_loss_scale' in state:        # (a resumed run does not repeat the warm-down from 65536)
                 self.loss_scale = max(self.amp_min_scale, float(state['amp_loss_scale']))
                 self._clean_steps = int(state.get('amp_clean_steps', 0))
         self._model = model
-        if self.ddp:
-            sync_parameters(model)                       # what DistributedDataParallel's constructor does
-            model.grad_reducer = FlatGradReducer(compress=grad_compress)
         self.base_lr = float(opt_args['lr'])
-        kw = {k: v for k, v in opt_args.items() if k in ('betas', 'eps', 'weight_decay', 'state_dtype', 'state_seed')}
-        self._optimizer = FusedAdamW(model, lr=self.base_lr, max_grad_norm=float(grad_clip or 0.0), **kw)
+        if self._plain:
+            self.predparam_wd = 0
+            self._optimizer = self._plain_optimizer(model, opt_args)
+        else:
+            if self.ddp:
+                sync_parameters(model)                   # what DistributedDataParallel's constructor does
+                model.grad_reducer = FlatGradReducer(compress=grad_compress)
+            kw = {k: v for k, v in opt_args.items() if k in ('betas', 'eps', 'weight_decay', 'state_dtype', 'state_seed')}
+            self._optimizer = FusedAdamW(model, lr=self.base_lr, max_grad_norm=float(grad_clip or 0.0), **kw)
         self._lr_mult = _schedule(scheduler, epochs or 1, self.base_lr, scheduler_args)
         self._epoch = self.start_epoch
         if state is not None and 'optimizer' in state:
@@ -178,6 +202,8 @@ class Trainer:
 
     # ------------------------------------------------------------------ one training step
     def update(self, images, targets, graphs=None):
+        if self._plain:
+            return self._update_plain(images, targets)
         ghn = self._model
         if not ghn.training:
             ghn.train()
@@ -218,6 +244,13 @@ class Trainer:
         # Graphormer already runs; the next forward joins in front of its decoders, save() waits explicitly)
         gnorm = self._optimizer.step(ghn.last_plan.gflat, grad_scale=self.loss_scale, plan=ghn.last_plan,
                                      local_grads=not self.ddp, overlap=True)
+        n = int(targets.numel()) * len(models) if images is not None else len(models)
+        return self._account(stats, gnorm, n)
+
+    def _account(self, stats, gnorm, n):
+        """The step's bookkeeping, on the device: stats = [loss, top1, top5, loss_predwd], gnorm = the optimizer's gradient
+        norm (not finite: the update was skipped), n = the samples the statistics are averages of."""
+        dev = self.device
         with torch.no_grad():
             bad = ~torch.isfinite(gnorm) if gnorm is not None else ~torch.isfinite(stats[0])
             vec = torch.cat([stats, bad.float().view(1)])
@@ -227,7 +260,6 @@ class Trainer:
             self._skipped = getattr(self, '_skipped', torch.zeros((), device=dev)) + (vec[4] > 0).float()
             # (steps whose AVERAGED loss is not finite, counted apart from overflowed gradients: only they can mean divergence)
             self._bad_loss = getattr(self, '_bad_loss', torch.zeros((), device=dev)) + (~torch.isfinite(vec[0])).float()
-            n = int(targets.numel()) * len(models) if images is not None else len(models)
             good = (vec[4] == 0).float()                 # (skipped steps enter neither the sums nor the counts)
             self.metrics.update(torch.nan_to_num(vec[:len(self.metrics.names)]) * good, good * n)
         self._step += 1
@@ -287,6 +319,65 @@ class Trainer:
                     self.loss_scale *= 2.0
                     self._clean_steps = 0
 
+    # ------------------------------------------------------------------ plain networks (train_ddp.py)
+    @staticmethod
+    def _check_plain(opt, bce, mixup, compile_mode):
+        """What the plain-network branch does not take (the GHN branch ignores these arguments, as before)."""
+        if is_ddp():
+            raise NotImplementedError('plain networks train on one GPU here: the data-parallel gradient exchange exists for '
+                                      'the GHN branch only')
+        if opt.lower() != 'sgd':
+            raise NotImplementedError('plain networks train with SGD (the train_ddp.py recipe); got %s' % opt)
+        if bce or mixup:
+            raise NotImplementedError('bce / mixup are the timm classes BinaryCrossEntropy and Mixup: timm is not installed '
+                                      'here, so their behaviour cannot be pinned by a test')
+        if compile_mode not in (None, 'none', False):
+            log('compile_mode=%s is ignored: the layers and the optimizer step are native already' % (compile_mode,))
+
+    def _ghn_init(self, model, ckpt, beta):
+        """Initial parameters predicted by the GHN checkpoint `ckpt`, plus noise (trainer.py:128-132).  The prediction runs on
+        the device (milliseconds), the GHN is dropped afterwards.  The noise restates ppuda.utils.init(model, orth=False,
+        beta): p += beta randn_like(p) for every parameter with more than one dimension, drawn from torch's global generator
+        of the parameter's device (parity with ppuda unpinned: ppuda is not installed)."""
+        from .nn import from_pretrained
+        ghn = from_pretrained(ckpt).to(self.device)
+        with torch.no_grad():
+            ghn(model, bn_track_running_stats=True, keep_grads=False, reduce_graph=False)
+            if beta != 0:
+                for p in model.parameters():
+                    if p.dim() > 1:
+                        p.add_(torch.randn_like(p), alpha=beta)
+        log('initial parameters predicted by %s (beta=%g)' % (ckpt, beta))
+
+    def _plain_optimizer(self, model, opt_args):
+        """FusedSGD, or with GHN3_FUSED_SGD=0 the stock pair behind the same interface (the A/B switch)."""
+        kw = {k: opt_args[k] for k in ('momentum', 'weight_decay', 'nesterov', 'dampening') if k in opt_args}
+        cls = FusedSGD if os.environ.get('GHN3_FUSED_SGD', '1') != '0' else StockSGD
+        return cls(model.parameters(), lr=self.base_lr, max_grad_norm=float(self.grad_clip or 0.0), **kw)
+
+    def _update_plain(self, images, targets):
+        model, dev = self._model, self.device
+        if not model.training:
+            model.train()
+        self._optimizer.zero_grad(set_to_none=True)      # (autograd then WRITES the gradients instead of adding into them)
+        images = images.to(dev, non_blocking=True)
+        targets = targets.to(dev, non_blocking=True)
+        with torch.autocast(torch.device(dev).type, dtype=torch.float16, enabled=self.amp):
+            out = model(images)
+        y, y_aux = (out[0], out[1]) if isinstance(out, tuple) else (out, None)
+        ce, hits = target_ops.meta_cross_entropy([y], targets, self.label_smoothing)
+        loss = ce.sum()
+        if self.auxiliary and y_aux is not None:
+            loss = loss + self.auxiliary_weight * target_ops.meta_cross_entropy([y_aux], targets, self.label_smoothing)[0].sum()
+        stats = torch.zeros(4, device=dev)               # loss, top1, top5, (unused: loss_predwd)
+        with torch.no_grad():
+            stats[0] = loss.detach()
+            stats[1:3] = hits * (100.0 / targets.numel())
+        (loss * self.loss_scale).backward()
+        # norm, unscale, clip and SGD in two launches; a non-finite norm (NaN loss, fp16 overflow) skips the update on the device
+        gnorm = self._optimizer.step(grad_scale=self.loss_scale)
+        return self._account(stats, gnorm, int(targets.numel()))
+
     # ------------------------------------------------------------------ checkpoints / logging
     def save(self, epoch, step, config, save_freq=300, interm_epoch=5):
         if not (((step + 1) % save_freq == 0) or step == self.n_batches - 1):
@@ -296,7 +387,8 @@ class Trainer:
         self._sync_skips()          # (the optimizer's bias-correction count must not include skipped steps when it is saved)
         if self.rank != 0:
             return
-        self._optimizer.wait()      # (an overlapped optimizer step may still be writing the decoder parameters / moments)
+        if not self._plain:
+            self._optimizer.wait()  # (an overlapped optimizer step may still be writing the decoder parameters / moments)
         if self.amp:
             config = dict(config or {}, amp_loss_scale=self.loss_scale, amp_clean_steps=self._clean_steps)
         save_checkpoint(self.checkpoint_path, self._model, self._optimizer, epoch, step, config)

@@ -853,6 +853,35 @@ int ghn3_join_fwd(const ghn3_join_desc* desc, float* out, void* stream);
 int ghn3_join_bwd(const ghn3_join_desc* desc, const float* dout, void* stream);
 int ghn3_posenc_bwd(int N, int C, int H, int W, int layout, const float* dy, float* dw, void* stream);
 
+/* ---- multi-tensor SGD step for plain networks (ABI v21, added without a version step) ------------------------------------------
+ * nn.utils.clip_grad_norm_ + torch.optim.SGD over a table of separate fp32 tensors (a network's parameters, their gradients and
+ * the optimizer's momentum buffers) in two launches, whatever the number of tensors.  Every table lives in DEVICE memory:
+ *   tensors [n_tensors]  the parameter, its momentum buffer (NULL when momentum == 0) and the element count: static;
+ *   grads   [n_tensors]  the gradient of each tensor: what changes from step to step;
+ *   chunks  [n_chunks]   the work list: chunk c covers elements [first, min(first + GHN3_MT_CHUNK, n)) of tensor `tensor`;
+ *                        `first` is a multiple of GHN3_MT_CHUNK, so a chunk starts a multiple of 4 floats into its tensor.  The
+ *                        chunks cover every element of every tensor exactly once (the caller's duty: the tables are not
+ *                        readable from the host).  An empty tensor has no chunk.
+ * One workgroup takes one chunk at a time (grid = min(n_chunks, 2048), striding).  A tensor whose pointers are all 16-byte aligned
+ * moves as 16-byte accesses, any other one (a view into a larger buffer) and the last n % 4 elements as 4-byte ones; the
+ * arithmetic is the same instructions on both paths, so the bits do not depend on the alignment.
+ * ghn3_mt_sumsq: parts[c] = sum of squares of chunk c's gradient, out[0] = the sum of parts in a fixed order (a second, one-
+ *   workgroup launch).  No atomics: the same bits on every run.  `parts` holds n_chunks floats.
+ * ghn3_mt_sgd: per element, with explicit fused multiply-adds (one rounding each),
+ *     d = g coef + wd p,   m = momentum m + d,   u = nesterov ? d + momentum m : m   (momentum == 0: u = d),   p -= lr u
+ *   coef = inv_scale min(1, max_norm / (sqrt(*sumsq) inv_scale + 1e-6)) (max_norm <= 0 or sumsq == NULL: coef = inv_scale), the
+ *   rule of GHN3_OP_ADAMW.  inv_scale = 1 / loss scale.  A non-finite *sumsq leaves every p and m untouched.  Momentum buffers start
+ *   at zero: with that the first step equals torch's buf = clone(d) bit for bit, and no per-tensor first-step flag exists
+ *   (dampening is not supported).  GHN3_E_ARG: a NULL or misaligned table, nesterov without momentum. */
+#define GHN3_MT_CHUNK 8192
+typedef struct ghn3_mt_tensor { float* p; float* m; int64_t n; } ghn3_mt_tensor;
+typedef struct ghn3_mt_chunk { int32_t tensor, _pad; int64_t first; } ghn3_mt_chunk;
+typedef struct ghn3_mt_sgd_args { float lr, momentum, weight_decay, max_norm, inv_scale; int32_t nesterov; } ghn3_mt_sgd_args;
+int ghn3_mt_sumsq(const ghn3_mt_tensor* tensors, const float* const* grads, const ghn3_mt_chunk* chunks, int n_chunks,
+                  float* parts, float* out, void* stream);
+int ghn3_mt_sgd(const ghn3_mt_tensor* tensors, const float* const* grads, const ghn3_mt_chunk* chunks, int n_chunks,
+                const float* sumsq, const ghn3_mt_sgd_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
