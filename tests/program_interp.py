@@ -93,9 +93,17 @@ class Interp:
             np.maximum(x, 0, out=x)
 
     def op_sumsq(self, o, problems):
-        n = int(o['i'][0])
+        n, lo, hi, n_extra = (int(v) for v in o['i'][:4])
         x = self.fview(o['r'][1], n).astype(np.float64)
-        self.fview(o['r'][0], 1)[0] += np.float32((x * x).sum())
+        if lo < hi:                                          # the floats [i1, i2) are left out: r3 carries their sum instead
+            assert 0 <= lo and hi <= n and lo % 4 == 0 and hi % 4 == 0 and int(o['r'][2]['buf']) >= 0
+            x = np.concatenate([x[:lo], x[hi:]])
+        total = (x * x).sum()
+        if n_extra > 0:
+            assert int(o['r'][2]['buf']) >= 0 and int(o['r'][3]['off']) % 16 == 0
+            total += self.fview(o['r'][3], n_extra).astype(np.float64).sum()
+        out = self.fview(o['r'][0], 1)
+        out[0] = np.float32(float(out[0]) + total)
 
     def op_adamw(self, o, problems):
         n = int(o['i'][0])
@@ -127,7 +135,9 @@ class Interp:
     def to16(x, bf16):
         x = np.ascontiguousarray(x, dtype=np.float32)
         if not bf16:
-            return x.astype(np.float16).view(np.uint16)
+            # cast_f16 (elementwise.hip) saturates at the largest finite f16 instead of rounding to infinity; NaN stays NaN
+            with np.errstate(invalid='ignore'):
+                return np.clip(x, np.float32(-65504.0), np.float32(65504.0)).astype(np.float16).view(np.uint16)
         u = x.view(np.uint32).astype(np.uint64)
         return (((u + 0x7fff + ((u >> 16) & 1)) >> 16) & 0xffff).astype(np.uint16)
 
@@ -232,7 +242,9 @@ class Interp:
                 q, s_ = int(D['bias_q']), int(D['bias_s'])
                 if q > 0:
                     c = (c // q) * s_ + c % q
-                np.add.at(dbias, c + int(D['bias_off']), Xsum.astype(np.float64).sum(0).astype(np.float32))
+                at = c + int(D['bias_off'])           # (a float64 sum added once: one rounding to the float32 buffer)
+                assert len(np.unique(at)) == len(at)
+                dbias[at] = (dbias[at].astype(np.float64) + Xsum.astype(np.float64).sum(0)).astype(np.float32)
         assert nb == blocks
 
     def _gemm_op16(self, o, p):
@@ -296,12 +308,39 @@ class Interp:
         ah, al = ah.astype(np.float64), al.astype(np.float64)
         self._gemm_finish(p, None, None, prod=ah @ bh + (ah @ bl + al @ bh))
 
+    XCD_B_BYTES = 5 << 19          # runtime.hip: budget of B per XCD in the tile order of the persistent kernels
+
+    def _persistent_tile_ids(self, p, bn, start):
+        """Tile ids of a tile code 25 / 29 / 30 problem inside its launch (runtime.hip + gemm_h16w_kernel's `setup`): the 8 XCDs
+        form a (8 / G) x G grid, id = start + 8 * group + x names row tile (group / npg) * (8 / G) + x / G and column tile
+        (x % G) * npg + group % npg; ids beyond the problem's tiles name nothing.  -> ({(mt, nt): id}, ids used)."""
+        M, N, K = int(p['M']), int(p['N']), int(p['K'])
+        tm, tn = (M + 255) // 256, (N + bn - 1) // bn
+        G = 1
+        while G < 8 and N * K * 2 // G > self.XCD_B_BYTES and tn >= 2 * G:
+            G *= 2
+        npg, mpc = (tn + G - 1) // G, (tm + 8 // G - 1) // (8 // G)
+        ids = {}
+        for tl in range(8 * npg * mpc):
+            x, grp = tl & 7, tl >> 3
+            nt, mt = (x % G) * npg + grp % npg, (grp // npg) * (8 // G) + x // G
+            if nt < tn and mt < tm:
+                ids[(mt, nt)] = start + tl
+        return ids, 8 * npg * mpc
+
     def op_gemm(self, o, problems):
         first, cnt = int(o['i'][0]), int(o['i'][1])
+        sq_start = 0
         for p in problems[first:first + cnt]:
             M, N, K = int(p['M']), int(p['N']), int(p['K'])
             if M <= 0 or N <= 0:
                 continue
+            sq_tiles = None
+            if int(p['flags']) & L.GEMM_OP16 and int(o['i'][2]) in (29, 30):
+                bn = 128 if int(o['i'][2]) == 30 else 256
+                ids, used = self._persistent_tile_ids(p, bn, sq_start)
+                sq_start += used
+                sq_tiles = (bn, ids)
             if int(p['flags']) & L.GEMM_X3:
                 self._gemm_x3(p, int(o['i'][2]))
                 continue
@@ -318,7 +357,7 @@ class Interp:
                         assert np.all(A[kk >= ext[:, None] * np.ones_like(kk)] == 0)
                     else:
                         col_ext = ext           # columns >= ext[row] are don't-care: the interpreter leaves them
-                self._gemm_finish(p, A, Bm, col_ext)
+                self._gemm_finish(p, A, Bm, col_ext, sq_tiles=sq_tiles)
                 continue
             lda, ldb, ldc = int(p['lda']), int(p['ldb']), int(p['ldc'])
             XA, XB, Y = self.tail(p['A'], np.float32), self.tail(p['B'], np.float32), self.tail(p['C'], np.float32)
@@ -374,7 +413,7 @@ class Interp:
                 P[5][idx] = out.astype(np.float32)
         return out.astype(np.float32)
 
-    def _gemm_finish(self, p, A, Bm, col_ext=None, prod=None):
+    def _gemm_finish(self, p, A, Bm, col_ext=None, prod=None, sq_tiles=None):
         if True:
             M, N = int(p['M']), int(p['N'])
             ldc = int(p['ldc'])
@@ -399,9 +438,18 @@ class Interp:
                 stride = int(p['bias_stride']) or 1
                 v = v + bias[bi * stride].astype(np.float64)[None, :]
             if int(p['flags']) & getattr(L, 'GEMM_SUMSQ', 16):
-                # GHN3_GEMM_SUMSQ: the slots of the table add up to the sum of the squares stored (the kernel's slot of a
-                # value is an implementation detail: here every problem adds into slot 0)
-                self.tail(p['aux_out'], np.float32)[0] += np.float32((v.astype(np.float32).astype(np.float64) ** 2).sum())
+                # GHN3_GEMM_SUMSQ: the slots of the table add up to the sum of the squares stored.  With the tile ids of the
+                # launch (`sq_tiles`, op_gemm) every tile's sum goes to the slot of wave 0 of its id, the other seven waves'
+                # slots get 0 and ids that name no tile are left alone; without them every problem adds into slot 0.
+                sq = v.astype(np.float32).astype(np.float64) ** 2
+                slots = self.tail(p['aux_out'], np.float32)
+                if sq_tiles is None:
+                    slots[0] += np.float32(sq.sum())
+                else:
+                    bn, ids = sq_tiles
+                    for (mt, nt), t in ids.items():
+                        slots[8 * t:8 * t + 8] = 0
+                        slots[8 * t] = np.float32(sq[mt * 256:(mt + 1) * 256, nt * bn:(nt + 1) * bn].sum())
             elif int(p['aux_out']['buf']) >= 0:
                 self.tail(p['aux_out'], np.float32)[ci] = v.astype(np.float32)
             act = int(p['act'])
