@@ -2190,6 +2190,8 @@ int ghn3_sumsq(float* out, const float* x, int64_t n, float* parts, int64_t skip
             ghn3_set_error("sumsq: a skipped range needs the scratch buffer, 4-float alignment and 0 <= lo <= hi <= n");
             return GHN3_E_ARG;
         }
+        // (refused before anything is launched: the partial sums of the two ranges must not be left behind a failed op)
+        if (n_extra > 0 && (reinterpret_cast<uintptr_t>(extra) & 15)) { ghn3_set_error("sumsq: slot table must be 16-byte aligned"); return GHN3_E_ARG; }
     }
     auto blocks_of = [](int64_t m) { int64_t b = (m / 4 + 255) / 256; return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b)); };
     if (!skip && n_extra <= 0) {
@@ -2211,7 +2213,6 @@ int ghn3_sumsq(float* out, const float* x, int64_t n, float* parts, int64_t skip
         hipLaunchKernelGGL(sumsq_kernel, dim3(b1), dim3(256), 0, s, out, x + hi, n - hi, parts + b0);
     }
     if (n_extra > 0) {
-        if (reinterpret_cast<uintptr_t>(extra) & 15) { ghn3_set_error("sumsq: slot table must be 16-byte aligned"); return GHN3_E_ARG; }
         b2 = 64;
         hipLaunchKernelGGL(slot_sum_kernel, dim3(b2), dim3(256), 0, s, parts + b0 + b1, extra, n_extra);
     }

@@ -389,7 +389,8 @@ enum ghn3_op_kind {
      *        r4 = squared gradient norm or absent, f0 = max_norm (<= 0: no clipping): the gradient is scaled by
      *        min(1, max_norm / (norm + 1e-6)); a non-finite r4 skips the whole update (NaN guard, trainer.py:240-257);
      *        f1 = 1 / loss scale (0 = 1): the gradients arrive multiplied by the AMP loss scale (trainer.py:346-352); i1..i7 = IEEE-754 double bit patterns of lr, beta1, beta2, eps,
-     *        weight_decay, 1 - beta1^t, 1 - beta2^t */
+     *        weight_decay, 1 - beta1^t, 1 - beta2^t.  The kernels work in fp32: the seven values are rounded to float on entry
+     *        and 1 - beta is formed from the rounded beta (beta2 = 0.999: the float 1 - beta2 is 1.3e-5 away from 0.001) */
     GHN3_OP_SUMSQ = 26,
     GHN3_OP_ADAMW = 27,
     /* ReLU of the classifier tiles (nn.py:755-758 `relu(x)` in front of class_layer_predictor) with EXACT masks in the

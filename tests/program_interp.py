@@ -105,21 +105,144 @@ class Interp:
         out = self.fview(o['r'][0], 1)
         out[0] = np.float32(float(out[0]) + total)
 
-    def op_adamw(self, o, problems):
-        n = int(o['i'][0])
-        lr, b1, b2, eps, wd, bc1, bc2 = (float(v) for v in o['i'][1:8].view(np.float64))
-        p, g, m, v = (self.fview(o['r'][k], n) for k in range(4))
+    def _adamw_clip(self, o):
+        """(hyper-parameters as the op takes them: doubles rounded to float on entry, factor on the gradient or None when the
+        NaN guard skips the update)"""
+        hyp = tuple(float(np.float32(v)) for v in o['i'][1:8].view(np.float64))
         inv = float(o['f'][1]) if float(o['f'][1]) > 0 else 1.0
         clip = inv
         if int(o['r'][4]['buf']) >= 0:
-            if not np.isfinite(self.fview(o['r'][4], 1)[0]):
-                return
+            ss = self.fview(o['r'][4], 1)[0]
+            if not np.isfinite(ss):
+                return hyp, None
             if float(o['f'][0]) > 0:
-                clip *= min(1.0, float(o['f'][0]) / (float(np.sqrt(self.fview(o['r'][4], 1)[0])) * inv + 1e-6))
+                clip = inv * min(1.0, float(o['f'][0]) / (float(np.sqrt(np.float64(ss))) * inv + float(np.float32(1e-6))))
+        return hyp, clip
+
+    @staticmethod
+    def _adamw_update(p, g, m, v, hyp, clip):
+        """float64 AdamW on float32 arrays -> new (p, m, v) in float32; p takes the unrounded moments"""
+        lr, b1, b2, eps, wd, bc1, bc2 = hyp
         gi = g.astype(np.float64) * clip
-        m[:] = b1 * m + (1 - b1) * gi
-        v[:] = b2 * v + (1 - b2) * gi * gi
-        p[:] = p * (1 - lr * wd) - (lr / bc1) * m / (np.sqrt(v) / np.sqrt(bc2) + eps)
+        m2 = b1 * m.astype(np.float64) + (1.0 - b1) * gi
+        v2 = b2 * v.astype(np.float64) + (1.0 - b2) * gi * gi
+        p2 = p.astype(np.float64) * (1.0 - lr * wd) - (lr / bc1) * m2 / (np.sqrt(v2) / np.sqrt(bc2) + eps)
+        return p2.astype(np.float32), m2.astype(np.float32), v2.astype(np.float32)
+
+    def op_adamw(self, o, problems):
+        n = int(o['i'][0])
+        hyp, clip = self._adamw_clip(o)
+        if clip is None:
+            return
+        p, g, m, v = (self.fview(o['r'][k], n) for k in range(4))
+        p[:], m[:], v[:] = self._adamw_update(p, g, m, v, hyp, clip)
+
+    def _cast_elements(self, o):
+        """flat element offsets (from r0) of every source element of the descriptor table r6, descriptor by descriptor"""
+        n_desc = int(o['i'][0]) & 0xffffffff
+        descs = self.view(o['r'][6], L.CAST_DT, n_desc)
+        el = []
+        for D in descs:
+            assert int(D['cols']) % 4 == 0 and int(D['ld_src']) % 4 == 0 and int(D['src_off']) % 4 == 0 and int(D['src_q']) == 0
+            assert not int(D['flags']) & (L.CAST_SCALED | L.CAST_COLSUM | L.CAST_SRC16)
+            el.append((int(D['src_off']) + np.arange(int(D['rows']))[:, None] * int(D['ld_src']) + np.arange(int(D['cols']))[None, :]).reshape(-1))
+        el = np.concatenate(el)
+        assert len(np.unique(el)) == len(el), 'a source element in two descriptors'
+        return el
+
+    def _cast_after_adamw(self, o, problems):
+        c = np.zeros(1, dtype=L.OP_DT)
+        c['r']['buf'][:] = -1
+        c['kind'] = L.OP_CAST16
+        for dst, src in ((0, 0), (1, 5), (2, 6)):
+            c['r']['buf'][0][dst], c['r']['off'][0][dst] = int(o['r'][src]['buf']), int(o['r'][src]['off'])
+        c['i'][0][0], c['i'][0][1] = int(o['i'][0]) & 0xffffffff, int(o['i'][0]) >> 32
+        self.op_cast16(c[0], problems)
+
+    def op_adamw_cast16(self, o, problems):
+        hyp, clip = self._adamw_clip(o)
+        if clip is None:
+            return
+        el = self._cast_elements(o)
+        p, g, m, v = (self.tail(o['r'][k], np.float32) for k in range(4))
+        p[el], m[el], v[el] = self._adamw_update(p[el], g[el], m[el], v[el], hyp, clip)
+        self._cast_after_adamw(o, problems)
+
+    def _adamw_s16(self, o, el):
+        """the bf16-state update of the elements `el` (offsets from the op's references) by the package's own restatement"""
+        import torch
+        from ghn3_amd.optim import adamw_state16_reference_
+        hyp = tuple(float(v) for v in o['i'][1:8].view(np.float64))
+        step, seed = int(o['f'][2]), int(o['f'][3])
+        assert abs((1.0 - hyp[1] ** step) - hyp[5]) < 1e-15 and abs((1.0 - hyp[2] ** step) - hyp[6]) < 1e-15
+        assert int(o['r'][2]['off']) % 2 == 0 and int(o['r'][2]['off']) == int(o['r'][3]['off'])
+        base = int(o['r'][2]['off']) // 2
+        p, g = self.tail(o['r'][0], np.float32), self.tail(o['r'][1], np.float32)
+        m, v = self.tail(o['r'][2], np.uint16), self.tail(o['r'][3], np.uint16)
+        ss = self.fview(o['r'][4], 1)[0] if int(o['r'][4]['buf']) >= 0 else None
+        # (the restatement takes a contiguous range: elements are handed over one run of consecutive indices at a time)
+        cuts = np.nonzero(np.diff(el) != 1)[0] + 1
+        for run in np.split(el, cuts):
+            a, b = int(run[0]), int(run[-1]) + 1
+            tp, tg = torch.from_numpy(p[a:b].copy()), torch.from_numpy(g[a:b].copy())
+            tm = torch.from_numpy(m[a:b].copy().view(np.int16)).view(torch.bfloat16)
+            tv = torch.from_numpy(v[a:b].copy().view(np.int16)).view(torch.bfloat16)
+            adamw_state16_reference_(tp, tg, tm, tv, ss, step, hyp[0], (hyp[1], hyp[2]), hyp[3], hyp[4], float(o['f'][0]),
+                                     float(o['f'][1]), seed=seed, base=base + a)
+            p[a:b] = tp.numpy()
+            m[a:b] = tm.view(torch.int16).numpy().view(np.uint16)
+            v[a:b] = tv.view(torch.int16).numpy().view(np.uint16)
+
+    def op_adamw_s16(self, o, problems):
+        if int(o['i'][0]) > 0:
+            self._adamw_s16(o, np.arange(int(o['i'][0])))
+
+    def op_adamw_s16_cast16(self, o, problems):
+        if int(o['r'][4]['buf']) >= 0 and not np.isfinite(self.fview(o['r'][4], 1)[0]):
+            return
+        self._adamw_s16(o, self._cast_elements(o))
+        self._cast_after_adamw(o, problems)
+
+    @staticmethod
+    def wire_bf16(x):
+        """round to nearest even; a NaN stays a NaN with its sign (the quiet bit is set: a payload in the low half alone would
+        otherwise round to an infinity)"""
+        u = np.ascontiguousarray(x, np.float32).view(np.uint32).astype(np.uint64)
+        r = ((u + 0x7fff + ((u >> 16) & 1)) >> 16) & 0xffff
+        nan = (u & 0x7fffffff) > 0x7f800000
+        return np.where(nan, (u >> 16) | 0x40, r).astype(np.uint16)
+
+    def op_wire_pack(self, o, problems):
+        n, n_pad, reverse = (int(v) for v in o['i'][:3])
+        if reverse:
+            if n > 0:
+                src = self.tail(o['r'][1], np.uint16)[:n]
+                self.tail(o['r'][0], np.uint32)[:n] = src.astype(np.uint32) << 16
+            return
+        if n_pad <= 0:
+            return
+        assert n_pad >= n, 'wire_pack: padded length below the valid length (GHN3_E_ARG)'
+        dst = self.tail(o['r'][0], np.uint16)
+        dst[:n] = self.wire_bf16(self.tail(o['r'][1], np.float32)[:n])
+        dst[n:n_pad] = 0
+
+    def op_rank_reduce(self, o, problems):
+        per, W, in16, out16 = (int(v) for v in o['i'][:4])
+        if per <= 0 or W <= 0:
+            return
+        if in16:
+            X = (self.tail(o['r'][1], np.uint16)[:W * per].astype(np.uint32) << 16).view(np.float32)
+        else:
+            X = self.tail(o['r'][1], np.float32)[:W * per]
+        acc = np.zeros(per, np.float32)
+        with np.errstate(invalid='ignore', over='ignore'):
+            for w in range(W):                               # fp32, rank order: what every rank computes
+                acc = acc + X[w * per:(w + 1) * per]
+            res = acc * np.float32(o['f'][0])
+        if out16:
+            self.tail(o['r'][0], np.uint16)[:per] = self.wire_bf16(res)
+        else:
+            self.tail(o['r'][0], np.float32)[:per] = res
 
     @staticmethod
     def _rowmap(r, g, q, s):
@@ -880,6 +1003,8 @@ class Interp:
 
     def op_memset0(self, o, problems):
         n = int(o['i'][0])
+        if int(o['r'][0]['buf']) < 0:                        # an absent buffer: nothing happens (runtime.hip)
+            return
         b = self.bufs[int(o['r'][0]['buf'])]
         off = int(o['r'][0]['off'])
         if n > 0:                                            # (unpatched placeholders carry -1: skipped, runtime.hip)
