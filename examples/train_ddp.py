@@ -6,6 +6,7 @@ parameters predicted by a GHN-3 checkpoint (--ckpt) plus a little noise (--beta)
 
     python examples/train_ddp.py --ckpt ghn3xlm16.pt [--lr 0.025] [--wd 3e-5] [--momentum 0.9] [--label_smooth 0.1]
                                  [--beta 1e-5] [--amp] [--arch resnet|genotype] [--steps 30] [--epochs 2] [--save DIR]
+                                 [--native-layers]
 
 Without --ckpt the network keeps its own initialisation.  The optimizer step is the fused multi-tensor SGD (ghn3_amd.FusedSGD);
 GHN3_FUSED_SGD=0 runs stock clip_grad_norm_ + torch.optim.SGD instead.  One GPU: the plain branch has no data-parallel path yet.
@@ -82,6 +83,8 @@ def main():
     ap.add_argument('--epochs', type=int, default=2)
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--save', default=None)
+    ap.add_argument('--native-layers', action='store_true',
+                    help='run the conv-norm-ReLU, pooling and head layers on the native nodes (ghn3_amd.nativize)')
     args = ap.parse_args()
 
     from ghn3_amd import Trainer, log
@@ -91,7 +94,7 @@ def main():
     trainer = Trainer(model, opt='sgd', opt_args={'lr': args.lr, 'weight_decay': args.wd, 'momentum': args.momentum},
                       scheduler='cosine', n_batches=args.steps, grad_clip=5, device='cuda', log_interval=10,
                       label_smoothing=args.label_smooth, save_dir=args.save, ckpt=args.ckpt, epochs=args.epochs, amp=args.amp,
-                      beta=args.beta)
+                      beta=args.beta, native_layers=args.native_layers)
     log('training %s (%d parameters in %d tensors), %d x %d images per step'
         % (type(model).__name__, sum(p.numel() for p in model.parameters()), len(list(model.parameters())), args.batch_size, 32))
     gen = torch.Generator().manual_seed(args.seed + 1)

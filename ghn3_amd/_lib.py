@@ -82,7 +82,9 @@ EXPORTS = ['ghn3_abi_version', 'ghn3_last_error', 'ghn3_ctx_create', 'ghn3_ctx_d
            'ghn3_attn_lean_fwd', 'ghn3_attn_lean_bwd', 'ghn3_msa_lean_scratch_floats', 'ghn3_msa_lean_fwd', 'ghn3_msa_lean_bwd',
            'ghn3_dw_scratch_floats', 'ghn3_dw_fwd', 'ghn3_dw_bwd', 'ghn3_patch_scratch_floats', 'ghn3_patch_fwd', 'ghn3_patch_bwd',
            'ghn3_attn_wide_fwd', 'ghn3_attn_wide_bwd', 'ghn3_msa_wide_scratch_floats', 'ghn3_msa_wide_fwd', 'ghn3_msa_wide_bwd',
-           'ghn3_mt_sumsq', 'ghn3_mt_sgd']
+           'ghn3_mt_sumsq', 'ghn3_mt_sgd',
+           'ghn3_conv_act_scratch_floats', 'ghn3_conv_bn_act_fwd', 'ghn3_conv_bn_act_bwd', 'ghn3_conv_frozen_act_fwd',
+           'ghn3_conv_frozen_act_bwd']
 OPFLAG_TIMED = 0x100
 OPFLAG_SIDE = 0x200
 
@@ -153,6 +155,12 @@ def load():
         lib.ghn3_conv_scratch_floats.restype = ctypes.c_int64
         lib.ghn3_conv_bn_fwd.argtypes = [ctypes.c_void_p] * 10
         lib.ghn3_conv_bn_bwd.argtypes = [ctypes.c_void_p] * 13
+        lib.ghn3_conv_act_scratch_floats.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        lib.ghn3_conv_act_scratch_floats.restype = ctypes.c_int64
+        lib.ghn3_conv_bn_act_fwd.argtypes = [ctypes.c_void_p] * 11
+        lib.ghn3_conv_bn_act_bwd.argtypes = [ctypes.c_void_p] * 15
+        lib.ghn3_conv_frozen_act_fwd.argtypes = [ctypes.c_void_p] * 12
+        lib.ghn3_conv_frozen_act_bwd.argtypes = [ctypes.c_void_p] * 16
         lib.ghn3_se_fwd.argtypes = [ctypes.c_int] * 4 + [ctypes.c_void_p] * 8
         lib.ghn3_se_bwd.argtypes = [ctypes.c_int] * 4 + [ctypes.c_void_p] * 12
         lib.ghn3_pool_fwd.argtypes = [ctypes.c_void_p] * 5

@@ -42,6 +42,9 @@
 // known before the launch, so the forward applies it to its accumulators in the epilogue -- no statistics, no second pass --
 // and the backward has dz = dout gamma rstd without the two batch-mean terms; dgamma / dbeta come from bn_bwd_partial +
 // reduce_rows on the frozen (mean, rstd).
+// With the ReLU BEHIND the norm layer and an optional skip tensor in between (ghn3_conv_bn_act_*, ghn3_conv_frozen_act_*: the
+// layer order of ResNet-shaped torch.nn networks): sibling kernels of bn_apply, bn_bwd_partial and the dz pass (tnet_bn_act_apply,
+// tnet_bn_act_bwd_partial, tnet_dz_act) around the unchanged convolution, weight-gradient and reduction kernels.
 
 #include <algorithm>
 #include "tnet_common.h"
@@ -345,6 +348,34 @@ __global__ __launch_bounds__(256) void tnet_bn_apply_kernel(const float* __restr
     }
 }
 
+// The "act" member of the dense-convolution family (conv -> BatchNorm [-> + skip] -> ReLU, the layer order of ResNet-shaped
+// networks): tnet_bn_apply_kernel with the skip tensor `res` [P][C] (null: none) added behind the affine map -- torch's order: norm,
+// add, clamp -- and the result clamped at zero as torch's ReLU does (a NaN stays one).  Nothing of activation size is read
+// beyond z and res.
+constexpr int ACT_GRID_CAP = 2048;                                             // workgroups of the two flat kernels of the member
+__global__ __launch_bounds__(256) void tnet_bn_act_apply_kernel(const float* __restrict__ z, const float* __restrict__ stats,
+                                                                const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                const float* __restrict__ res, float* __restrict__ out,
+                                                                int64_t total4, int C) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (int64_t)gridDim.x * 256) {
+        const int c = (int)((i * 4) % C);
+        const f32x4 v = *reinterpret_cast<const f32x4*>(z + i * 4);
+        const f32x4 mu = *reinterpret_cast<const f32x4*>(stats + c), rs = *reinterpret_cast<const f32x4*>(stats + C + c);
+        const f32x4 ga = *reinterpret_cast<const f32x4*>(gamma + c), be = *reinterpret_cast<const f32x4*>(beta + c);
+        f32x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = (v[e] - mu[e]) * rs[e] * ga[e] + be[e];
+        if (res) {
+            const f32x4 r = *reinterpret_cast<const f32x4*>(res + i * 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] += r[e];
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = o[e] <= 0.f ? 0.f : o[e];
+        *reinterpret_cast<f32x4*>(out + i * 4) = o;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // backward
 // ---------------------------------------------------------------------------------------------------------------------
@@ -379,6 +410,60 @@ __global__ __launch_bounds__(256) void tnet_bn_bwd_partial_kernel(const float* _
         const f32x4 mu = *reinterpret_cast<const f32x4*>(stats + c), rs = *reinterpret_cast<const f32x4*>(stats + C + c);
         for (int p = p0 + g; p < p1; p += ng) {
             const f32x4 gd = *reinterpret_cast<const f32x4*>(dout + (int64_t)p * C + c);
+            const f32x4 zz = *reinterpret_cast<const f32x4*>(z + (int64_t)p * C + c);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { s1[e] += gd[e]; s2[e] += gd[e] * (zz[e] - mu[e]) * rs[e]; }
+        }
+        *reinterpret_cast<f32x4*>(red + (g * 2) * C + c) = s1;
+        *reinterpret_cast<f32x4*>(red + (g * 2 + 1) * C + c) = s2;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 2 * C; i += 256) {
+        float s = 0.f;
+        for (int k = 0; k < ng; ++k) s += red[k * 2 * C + i];
+        part[(int64_t)blockIdx.x * 2 * C + i] = s;
+    }
+}
+
+// The same sums behind the ReLU of the "act" member: the upstream gradient is g = dout 1[out > 0], masked where it is read (torch
+// masks on the ReLU's RESULT); `out` [P][C] is the forward's result.  Geometry, LDS and summation order of the kernel above, in
+// both of its arms.
+__device__ __forceinline__ f32x4 act_masked(const f32x4 g, const f32x4 o) {
+    f32x4 m;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) m[e] = o[e] > 0.f ? g[e] : 0.f;
+    return m;
+}
+__global__ __launch_bounds__(256) void tnet_bn_act_bwd_partial_kernel(const float* __restrict__ dout, const float* __restrict__ out,
+                                                                      const float* __restrict__ z, const float* __restrict__ stats,
+                                                                      float* __restrict__ part, int P, int C) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    float* red = reinterpret_cast<float*>(smem);                               // [ng][2][C]
+    const int nq = C / 4, ng = max(1, 256 / nq);
+    const int g = threadIdx.x / nq, q = threadIdx.x % nq, c = 4 * q;
+    const int p0 = blockIdx.x * TP, p1 = min(P, p0 + TP);
+    if (nq > 256) {
+        for (int cw = 4 * threadIdx.x; cw < C; cw += 1024) {
+            f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = s1;
+            const f32x4 mu = *reinterpret_cast<const f32x4*>(stats + cw), rs = *reinterpret_cast<const f32x4*>(stats + C + cw);
+            for (int p = p0; p < p1; ++p) {
+                const f32x4 gd = act_masked(*reinterpret_cast<const f32x4*>(dout + (int64_t)p * C + cw),
+                                            *reinterpret_cast<const f32x4*>(out + (int64_t)p * C + cw));
+                const f32x4 zz = *reinterpret_cast<const f32x4*>(z + (int64_t)p * C + cw);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { s1[e] += gd[e]; s2[e] += gd[e] * (zz[e] - mu[e]) * rs[e]; }
+            }
+            *reinterpret_cast<f32x4*>(part + (int64_t)blockIdx.x * 2 * C + cw) = s1;
+            *reinterpret_cast<f32x4*>(part + (int64_t)blockIdx.x * 2 * C + C + cw) = s2;
+        }
+        return;
+    }
+    if (g < ng) {
+        f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = s1;
+        const f32x4 mu = *reinterpret_cast<const f32x4*>(stats + c), rs = *reinterpret_cast<const f32x4*>(stats + C + c);
+        for (int p = p0 + g; p < p1; p += ng) {
+            const f32x4 gd = act_masked(*reinterpret_cast<const f32x4*>(dout + (int64_t)p * C + c),
+                                        *reinterpret_cast<const f32x4*>(out + (int64_t)p * C + c));
             const f32x4 zz = *reinterpret_cast<const f32x4*>(z + (int64_t)p * C + c);
 #pragma unroll
             for (int e = 0; e < 4; ++e) { s1[e] += gd[e]; s2[e] += gd[e] * (zz[e] - mu[e]) * rs[e]; }
@@ -850,13 +935,19 @@ __global__ __launch_bounds__(256) void tnet_bn_frozen_stats_kernel(const float* 
 // Step 1 of the backward of a norm layer: dbeta = sum dout, dgamma = sum dout xhat over the P pixels (per-tile partials, then a
 // fixed-order reduction).  *s12_out = where the reduced pair [sum dout | sum dout xhat] lies: dbeta directly followed by dgamma --
 // how target_ops.py lays them out -- IS that pair (no copies); otherwise it is reduced into s12_scratch and copied out.
+// act_out != null (the "act" member): the sums of dout 1[act_out > 0], by the sibling kernel in the same launch slot.
 int bn_param_grads(const float* dout, const float* z, const float* stats, float* part12, float* s12_scratch, float* dgamma,
-                   float* dbeta, int n_tiles, int P, int C, hipStream_t s, const float** s12_out) {
+                   float* dbeta, int n_tiles, int P, int C, hipStream_t s, const float** s12_out, const float* act_out = nullptr) {
     const bool in_place = dgamma == dbeta + C;
     float* s12 = in_place ? dbeta : s12_scratch;
     const int nq = C / 4, ng = std::max(1, 256 / nq);
-    hipLaunchKernelGGL(tnet_bn_bwd_partial_kernel, dim3(n_tiles), dim3(256), nq > 256 ? 0 : (size_t)ng * 2 * C * 4, s, dout, z, stats,
-                       part12, P, C);
+    if (act_out) {                                                 // (the "act" member: dout masked by its result, in the same launch)
+        hipLaunchKernelGGL(tnet_bn_act_bwd_partial_kernel, dim3(n_tiles), dim3(256), nq > 256 ? 0 : (size_t)ng * 2 * C * 4, s, dout, act_out,
+                           z, stats, part12, P, C);
+    } else {
+        hipLaunchKernelGGL(tnet_bn_bwd_partial_kernel, dim3(n_tiles), dim3(256), nq > 256 ? 0 : (size_t)ng * 2 * C * 4, s, dout, z, stats,
+                           part12, P, C);
+    }
     TNET_LAUNCH_CHECK("bn bwd partial")
     const int rc = reduce_rows(part12, n_tiles, (int64_t)2 * C, s12, 0, 0, s, "bn bwd reduce");
     if (rc) return rc;
@@ -1227,6 +1318,36 @@ __global__ __launch_bounds__(256) void tnet_dz_kernel(const float* __restrict__ 
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (int64_t)gridDim.x * 256) {
         const int c = (int)((i * 4) % C);
         const f32x4 g = *reinterpret_cast<const f32x4*>(dout + 4 * i);
+        const f32x4 rs = *reinterpret_cast<const f32x4*>(stats + C + c), ga = *reinterpret_cast<const f32x4*>(gamma + c);
+        f32x4 o;
+        if constexpr (BATCH) {
+            const f32x4 zz = *reinterpret_cast<const f32x4*>(z + 4 * i), mu = *reinterpret_cast<const f32x4*>(stats + c);
+            const f32x4 a1 = *reinterpret_cast<const f32x4*>(s12 + c), a2 = *reinterpret_cast<const f32x4*>(s12 + C + c);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float xh = (zz[e] - mu[e]) * rs[e];
+                o[e] = ga[e] * rs[e] * (g[e] - a1[e] * invP - xh * a2[e] * invP);
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = ga[e] * rs[e] * g[e];
+        }
+        *reinterpret_cast<f32x4*>(dz + 4 * i) = o;
+    }
+}
+
+// dz of the "act" member: tnet_dz_kernel on g = dout 1[out > 0], the mask applied as dout is read; the same pass writes the
+// skip tensor's gradient dres = g when dres is non-null.  s12 holds the sums of the MASKED gradient (tnet_bn_act_bwd_partial_kernel).
+template <bool BATCH = true>
+__global__ __launch_bounds__(256) void tnet_dz_act_kernel(const float* __restrict__ dout, const float* __restrict__ out,
+                                                          const float* __restrict__ z, const float* __restrict__ stats,
+                                                          const float* __restrict__ gamma, const float* __restrict__ s12,
+                                                          float* __restrict__ dz, float* __restrict__ dres, int64_t total4, int C, int P) {
+    const float invP = 1.f / (float)P;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (int64_t)gridDim.x * 256) {
+        const int c = (int)((i * 4) % C);
+        const f32x4 g = act_masked(*reinterpret_cast<const f32x4*>(dout + 4 * i), *reinterpret_cast<const f32x4*>(out + 4 * i));
+        if (dres) *reinterpret_cast<f32x4*>(dres + 4 * i) = g;
         const f32x4 rs = *reinterpret_cast<const f32x4*>(stats + C + c), ga = *reinterpret_cast<const f32x4*>(gamma + c);
         f32x4 o;
         if constexpr (BATCH) {
@@ -1667,6 +1788,141 @@ extern "C" int ghn3_conv_frozen_bwd(const ghn3_conv_desc* g, const float* dout, 
                                     float* dbeta, float* scratch, void* stream_) {
     return conv_bwd_core(g, true, "conv frozen bwd", dout && x && w && dx && dw && scratch, z && gamma && mean && var && dgamma && dbeta, dout,
                          x, z, nullptr, w, gamma, mean, var, dx, dw, dgamma, dbeta, scratch, stream_);
+}
+
+// ---- the "act" member: [ReLU ->] convolution -> BatchNorm [-> + skip] -> ReLU, the layer order of ResNet-shaped networks --------
+//   out = relu((z - mean) rstd gamma + beta [+ res]),  z = conv(relu(x) if desc->relu else x, w)
+// Forward, batch statistics: the launches of ghn3_conv_bn_fwd with tnet_bn_act_apply_kernel as the last one (4: weight pack,
+// convolution + per-tile statistics, finalize, apply).  Frozen statistics: the convolution ALONE (the kernel of the batch member:
+// its frozen epilogue knows neither skip nor clamp and is not touched), (mean, var) -> (mean, rstd), then the same apply kernel
+// (4).  Backward: g = dout 1[out > 0] is never materialised -- the mask is applied where dout is first read, in the per-tile
+// partial sums (tnet_bn_act_bwd_partial_kernel) and in the pass that writes dz (tnet_dz_act_kernel), which writes dres = g as
+// well --, then conv_bwd_products as for every member: the launches of ghn3_conv_bn_bwd / ghn3_conv_frozen_bwd, none more.
+// Saved between the directions: x, z, out (the next layer's input), stats.
+// Scratch (ghn3_conv_act_scratch_floats, mode = backward | 2 frozen): the layouts of the members without the ReLU, except the frozen
+// forward = the batch member's forward layout (the convolution leaves its per-tile statistics there; they are not read) followed
+// by the (mean, rstd) pair.
+namespace {
+
+struct ActScratch { CScratch sc; int64_t total; };
+
+ActScratch conv_act_scratch(const CDesc& d, const CPlan& pl, bool frozen, bool backward) {
+    ActScratch a;
+    a.sc = conv_scratch(d, pl, frozen && backward, backward);
+    a.total = a.sc.total;
+    if (frozen && !backward) { a.sc.stats = a.total; a.total += 2 * d.C_out; }
+    return a;
+}
+
+int check_act_desc(const ghn3_conv_desc* g, CDesc& d, const char* who) {
+    const int rc = check_cdesc(g, d);
+    if (rc) return rc;
+    if (g->relu & GHN3_CONV_NO_NORM) { ghn3_set_error("%s: GHN3_CONV_NO_NORM has no meaning here", who); return GHN3_E_ARG; }
+    return GHN3_OK;
+}
+
+// the last launch of both forwards
+int act_apply_launch(const CPlan& pl, int C, const float* z, const float* stats, const float* gamma, const float* beta, const float* res,
+                     float* out, hipStream_t s) {
+    const int64_t total4 = (int64_t)pl.P * C / 4;
+    hipLaunchKernelGGL(tnet_bn_act_apply_kernel, grid1d(total4, ACT_GRID_CAP), dim3(256), 0, s, z, stats, gamma, beta, res, out, total4, C);
+    TNET_LAUNCH_CHECK("bn act apply")
+    return GHN3_OK;
+}
+
+// The backward of both: `stats` = (mean, rstd) of the batch, or null with the frozen (mean, var) given.
+int conv_act_bwd_core(const ghn3_conv_desc* g, bool frozen, const char* who, bool required, const float* dout, const float* out,
+                      const float* x, const float* z, const float* stats, const float* w, const float* gamma, const float* mean,
+                      const float* var, float* dx, float* dw, float* dgamma, float* dbeta, float* dres, float* scratch, void* stream_) {
+    CDesc d;
+    int rc = check_act_desc(g, d, who);
+    if (rc) return rc;
+    if (!required) { ghn3_set_error("%s: null pointer", who); return GHN3_E_ARG; }
+    hipStream_t s = (hipStream_t)stream_;
+    const CPlan pl = make_cplan(d);
+    const CScratch sc = conv_act_scratch(d, pl, frozen, true).sc;
+    if (frozen) {
+        rc = frozen_stats(mean, var, d.eps, d.C_out, scratch + sc.stats, s);
+        if (rc) return rc;
+        stats = scratch + sc.stats;
+    }
+    // 1. dgamma / dbeta from the masked gradient
+    const float* s12;
+    rc = bn_param_grads(dout, z, stats, scratch + sc.part, scratch + sc.s12, dgamma, dbeta, pl.n_tiles, pl.P, d.C_out, s, &s12, out);
+    if (rc) return rc;
+    // 2. dz [P][C_out] (and dres) from the masked gradient, written once
+    const int64_t total4 = (int64_t)pl.P * d.C_out / 4;
+    float* const dz = scratch + sc.dz;
+    if (frozen) {
+        hipLaunchKernelGGL(tnet_dz_act_kernel<false>, grid1d(total4, ACT_GRID_CAP), dim3(256), 0, s, dout, out, (const float*)nullptr, stats,
+                           gamma, (const float*)nullptr, dz, dres, total4, d.C_out, pl.P);
+    } else {
+        hipLaunchKernelGGL(tnet_dz_act_kernel<true>, grid1d(total4, ACT_GRID_CAP), dim3(256), 0, s, dout, out, z, stats, gamma, s12, dz, dres,
+                           total4, d.C_out, pl.P);
+    }
+    TNET_LAUNCH_CHECK("conv act bwd dz")
+    return conv_bwd_products(d, pl, sc, dz, x, w, dx, dw, scratch, s);
+}
+
+}  // namespace
+
+extern "C" int64_t ghn3_conv_act_scratch_floats(const ghn3_conv_desc* g, int mode) {
+    CDesc d;
+    const int rc = check_act_desc(g, d, "conv act");
+    if (rc) return rc;                                            // GHN3_E_ARG / GHN3_E_LIMIT
+    return conv_act_scratch(d, make_cplan(d), (mode & 2) != 0, (mode & 1) != 0).total;
+}
+
+extern "C" int ghn3_conv_bn_act_fwd(const ghn3_conv_desc* g, const float* x, const float* w, const float* gamma, const float* beta,
+                                    const float* res, float* z, float* out, float* stats, float* scratch, void* stream_) {
+    CDesc d;
+    int rc = check_act_desc(g, d, "conv act fwd");
+    if (rc) return rc;
+    if (!x || !w || !gamma || !beta || !z || !out || !stats || !scratch) { ghn3_set_error("conv act fwd: null pointer"); return GHN3_E_ARG; }
+    hipStream_t s = (hipStream_t)stream_;
+    const CPlan pl = make_cplan(d);
+    const CScratch sc = conv_act_scratch(d, pl, false, false).sc;
+    rc = conv_fwd_launch<false>(d, pl, sc, x, w, z, Frozen{}, scratch, s, "conv act fwd");
+    if (rc) return rc;
+    hipLaunchKernelGGL(tnet_bn_finalize_kernel, dim3((d.C_out + 15) / 16), dim3(256), 0, s, scratch + sc.part, pl.n_tiles, pl.P, d.C_out, d.eps,
+                       stats);
+    TNET_LAUNCH_CHECK("bn finalize")
+    return act_apply_launch(pl, d.C_out, z, stats, gamma, beta, res, out, s);
+}
+
+extern "C" int ghn3_conv_bn_act_bwd(const ghn3_conv_desc* g, const float* dout, const float* out, const float* x, const float* z,
+                                    const float* stats, const float* w, const float* gamma, float* dx, float* dw, float* dgamma,
+                                    float* dbeta, float* dres, float* scratch, void* stream_) {
+    return conv_act_bwd_core(g, false, "conv act bwd", dout && out && x && z && stats && w && gamma && dx && dw && dgamma && dbeta && scratch,
+                             dout, out, x, z, stats, w, gamma, nullptr, nullptr, dx, dw, dgamma, dbeta, dres, scratch, stream_);
+}
+
+extern "C" int ghn3_conv_frozen_act_fwd(const ghn3_conv_desc* g, const float* x, const float* w, const float* gamma, const float* beta,
+                                        const float* mean, const float* var, const float* res, float* z, float* out, float* scratch,
+                                        void* stream_) {
+    CDesc d;
+    int rc = check_act_desc(g, d, "conv frozen act fwd");
+    if (rc) return rc;
+    if (!x || !w || !gamma || !beta || !mean || !var || !z || !out || !scratch) {
+        ghn3_set_error("conv frozen act fwd: null pointer");
+        return GHN3_E_ARG;
+    }
+    hipStream_t s = (hipStream_t)stream_;
+    const CPlan pl = make_cplan(d);
+    const CScratch sc = conv_act_scratch(d, pl, true, false).sc;
+    rc = conv_fwd_launch<false>(d, pl, sc, x, w, z, Frozen{}, scratch, s, "conv frozen act fwd");
+    if (rc) return rc;
+    rc = frozen_stats(mean, var, d.eps, d.C_out, scratch + sc.stats, s);
+    if (rc) return rc;
+    return act_apply_launch(pl, d.C_out, z, scratch + sc.stats, gamma, beta, res, out, s);
+}
+
+extern "C" int ghn3_conv_frozen_act_bwd(const ghn3_conv_desc* g, const float* dout, const float* out, const float* x, const float* z,
+                                        const float* w, const float* gamma, const float* mean, const float* var, float* dx, float* dw,
+                                        float* dgamma, float* dbeta, float* dres, float* scratch, void* stream_) {
+    return conv_act_bwd_core(g, true, "conv frozen act bwd",
+                             dout && out && x && z && w && gamma && mean && var && dx && dw && dgamma && dbeta && scratch, dout, out, x, z,
+                             nullptr, w, gamma, mean, var, dx, dw, dgamma, dbeta, dres, scratch, stream_);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -1,0 +1,335 @@
+"""
+``nativize(model)``: an arbitrary ``torch.nn`` network on the native target-network nodes, without rewriting it by hand.
+
+The native ops of ``ghn3_amd.target_ops`` are called from the block classes of ``ghn3_amd.ops``, which run the DeepNets-1M order
+``ReLU -> conv -> BatchNorm``.  The networks the plain ``Trainer`` branch fine-tunes are ResNet-shaped ``torch.nn`` modules that run
+``conv -> BatchNorm -> ReLU`` and, at the end of a block, ``conv -> BatchNorm -> (+ skip) -> ReLU``.  ``nativize`` traces such a module
+with ``torch.fx`` and replaces these windows of the graph by calls of the runners:
+
+    window                                               runner                                   report key
+    Conv2d -> BatchNorm2d -> ReLU                        target_ops.run_conv_bn_act               'conv_bn_relu'
+    Conv2d -> BatchNorm2d -> add(., r) -> ReLU           target_ops.run_conv_bn_act(residual=r)   'conv_bn_add_relu'
+    Conv2d -> BatchNorm2d -> add (the other operand;     target_ops._conv_dispatch(relu=False)    'conv_bn'
+      a block's downsample branch)
+    MaxPool2d / AvgPool2d / F.max_pool2d / F.avg_pool2d  target_ops.run_pool                      'pool'
+    global average pool -> flatten -> Linear             target_ops.run_classifier_head           'head'
+
+The result is a ``torch.fx.GraphModule`` that SHARES the original's submodules, Parameters and buffers (same ``state_dict`` keys; the
+original is not modified, and ``train()`` / ``eval()`` / ``to()`` on either reach the same layers).  Every replaced window keeps the
+very modules it replaced and runs them whenever its runner does not apply -- CPU tensors, a switch that is off
+(GHN3_NATIVE_OPS / _CONV / _ACT / _POOL / _HEAD / _EVALBN = 0), a limit of the kernels, autocast with GHN3_NATIVE_AMP=0 --, so on the
+CPU the nativized module computes what the original computes, bit for bit.  Tensors stay channels_last between native nodes; a stock
+node that reads a native node's result gets it NCHW-contiguous (the stock layers of this ROCm build return wrong gradients for
+channels_last inputs: target_ops' module text).
+
+Every intermediate node of a window has exactly one user; the convolution is bias-free, ungrouped, zero-padded with numeric
+padding, at most 7 x 7 and of one dilation.  Anything else stays stock, and ``report()`` says why.
+"""
+
+import operator
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import target_ops as T
+from .utils import log
+
+WINDOW_KINDS = ('conv_bn_relu', 'conv_bn_add_relu', 'conv_bn', 'pool', 'head')
+
+
+def _stock_layout(t):
+    """A native node's channels_last result as a stock layer takes it: NCHW-contiguous (the tensor itself when it is already)."""
+    if torch.is_tensor(t) and t.dim() == 4 and not t.is_contiguous():
+        return t.contiguous()
+    return t
+
+
+class _Window(nn.Module):
+    """A replaced window: the layers it stands for are kept OUTSIDE the module registry (they are registered once, where the
+    original network has them), so the nativized module's state_dict is the original's."""
+
+    def __init__(self, **layers):
+        super().__init__()
+        self.__dict__['layers'] = layers
+
+    def extra_repr(self):
+        return ', '.join('%s=%s' % (k, type(v).__name__) for k, v in self.layers.items() if v is not None)
+
+
+class NativeConvBnAct(_Window):
+    """Conv2d -> BatchNorm2d [-> + residual] -> ReLU."""
+
+    def forward(self, x, residual=None):
+        conv, bn = self.layers['conv'], self.layers['bn']
+        out = T.run_conv_bn_act(conv, bn, x, residual)
+        if out is not None:
+            return out
+        y = bn(conv(_stock_layout(x)))
+        if residual is not None:
+            y = y + _stock_layout(residual)
+        return F.relu(y)
+
+
+class NativeConvBn(_Window):
+    """Conv2d -> BatchNorm2d without a ReLU (a downsample branch): the existing members of the dense-convolution family."""
+
+    def forward(self, x):
+        conv, bn = self.layers['conv'], self.layers['bn']
+        if T._native_input(x, 'GHN3_NATIVE_CONV') and T.zero_padded_conv(conv) and T._is_kind(bn, 'BatchNorm2d'):
+            xin, w = T._image_pad(x, conv.weight)
+            dil = T._pair(conv.dilation)[0]
+            if T.conv_desc_fits(T._conv_desc(xin, w, conv.stride, conv.padding, dil, False, 0.0)):
+                out = T._conv_dispatch(xin, w, T._norm_slot(bn), conv.stride, conv.padding, dil, False)
+                if out is not None:
+                    return out
+        return bn(conv(_stock_layout(x)))
+
+
+class NativePool(_Window):
+    """MaxPool2d / AvgPool2d (module or functional form; `stock` re-runs the replaced call)."""
+
+    def __init__(self, stock, kernel_size, stride, padding, mode):
+        super().__init__(pool=stock if isinstance(stock, nn.Module) else None)
+        self.__dict__['stock'] = stock
+        self.cfg = (kernel_size, kernel_size if stride is None else stride, padding, mode)
+
+    def forward(self, x):
+        out = T.run_pool(x, *self.cfg) if torch.is_tensor(x) and x.dim() == 4 else None
+        return self.__dict__['stock'](_stock_layout(x)) if out is None else out
+
+
+class NativeHead(_Window):
+    """Global average pool -> flatten -> Linear."""
+
+    def __init__(self, fc):
+        super().__init__(fc=fc)
+        self.__dict__['pool'] = nn.AdaptiveAvgPool2d(1)
+
+    def forward(self, x):
+        pool, fc = self.__dict__['pool'], self.layers['fc']
+        out = T.run_classifier_head(pool, [fc], x) if torch.is_tensor(x) and x.dim() == 4 else None
+        return fc(torch.flatten(pool(_stock_layout(x)), 1)) if out is None else out
+
+
+class NativeReport(dict):
+    """What nativize did: `windows` (kind -> count), `stock_convs` (module name -> reason), and `traced`."""
+
+    def __str__(self):
+        rows = ['%-18s %d' % (k, self['windows'][k]) for k in WINDOW_KINDS]
+        rows += ['stock %s: %s' % kv for kv in self['stock_convs'].items()]
+        return '\n'.join(rows)
+
+
+# ---- the matcher ------------------------------------------------------------------------------------------------------------------
+_RELU_FUNCTIONS = (F.relu, torch.relu, torch.relu_, F.relu_)
+_ADD_FUNCTIONS = (operator.add, operator.iadd, torch.add)
+
+
+def conv_refusal(conv):
+    """Why the dense kernels do not take this Conv2d, or None.  Asked of the layer itself, padding_mode included."""
+    if conv.bias is not None:
+        return 'biased convolution'
+    if conv.groups != 1:
+        return 'grouped convolution (groups=%d)' % conv.groups
+    if conv.padding_mode != 'zeros':
+        return "padding_mode='%s'" % conv.padding_mode
+    if isinstance(conv.padding, str):
+        return "padding='%s'" % conv.padding
+    if max(conv.kernel_size) > 7:
+        return 'kernel %d x %d is larger than 7 x 7' % tuple(conv.kernel_size)
+    if len(set(T._pair(conv.dilation))) != 1:
+        return 'two dilations'
+    return None
+
+
+class _Matcher:
+    def __init__(self, gm):
+        self.gm, self.graph = gm, gm.graph
+        self.mods = dict(gm.named_modules())
+        self.native = set()                 # the windows' nodes: they read either layout
+        self.nhwc = set()                   # those of them whose result is channels_last
+        self.windows = dict.fromkeys(WINDOW_KINDS, 0)
+        self.stock = {}
+        self.n = 0
+
+    def mod(self, node, cls):
+        """The module a call_module node calls when it is exactly a `cls`, else None."""
+        if node.op == 'call_module':
+            m = self.mods.get(node.target)
+            if type(m) is cls:
+                return m
+        return None
+
+    def is_relu(self, node):
+        if node.op == 'call_module':
+            return self.mod(node, nn.ReLU) is not None
+        if node.op == 'call_function':
+            return node.target in _RELU_FUNCTIONS
+        return node.op == 'call_method' and node.target in ('relu', 'relu_')
+
+    @staticmethod
+    def is_add(node):
+        if not ((node.op == 'call_function' and node.target in _ADD_FUNCTIONS) or
+                (node.op == 'call_method' and node.target in ('add', 'add_'))):
+            return False
+        return len(node.args) == 2 and not node.kwargs and all(isinstance(a, torch.fx.Node) for a in node.args)
+
+    @staticmethod
+    def input_of(node):
+        return node.args[0] if node.args else node.kwargs.get('input')
+
+    def chain(self, bn_node):
+        """(conv node, conv, bn) when bn_node is the BatchNorm2d of a fusable Conv2d -> BatchNorm2d pair with one user each."""
+        if not isinstance(bn_node, torch.fx.Node) or self.mod(bn_node, nn.BatchNorm2d) is None or len(bn_node.users) != 1:
+            return None
+        c = self.input_of(bn_node)
+        if not isinstance(c, torch.fx.Node) or len(c.users) != 1:
+            return None
+        conv = self.mod(c, nn.Conv2d)
+        if conv is None or conv_refusal(conv) is not None:
+            return None
+        return c, conv, self.mods[bn_node.target]
+
+    def put(self, module, args, last, dead, kind, nhwc=True):
+        """The window's module in place of its `last` node; `dead`: the window's nodes, last first."""
+        name = '_native_%d' % self.n
+        self.n += 1
+        self.gm.add_module(name, module)
+        self.mods[name] = module
+        with self.graph.inserting_before(last):
+            new = self.graph.call_module(name, args)
+        last.replace_all_uses_with(new)
+        for node in dead:
+            self.graph.erase_node(node)
+        self.native.add(new)
+        if nhwc:
+            self.nhwc.add(new)
+        self.windows[kind] += 1
+        return new
+
+    def conv_window(self, c):
+        conv = self.mod(c, nn.Conv2d)
+        why = conv_refusal(conv)
+        users = list(c.users)
+        if why is None and len(users) != 1:
+            why = 'the convolution has %d users' % len(users)
+        if why is None and (self.mod(users[0], nn.BatchNorm2d) is None or self.input_of(users[0]) is not c):
+            why = 'not followed by a BatchNorm2d'
+        if why is None and len(users[0].users) != 1:
+            why = 'the norm layer has %d users' % len(users[0].users)
+        if why is not None:
+            self.stock[c.target] = why
+            return
+        b = users[0]
+        bn, x = self.mods[b.target], self.input_of(c)
+        nxt = next(iter(b.users))
+        if self.is_relu(nxt) and self.input_of(nxt) is b:
+            self.put(NativeConvBnAct(conv=conv, bn=bn), (x,), nxt, (nxt, b, c), 'conv_bn_relu')
+            return
+        if nxt in self.native and type(self.mods[nxt.target]) is NativeConvBnAct and nxt.args[0] is not b:
+            # (the skip operand of a window that is in place already: the other branch of the block)
+            self.put(NativeConvBn(conv=conv, bn=bn), (x,), b, (b, c), 'conv_bn')
+            return
+        if self.is_add(nxt):
+            other = nxt.args[1] if nxt.args[0] is b else nxt.args[0]
+            relu = next(iter(nxt.users)) if len(nxt.users) == 1 else None
+            fuse = relu is not None and self.is_relu(relu) and self.input_of(relu) is nxt and other is not b
+            # both operands are conv -> norm results (a block with a downsample branch): the first one takes the add and the ReLU
+            if fuse and nxt.args[1] is b and self.chain(nxt.args[0]) is not None:
+                fuse = False
+            if fuse:
+                self.put(NativeConvBnAct(conv=conv, bn=bn), (x, other), relu, (relu, nxt, b, c), 'conv_bn_add_relu')
+            else:
+                self.put(NativeConvBn(conv=conv, bn=bn), (x,), b, (b, c), 'conv_bn')
+            return
+        what = type(self.mods[nxt.target]).__name__ if nxt.op == 'call_module' else getattr(nxt.target, '__name__', str(nxt.target))
+        self.stock[c.target] = 'the norm layer is followed by %s, neither a ReLU nor an add' % what
+
+    def pool_window(self, node):
+        m = self.mods.get(node.target) if node.op == 'call_module' else None
+        if type(m) is nn.MaxPool2d:
+            if T._pair(m.dilation) == (1, 1) and not m.ceil_mode and not m.return_indices:
+                self.put(NativePool(m, m.kernel_size, m.stride, m.padding, 1), (self.input_of(node),), node, (node,), 'pool')
+        elif type(m) is nn.AvgPool2d:
+            if not m.ceil_mode and m.divisor_override is None and (not m.count_include_pad or T._pair(m.padding) == (0, 0)):
+                self.put(NativePool(m, m.kernel_size, m.stride, m.padding, 0), (self.input_of(node),), node, (node,), 'pool')
+        elif node.op == 'call_function' and node.target in (F.max_pool2d, F.avg_pool2d):
+            # (input, kernel_size, stride=None, padding=0, ...): anything beyond the three, or a traced value among them, stays stock
+            # (torch.fx records max_pool2d's defaults as keyword arguments)
+            names = ('input', 'kernel_size', 'stride', 'padding')
+            defaults = {'dilation': (1, (1, 1)), 'ceil_mode': (False,), 'return_indices': (False,), 'divisor_override': (None,),
+                        'count_include_pad': (True, False)}
+            if len(node.args) > 4 or any(k not in names and not (k in defaults and not isinstance(v, torch.fx.Node) and v in defaults[k])
+                                         for k, v in node.kwargs.items()):
+                return
+            a = dict(zip(names, node.args), **{k: v for k, v in node.kwargs.items() if k in names})
+            cfg = (a.get('kernel_size'), a.get('stride'), a.get('padding', 0))
+            if not isinstance(a.get('input'), torch.fx.Node) or any(isinstance(v, torch.fx.Node) for v in cfg):
+                return
+            if node.target is F.avg_pool2d and T._pair(cfg[2]) != (0, 0):      # (count_include_pad=True: not the kernel's average)
+                return
+            fn, kw = node.target, dict(kernel_size=cfg[0], stride=cfg[1], padding=cfg[2])
+            self.put(NativePool(lambda t: fn(t, **kw), *cfg, 1 if fn is F.max_pool2d else 0), (a['input'],), node, (node,), 'pool')
+
+    def head_window(self, node):
+        """node: a Linear; its input flatten(global average pool(x), 1)."""
+        fc = self.mod(node, nn.Linear)
+        fl = self.input_of(node)
+        if fc is None or not isinstance(fl, torch.fx.Node) or len(fl.users) != 1:
+            return
+        if fl.op == 'call_module':
+            m = self.mods.get(fl.target)
+            ok = type(m) is nn.Flatten and m.start_dim == 1 and m.end_dim == -1
+        else:
+            ok = ((fl.op == 'call_function' and fl.target is torch.flatten) or (fl.op == 'call_method' and fl.target == 'flatten')) and \
+                tuple(fl.args[1:]) + tuple(fl.kwargs.values()) == (1,)
+        gp = self.input_of(fl) if ok else None
+        if not isinstance(gp, torch.fx.Node) or len(gp.users) != 1:
+            return
+        if gp.op == 'call_module':
+            ok = T._is_global_pool(self.mods.get(gp.target)) and type(self.mods.get(gp.target)) is nn.AdaptiveAvgPool2d
+        else:
+            size = gp.args[1] if len(gp.args) > 1 else gp.kwargs.get('output_size')
+            ok = gp.op == 'call_function' and gp.target is F.adaptive_avg_pool2d and size in (1, (1, 1), [1, 1])
+        if ok:
+            self.put(NativeHead(fc), (self.input_of(gp),), node, (node, fl, gp), 'head', nhwc=False)
+
+    def run(self):
+        for node in list(self.graph.nodes):
+            if node.op == 'call_module' and self.mod(node, nn.Conv2d) is not None:
+                self.conv_window(node)
+        for node in list(self.graph.nodes):
+            if node not in self.native:
+                self.pool_window(node)
+        for node in list(self.graph.nodes):
+            if node.op == 'call_module' and node not in self.native:
+                self.head_window(node)
+        # a stock node (the output included) reads a native node's result NCHW-contiguous; the head reads either layout
+        for node in list(self.nhwc):
+            readers = [u for u in node.users if u not in self.native]
+            if readers:
+                with self.graph.inserting_after(node):
+                    plain = self.graph.call_function(_stock_layout, (node,))
+                for u in readers:
+                    u.replace_input_with(node, plain)
+        self.graph.lint()
+        self.gm.recompile()
+        return NativeReport(traced=True, windows=self.windows, stock_convs=self.stock)
+
+
+def nativize(model, strict=False):
+    """`model` (a torch.nn.Module) with its conv -> norm [-> add] -> ReLU, pooling and head windows on the native nodes: a
+    torch.fx.GraphModule over the SAME submodules, Parameters and buffers, with `report()`.  A model torch.fx cannot trace (data-
+    dependent control flow) is returned unchanged and the reason logged; strict=True raises instead."""
+    try:
+        gm = torch.fx.symbolic_trace(model)
+    except Exception as e:                                  # (torch.fx raises TraceError, TypeError, ... depending on the construct)
+        if strict:
+            raise
+        log('nativize: %s cannot be traced (%s: %s): it stays on the stock layers'
+            % (type(model).__name__, type(e).__name__, str(e).splitlines()[0] if str(e) else ''))
+        return model
+    report = _Matcher(gm).run()
+    gm.report = lambda: report
+    return gm

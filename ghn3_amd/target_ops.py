@@ -45,6 +45,12 @@ The patch embedding of the ViT-style networks (``run_conv_layer``): 3 x 3 / stri
 (ghn3_patch_fwd / _bwd, ghn3_amd/csrc/tnet_patch.hip): non-overlapping windows as a GEMM over the image as stored.
 GHN3_NATIVE_STEM=0 keeps the layer stock.
 
+Plain ``torch.nn`` networks (ResNet-shaped: ``conv -> BatchNorm -> ReLU``, and ``conv -> BatchNorm -> (+ skip) -> ReLU`` at the end of a
+block -- the ReLU BEHIND the norm layer, which no member above has) run on the "act" members of the dense-convolution family,
+``ConvBnAct`` / ``conv_bn_act`` (batch statistics) and ``ConvBnActEval`` / ``conv_bn_act_eval`` (running statistics), through the
+runner ``run_conv_bn_act(conv, bn, x, residual=None)``; ``ghn3_amd.nativize`` (native_net.py) finds these windows in a traced
+module.  GHN3_NATIVE_ACT=0 keeps them stock.
+
 ``DwPwBn.applicable`` states what the kernels take (fp32 CUDA tensors, batch statistics, C <= 512, ks <= 7); a layer
 outside of it goes to the two-node form above or keeps the stock path.  There is no CPU implementation: on a CPU tensor the
 stock path runs (the target networks themselves are torch modules), and ``dwpw_bn`` raises without the library.
@@ -620,6 +626,149 @@ def conv_reference(x, w, gamma, beta, stride=1, padding=0, dilation=1, relu=True
     return F.batch_norm(y, None, None, gamma, beta, True, 0.1, eps)
 
 
+# ---- the "act" member of the dense-convolution family: [ReLU ->] convolution -> norm [-> + skip] -> ReLU -----------------------
+# The layer order of ResNet-shaped torch.nn networks (ghn3_amd.nativize puts them onto these nodes): the ReLU sits behind the norm
+# layer, and at the end of a residual block the skip tensor is added between the two.  ghn3_conv_bn_act_* / ghn3_conv_frozen_act_*.
+_ACT_SCRATCH = 'ghn3_conv_act_scratch_floats'         # (desc, mode): mode = backward | 2 frozen
+
+
+def act_enabled():
+    """GHN3_NATIVE_ACT=0 keeps every conv -> norm [-> add] -> ReLU window on the stock layers."""
+    return os.environ.get('GHN3_NATIVE_ACT', '1') != '0'
+
+
+def _conv_act_applicable(x, w, gamma, beta, residual, stride, padding, dilation):
+    """Every limit of the C side (check_cdesc, the two 2^31 rules included) for the two members, and what they ask of the skip
+    tensor: an fp32 CUDA tensor of the output's shape."""
+    if not (act_enabled() and ConvBn.applicable(x, w, gamma, beta) and beta.numel() == w.shape[0]):
+        return False
+    (sh, sw), (ph, pw) = _pair(stride), _pair(padding)
+    if min(sh, sw) <= 0 or min(ph, pw) < 0 or int(dilation) <= 0:
+        return False
+    d = _conv_desc(x, w, stride, padding, dilation, False, 0.0)
+    if not conv_desc_fits(d):
+        return False
+    return residual is None or (_f32_cuda(residual) and tuple(residual.shape) == (d.N, d.C_out, d.Ho, d.Wo))
+
+
+def _conv_act_forward(ctx, frozen, x, w, norm, res, stride, pad, dil, relu, eps, keep=True):
+    """The forward of ConvBnAct (norm = (gamma, beta)) and ConvBnActEval (norm = (gamma, beta, running_mean, running_var)); res:
+    the skip tensor or None.  Returns (out, stats -- None when frozen).  With `keep`, x, w, z, out, gamma and the statistics are
+    saved: out, which the next layer reads anyway, carries the ReLU mask."""
+    lib = L.load()
+    xc = x.contiguous(memory_format=torch.channels_last)
+    wc = w.contiguous()
+    norm = [t.contiguous() for t in norm]
+    rc = None if res is None else res.contiguous(memory_format=torch.channels_last)
+    d = _conv_desc(xc, wc, stride, pad, dil, relu, eps)
+    dev, C_out = x.device, int(wc.shape[0])
+    out = torch.empty((d.N, C_out, d.Ho, d.Wo), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
+    z = torch.empty_like(out)
+    scratch = torch.empty(_scratch_floats(_ACT_SCRATCH, d, 2 if frozen else 0), dtype=torch.float32, device=dev)
+    if frozen:
+        stats = None
+        L._check(lib.ghn3_conv_frozen_act_fwd(ctypes.byref(d), *_ptrs(xc, wc, *norm, rc, z, out, scratch), _stream()),
+                 'ghn3_conv_frozen_act_fwd')
+        saved = (norm[0], norm[2], norm[3])
+    else:
+        stats = torch.empty(3 * C_out, dtype=torch.float32, device=dev)
+        L._check(lib.ghn3_conv_bn_act_fwd(ctypes.byref(d), *_ptrs(xc, wc, *norm, rc, z, out, stats, scratch), _stream()),
+                 'ghn3_conv_bn_act_fwd')
+        saved = (norm[0], stats)
+    if keep:
+        ctx.save_for_backward(xc, wc, z, out, *saved)
+        ctx.cfg = (stride, pad, dil, relu, eps)
+        ctx.has_res = res is not None
+    return out, stats
+
+
+def _conv_act_backward(ctx, frozen, dout, want_dres):
+    """The backward of both members: (dx, dw, dgamma, dbeta, dres).  The parameter gradients are tensors of their own, not views of
+    one buffer with the scratch area (`_carve`): the parameters of a plain network are leaves, whose .grad would pin it."""
+    lib = L.load()
+    xc, wc, z, out, g, *st = ctx.saved_tensors
+    stride, pad, dil, relu, eps = ctx.cfg
+    d = _conv_desc(xc, wc, stride, pad, dil, relu, eps)
+    do = dout.contiguous(memory_format=torch.channels_last)
+    dx, dw = torch.empty_like(xc), torch.empty_like(wc)
+    dg, db = torch.empty_like(g), torch.empty_like(g)
+    dres = torch.empty_like(out) if (ctx.has_res and want_dres) else None
+    scratch = torch.empty(_scratch_floats(_ACT_SCRATCH, d, 3 if frozen else 1), dtype=torch.float32, device=xc.device)
+    if frozen:
+        rm, rv = st
+        L._check(lib.ghn3_conv_frozen_act_bwd(ctypes.byref(d), *_ptrs(do, out, xc, z, wc, g, rm, rv, dx, dw, dg, db, dres, scratch),
+                                              _stream()), 'ghn3_conv_frozen_act_bwd')
+    else:
+        stats, = st
+        L._check(lib.ghn3_conv_bn_act_bwd(ctypes.byref(d), *_ptrs(do, out, xc, z, stats, wc, g, dx, dw, dg, db, dres, scratch),
+                                          _stream()), 'ghn3_conv_bn_act_bwd')
+    return dx, dw, dg, db, dres
+
+
+class ConvBnAct(torch.autograd.Function):
+    """[ReLU ->] dense kh x kw convolution -> BatchNorm (batch statistics) [-> + residual] -> ReLU as ONE autograd node on
+    ghn3_conv_bn_act_fwd / _bwd; returns (out, stats), stats not differentiable.  Conventions of ConvBn."""
+
+    @staticmethod
+    def applicable(x, w, gamma, beta, residual=None, stride=1, padding=0, dilation=1, training_stats=True):
+        return bool(training_stats) and _conv_act_applicable(x, w, gamma, beta, residual, stride, padding, dilation)
+
+    @staticmethod
+    def forward(ctx, x, w, gamma, beta, residual, stride, pad, dil, relu, eps):
+        out, stats = _conv_act_forward(ctx, False, x, w, (gamma, beta), residual, stride, pad, dil, relu, eps)
+        ctx.mark_non_differentiable(stats)
+        return out, stats
+
+    @staticmethod
+    def backward(ctx, dout, _dstats):
+        return _conv_act_backward(ctx, False, dout, ctx.needs_input_grad[4]) + (None,) * 5
+
+
+class ConvBnActEval(torch.autograd.Function):
+    """The same behind a BatchNorm with RUNNING statistics (eval mode): ghn3_conv_frozen_act_fwd / _bwd.  Without `keep` (no
+    backward can follow) nothing is saved."""
+
+    @staticmethod
+    def applicable(x, w, gamma, beta, running_mean, running_var, residual=None, stride=1, padding=0, dilation=1):
+        return _conv_act_applicable(x, w, gamma, beta, residual, stride, padding, dilation) and \
+            _frozen_stats_ok(running_mean, running_var, w.shape[0])
+
+    @staticmethod
+    def forward(ctx, x, w, gamma, beta, running_mean, running_var, residual, stride, pad, dil, relu, eps, keep):
+        return _conv_act_forward(ctx, True, x, w, (gamma, beta, running_mean, running_var), residual, stride, pad, dil, relu, eps,
+                                 keep)[0]
+
+    @staticmethod
+    def backward(ctx, dout):
+        dx, dw, dg, db, dres = _conv_act_backward(ctx, True, dout, ctx.needs_input_grad[6])
+        return (dx, dw, dg, db, None, None, dres) + (None,) * 6
+
+
+def conv_bn_act(x, w, gamma, beta, residual=None, stride=1, padding=0, dilation=1, relu_in=False, eps=1e-5):
+    """out = relu(batch_norm(conv2d(relu(x) if relu_in else x, w)) [+ residual]) with batch statistics; returns (out, stats) as
+    conv_bn does.  residual: a tensor of the output's shape (any layout; channels_last is read as it is) or None."""
+    _needs_gpu('conv_bn_act', x)
+    return ConvBnAct.apply(x, w, gamma, beta, residual, _pair(stride), _pair(padding), int(dilation), bool(relu_in), float(eps))
+
+
+def conv_bn_act_eval(x, w, gamma, beta, running_mean, running_var, residual=None, stride=1, padding=0, dilation=1, relu_in=False,
+                     eps=1e-5):
+    """The same with the given running statistics (a BatchNorm in eval mode); returns out.  Under torch.no_grad(), or when no
+    input requires a gradient, nothing is saved."""
+    _needs_gpu('conv_bn_act_eval', x)
+    return ConvBnActEval.apply(x, w, gamma, beta, running_mean, running_var, residual, _pair(stride), _pair(padding), int(dilation),
+                               bool(relu_in), float(eps), _wants_grad(x, w, gamma, beta, residual))
+
+
+def conv_act_reference(x, w, gamma, beta, residual=None, stride=1, padding=0, dilation=1, relu_in=False, eps=1e-5,
+                       running_mean=None, running_var=None):
+    """The stock layers the two nodes replace, functional form -- the parity reference of the tests.  With running statistics
+    given they normalise (eval mode) and are not updated."""
+    y = F.conv2d(F.relu(x) if relu_in else x, w, None, stride, padding, dilation)
+    y = F.batch_norm(y, running_mean, running_var, gamma, beta, running_mean is None, 0.1, eps)
+    return F.relu(y if residual is None else y + residual)
+
+
 class _PatchDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ('N', 'H', 'W', 'C_in', 'C_out', 'kh', 'kw', 'stride_h', 'stride_w', 'Ho', 'Wo', 'nhwc')]
 
@@ -991,6 +1140,35 @@ def run_layer_seq(seq, x):
             x = _hand_on(out, False, conv, bn)
             k += 3 if relu else 2
     return x
+
+
+def zero_padded_conv(conv):
+    """`_plain_conv` and zero padding: what a convolution of a torch.nn network has to be for the dense kernels (the layers of
+    ghn3_amd.ops never pad otherwise; an arbitrary nn.Conv2d may reflect, replicate or wrap)."""
+    return _plain_conv(conv) and getattr(conv, 'padding_mode', 'zeros') == 'zeros'
+
+
+def run_conv_bn_act(conv, bn, x, residual=None):
+    """Conv2d -> BatchNorm2d [-> + residual] -> ReLU of a torch.nn network on the "act" member that fits the norm slot
+    (`_norm_slot`: ConvBnAct with batch statistics, whose running statistics follow as torch's would; ConvBnActEval in eval mode),
+    3-channel images as `_image_pad` says; the NHWC result, or None where the node does not apply (the caller keeps its stock
+    layers)."""
+    if not (act_enabled() and _native_input(x, 'GHN3_NATIVE_CONV') and zero_padded_conv(conv) and _is_kind(bn, 'BatchNorm2d')):
+        return None
+    slot = _norm_slot(bn)
+    if slot.kind not in ('batch', 'frozen'):
+        return None
+    xin, w = _image_pad(x, conv.weight)
+    args = (residual, conv.stride, conv.padding, _pair(conv.dilation)[0])
+    g, b = slot.gamma, slot.beta
+    if slot.kind == 'frozen':
+        if ConvBnActEval.applicable(xin, w, g, b, slot.mean, slot.var, *args):
+            return conv_bn_act_eval(xin, w, g, b, slot.mean, slot.var, *args, False, slot.eps)
+    elif ConvBnAct.applicable(xin, w, g, b, *args):
+        out, stats = conv_bn_act(xin, w, g, b, *args, False, slot.eps)
+        _update_running_stats(slot, stats, out)
+        return out
+    return None
 
 
 def run_factorized_reduce(relu, conv_1, conv_2, bn, x, stride=2, keep_layout=False):

@@ -107,7 +107,7 @@ class Trainer:
     def __init__(self, model, opt, opt_args, scheduler, n_batches, grad_clip=5, auxiliary=False, auxiliary_weight=0.4,
                  device='cuda', log_interval=100, label_smoothing=0, predparam_wd=0, scheduler_args=None, save_dir=None,
                  ckpt=None, epochs=None, verbose=False, amp=False, amp_min_scale=None, amp_growth_interval=2000,
-                 grad_compress=None, amp_init_scale=65536.0, bce=False, mixup=False, compile_mode=None, beta=1e-5, **unused):
+                 grad_compress=None, amp_init_scale=65536.0, bce=False, mixup=False, compile_mode=None, beta=1e-5, native_layers=False, **unused):
         from .nn import GHN3
         self._plain = not isinstance(model, GHN3)
         if self._plain:
@@ -161,6 +161,11 @@ class Trainer:
                 self.loss_scale = max(self.amp_min_scale, float(state['amp_loss_scale']))
                 self._clean_steps = int(state.get('amp_clean_steps', 0))
         self._model = model
+        # native_layers (plain branch only; the GHN branch ignores it): the forward runs ghn3_amd.nativize(model), a view of the
+        # SAME modules and Parameters on the native conv-norm-ReLU, pooling and head nodes.  self._model stays the original, so
+        # checkpoints, the GHN initialisation and the optimizer do not see the difference.
+        self._native_layers = bool(native_layers) and self._plain
+        self._forward_model = None
         self.base_lr = float(opt_args['lr'])
         if self._plain:
             self.predparam_wd = 0
@@ -355,6 +360,16 @@ class Trainer:
         cls = FusedSGD if os.environ.get('GHN3_FUSED_SGD', '1') != '0' else StockSGD
         return cls(model.parameters(), lr=self.base_lr, max_grad_norm=float(self.grad_clip or 0.0), **kw)
 
+    def _plain_forward_model(self):
+        """What the plain branch's forward calls: the model, or with native_layers its nativized form (traced once; a model
+        torch.fx cannot trace is returned as it is, with the reason logged)."""
+        if not self._native_layers:
+            return self._model
+        if self._forward_model is None:
+            from .native_net import nativize
+            self._forward_model = nativize(self._model)
+        return self._forward_model
+
     def _update_plain(self, images, targets):
         model, dev = self._model, self.device
         if not model.training:
@@ -363,7 +378,7 @@ class Trainer:
         images = images.to(dev, non_blocking=True)
         targets = targets.to(dev, non_blocking=True)
         with torch.autocast(torch.device(dev).type, dtype=torch.float16, enabled=self.amp):
-            out = model(images)
+            out = self._plain_forward_model()(images)
         y, y_aux = (out[0], out[1]) if isinstance(out, tuple) else (out, None)
         ce, hits = target_ops.meta_cross_entropy([y], targets, self.label_smoothing)
         loss = ce.sum()

@@ -651,6 +651,42 @@ int ghn3_conv_frozen_bwd(const ghn3_conv_desc* desc, const float* dout, const fl
                          const float* gamma, const float* mean, const float* var, float* dx, float* dw, float* dgamma, float* dbeta,
                          float* scratch, void* stream);
 
+/* The "act" member of the family: the layer order of ResNet-shaped plain networks (conv -> BatchNorm -> ReLU, and at the end of
+ * a block conv -> BatchNorm -> + skip -> ReLU),
+ *   out = relu((z - mean) rstd gamma + beta [+ res]),  z = conv(relu(x) if desc->relu else x, w),
+ * with batch statistics (ghn3_conv_bn_act_*) or running statistics (ghn3_conv_frozen_act_*: mean / var [C_out] read only).
+ * Same descriptor, limits, error codes, NHWC fp32 conventions and in-place weight views as ghn3_conv_bn_fwd / _bwd;
+ * GHN3_CONV_NO_NORM in desc->relu is GHN3_E_ARG.  Added without an ABI version step (symbols only).
+ * res [N Ho Wo][C_out] is the skip tensor, NULL for none.  z, out, stats [3 C_out] are written by the forward and read by the
+ * backward: out (alive anyway as the next layer's input) carries the ReLU mask 1[out > 0] -- torch's rule, which masks on the
+ * result -- so nothing of activation size is saved beyond what ghn3_conv_bn_fwd leaves.  dres [N Ho Wo][C_out] = dout 1[out > 0]
+ * is the skip tensor's gradient; NULL: not wanted.  It must be NULL when the forward had no res.
+ * Forward: 4 launches, as ghn3_conv_bn_fwd -- weight pack, convolution + per-tile statistics, their combination, and an apply
+ * pass that also reads res and clamps at zero: no pass of activation size beyond reading res.  Frozen: weight pack, the
+ * convolution alone, (mean, var) -> (mean, rstd), the same apply pass; z is always written (never NULL).
+ * Backward: the launches of ghn3_conv_bn_bwd (7) / ghn3_conv_frozen_bwd (8), none more: the mask is applied where dout is first
+ * read -- in the per-tile (sum g, sum g xhat) partial sums and in the pass that writes dz, which writes dres beside it --, then
+ * weight pack, dx, dW and its reduction unchanged.  dgamma / dbeta may be any two buffers (adjacent, dbeta first: two device
+ * copies fewer, as for ghn3_conv_bn_bwd).
+ * `scratch` = ghn3_conv_act_scratch_floats(desc, mode) floats, a size function of this member's own, mode = backward | 2 frozen:
+ *   batch statistics (mode 0, 1)  what ghn3_conv_scratch_floats(desc, backward) answers
+ *   frozen backward  (mode 3)     what ghn3_conv_frozen_scratch_floats(desc, 1) answers
+ *   frozen forward   (mode 2)     2 tiles C_out + pack(C_out, C_in) + 64 + 2 C_out
+ * (a negative GHN3_E_* code for a descriptor the op does not take).  No float atomics, no allocation, no synchronisation
+ * inside.  Deterministic (fixed-order partial sums). */
+int64_t ghn3_conv_act_scratch_floats(const ghn3_conv_desc* desc, int mode);     /* < 0: bad descriptor (ghn3_last_error) */
+int ghn3_conv_bn_act_fwd(const ghn3_conv_desc* desc, const float* x, const float* w, const float* gamma, const float* beta,
+                         const float* res, float* z, float* out, float* stats, float* scratch, void* stream);
+int ghn3_conv_bn_act_bwd(const ghn3_conv_desc* desc, const float* dout, const float* out, const float* x, const float* z,
+                         const float* stats, const float* w, const float* gamma, float* dx, float* dw, float* dgamma, float* dbeta,
+                         float* dres, float* scratch, void* stream);
+int ghn3_conv_frozen_act_fwd(const ghn3_conv_desc* desc, const float* x, const float* w, const float* gamma, const float* beta,
+                             const float* mean, const float* var, const float* res, float* z, float* out, float* scratch,
+                             void* stream);
+int ghn3_conv_frozen_act_bwd(const ghn3_conv_desc* desc, const float* dout, const float* out, const float* x, const float* z,
+                             const float* w, const float* gamma, const float* mean, const float* var, float* dx, float* dw,
+                             float* dgamma, float* dbeta, float* dres, float* scratch, void* stream);
+
 /* The patch embedding of the ImageNet-sized ViT-style networks (`conv_stride`: Conv2d(3, C, 16, stride = 16) on 224 x 224
  * images) -- a bias-free, ungrouped convolution without padding or dilation whose windows do not overlap, which is a plain GEMM
  * over a permutation of the image (ghn3_amd/csrc/tnet_patch.hip):
