@@ -9,7 +9,15 @@ parameters predicted by a GHN-3 checkpoint (--ckpt) plus a little noise (--beta)
                                  [--native-layers]
 
 Without --ckpt the network keeps its own initialisation.  The optimizer step is the fused multi-tensor SGD (ghn3_amd.FusedSGD);
-GHN3_FUSED_SGD=0 runs stock clip_grad_norm_ + torch.optim.SGD instead.  One GPU: the plain branch has no data-parallel path yet.
+GHN3_FUSED_SGD=0 runs stock clip_grad_norm_ + torch.optim.SGD instead.
+
+Data parallel, like the reference's recipes, under torchrun (one process per GPU):
+
+    torchrun --standalone --nproc_per_node=4 examples/train_ddp.py --ckpt ghn3xlm16.pt ...
+
+Rank 0's parameters and buffers become every rank's, each rank draws its own images (seed + 1 + rank, standing in for
+DistributedSampler's shards; --batch-size is per rank), the gradients are averaged through one flat buffer inside the optimizer
+step (Trainer(..., data_parallel=True)), and rank 0 logs and saves.  Without torchrun the script is the one-GPU run it always was.
 """
 import argparse
 import os
@@ -87,19 +95,20 @@ def main():
                     help='run the conv-norm-ReLU, pooling and head layers on the native nodes (ghn3_amd.nativize)')
     args = ap.parse_args()
 
-    from ghn3_amd import Trainer, log
+    from ghn3_amd import Trainer, log, setup_ddp, clean_ddp
+    ddp = setup_ddp()                      # (under torchrun: the process group, device = cuda:LOCAL_RANK; else rank 0 of 1)
     torch.manual_seed(args.seed)
     num_classes = 10
     model = SmallResNet(num_classes) if args.arch == 'resnet' else genotype_network(num_classes)
     trainer = Trainer(model, opt='sgd', opt_args={'lr': args.lr, 'weight_decay': args.wd, 'momentum': args.momentum},
-                      scheduler='cosine', n_batches=args.steps, grad_clip=5, device='cuda', log_interval=10,
+                      scheduler='cosine', n_batches=args.steps, grad_clip=5, device=ddp.device, log_interval=10,
                       label_smoothing=args.label_smooth, save_dir=args.save, ckpt=args.ckpt, epochs=args.epochs, amp=args.amp,
-                      beta=args.beta, native_layers=args.native_layers)
+                      beta=args.beta, native_layers=args.native_layers, data_parallel=ddp.ddp)
     log('training %s (%d parameters in %d tensors), %d x %d images per step'
         % (type(model).__name__, sum(p.numel() for p in model.parameters()), len(list(model.parameters())), args.batch_size, 32))
-    gen = torch.Generator().manual_seed(args.seed + 1)
-    images = torch.randn(args.batch_size, 3, 32, 32, generator=gen).cuda()
-    targets = torch.randint(0, num_classes, (args.batch_size,), generator=gen).cuda()
+    gen = torch.Generator().manual_seed(args.seed + 1 + ddp.rank)
+    images = torch.randn(args.batch_size, 3, 32, 32, generator=gen).to(ddp.device)
+    targets = torch.randint(0, num_classes, (args.batch_size,), generator=gen).to(ddp.device)
     t0, n_timed = None, 0
     for epoch in range(trainer.start_epoch, args.epochs):
         trainer.reset_metrics(epoch)
@@ -108,7 +117,7 @@ def main():
                 torch.cuda.synchronize()
                 t0, n_timed = time.perf_counter(), 0
             trainer.update(images, targets)
-            trainer.log(step)
+            trainer.log(step)              # (on every rank -- its check of skipped steps moves the loss scale; rank 0 prints)
             n_timed += 1
             if args.save:
                 trainer.save(epoch, step, {})
@@ -117,6 +126,11 @@ def main():
     if t0 is not None and n_timed:
         log('%.2f ms per step over %d steps; %d updates skipped'
             % (1e3 * (time.perf_counter() - t0) / n_timed, n_timed, trainer.skipped_updates))
+    if ddp.ddp:
+        trainer._sync_skips()
+        log('final loss %.4f on %d ranks; %d updates skipped'
+            % (trainer.metrics.avg()['loss'], ddp.world_size, trainer.skipped_updates))
+    clean_ddp()
 
 
 if __name__ == '__main__':

@@ -10,7 +10,7 @@ from .graph import Graph, GraphBatch
 from .nn import from_pretrained, GHN3, ConvDecoder3, SequentialMultipleInOut, norm_check, get_metadata
 from .utils import log, Logger, print_grads
 from .ddp_utils import (setup_ddp, is_ddp, get_ddp_rank, clean_ddp, avg_ddp_metric, all_reduce_flat_grads,
-                        sync_parameters)
+                        sync_parameters, sync_module_states)
 from .optim import FusedAdamW, FusedSGD, save_checkpoint
 from .trainer import Trainer
 from .native_net import nativize
@@ -18,5 +18,5 @@ from .ops import Network, NetworkLight
 from .deepnets1m import DeepNets1MDDP, NetBatchSamplerDDP
 
 __all__ = ['Graph', 'GraphBatch', 'from_pretrained', 'GHN3', 'ConvDecoder3', 'SequentialMultipleInOut', 'log', 'Logger', 'print_grads', 'norm_check', 'get_metadata',
-           'setup_ddp', 'is_ddp', 'get_ddp_rank', 'clean_ddp', 'avg_ddp_metric', 'all_reduce_flat_grads', 'sync_parameters', 'FusedAdamW', 'save_checkpoint', 'Trainer', 'nativize',
+           'setup_ddp', 'is_ddp', 'get_ddp_rank', 'clean_ddp', 'avg_ddp_metric', 'all_reduce_flat_grads', 'sync_parameters', 'sync_module_states', 'FusedAdamW', 'save_checkpoint', 'Trainer', 'nativize',
            'Network', 'NetworkLight', 'DeepNets1MDDP', 'NetBatchSamplerDDP']

@@ -82,7 +82,7 @@ EXPORTS = ['ghn3_abi_version', 'ghn3_last_error', 'ghn3_ctx_create', 'ghn3_ctx_d
            'ghn3_attn_lean_fwd', 'ghn3_attn_lean_bwd', 'ghn3_msa_lean_scratch_floats', 'ghn3_msa_lean_fwd', 'ghn3_msa_lean_bwd',
            'ghn3_dw_scratch_floats', 'ghn3_dw_fwd', 'ghn3_dw_bwd', 'ghn3_patch_scratch_floats', 'ghn3_patch_fwd', 'ghn3_patch_bwd',
            'ghn3_attn_wide_fwd', 'ghn3_attn_wide_bwd', 'ghn3_msa_wide_scratch_floats', 'ghn3_msa_wide_fwd', 'ghn3_msa_wide_bwd',
-           'ghn3_mt_sumsq', 'ghn3_mt_sgd',
+           'ghn3_mt_sumsq', 'ghn3_mt_sgd', 'ghn3_mt_pack', 'ghn3_mt_unpack',
            'ghn3_conv_act_scratch_floats', 'ghn3_conv_bn_act_fwd', 'ghn3_conv_bn_act_bwd', 'ghn3_conv_frozen_act_fwd',
            'ghn3_conv_frozen_act_bwd']
 OPFLAG_TIMED = 0x100
@@ -192,6 +192,7 @@ def load():
         lib.ghn3_posenc_bwd.argtypes = [ctypes.c_int] * 5 + [ctypes.c_void_p] * 3
         lib.ghn3_mt_sumsq.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] + [ctypes.c_void_p] * 3
         lib.ghn3_mt_sgd.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] + [ctypes.c_void_p] * 3
+        lib.ghn3_mt_pack.argtypes = lib.ghn3_mt_unpack.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p]
         if lib.ghn3_abi_version() != ABI_VERSION:
             raise Ghn3Error('libghn3_hip.so ABI %d != expected %d: rebuild' % (lib.ghn3_abi_version(), ABI_VERSION))
         _lib = lib

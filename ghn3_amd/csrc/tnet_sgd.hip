@@ -134,6 +134,30 @@ __global__ __launch_bounds__(MT_THREADS) void mt_sgd_kernel(const ghn3_mt_tensor
     }
 }
 
+// Gather / scatter between the table's separate tensors and their segments of ONE flat buffer (ghn3_mt_pack / ghn3_mt_unpack):
+// bit copies over the same chunk list and with the same quad accesses as the step above.  PACK: other[k] -> segs[k].p, else
+// segs[k].p -> other[k]; elements [0, n) only, so a segment's pad floats and everything around a tensor stay as they are.
+template <bool PACK>
+__global__ __launch_bounds__(MT_THREADS) void mt_wire_kernel(const ghn3_mt_tensor* __restrict__ segs,
+                                                             float* const* __restrict__ other,
+                                                             const ghn3_mt_chunk* __restrict__ chunks, int n_chunks) {
+    for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+        const ghn3_mt_chunk ch = chunks[c];
+        const ghn3_mt_tensor t = segs[ch.tensor];
+        const int64_t left = t.n - ch.first;
+        const int len = left < GHN3_MT_CHUNK ? (int)left : GHN3_MT_CHUNK;
+        float* flat = t.p + ch.first;
+        float* sep = other[ch.tensor] + ch.first;
+        const float* src = PACK ? sep : flat;
+        float* dst = PACK ? flat : sep;
+        const bool vec = aligned16(src) && aligned16(dst);
+        for (int q = threadIdx.x; 4 * q < len; q += MT_THREADS) {
+            const int cnt = len - 4 * q < 4 ? len - 4 * q : 4;
+            store_quad(dst + 4 * q, vec, cnt, load_quad(src + 4 * q, vec, cnt));
+        }
+    }
+}
+
 int check_tables(const char* what, const void* tensors, const void* grads, const void* chunks, int n_chunks) {
     if (n_chunks < 0) { ghn3_set_error("%s: %d chunks", what, n_chunks); return GHN3_E_ARG; }
     if (n_chunks == 0) return GHN3_OK;
@@ -174,5 +198,26 @@ extern "C" int ghn3_mt_sgd(const ghn3_mt_tensor* tensors, const float* const* gr
     const int grid = n_chunks < MT_MAX_BLOCKS ? n_chunks : MT_MAX_BLOCKS;
     hipLaunchKernelGGL(mt_sgd_kernel, dim3(grid), dim3(MT_THREADS), 0, (hipStream_t)stream, tensors, grads, chunks, n_chunks, sumsq, a);
     TNET_LAUNCH_CHECK("mt_sgd")
+    return GHN3_OK;
+}
+
+extern "C" int ghn3_mt_pack(const ghn3_mt_tensor* segs, const float* const* src, const ghn3_mt_chunk* chunks, int n_chunks,
+                            void* stream) {
+    const int rc = check_tables("mt_pack", segs, src, chunks, n_chunks);
+    if (rc || n_chunks == 0) return rc;
+    const int grid = n_chunks < MT_MAX_BLOCKS ? n_chunks : MT_MAX_BLOCKS;
+    hipLaunchKernelGGL(mt_wire_kernel<true>, dim3(grid), dim3(MT_THREADS), 0, (hipStream_t)stream, segs,
+                       const_cast<float* const*>(src), chunks, n_chunks);
+    TNET_LAUNCH_CHECK("mt_pack")
+    return GHN3_OK;
+}
+
+extern "C" int ghn3_mt_unpack(const ghn3_mt_tensor* segs, float* const* dst, const ghn3_mt_chunk* chunks, int n_chunks,
+                              void* stream) {
+    const int rc = check_tables("mt_unpack", segs, dst, chunks, n_chunks);
+    if (rc || n_chunks == 0) return rc;
+    const int grid = n_chunks < MT_MAX_BLOCKS ? n_chunks : MT_MAX_BLOCKS;
+    hipLaunchKernelGGL(mt_wire_kernel<false>, dim3(grid), dim3(MT_THREADS), 0, (hipStream_t)stream, segs, dst, chunks, n_chunks);
+    TNET_LAUNCH_CHECK("mt_unpack")
     return GHN3_OK;
 }

@@ -74,6 +74,46 @@ def sync_parameters(ghn, src=0):
     return ghn
 
 
+def sync_module_states(model, src=0, force=False, parameters=True):
+    """Rank `src`'s parameters and buffers become every rank's -- what DistributedDataParallel's constructor does for a plain
+    nn.Module.  The fp32 tensors (parameters and BatchNorm statistics) are gathered into ONE flat buffer (GPU: ghn3_mt_pack,
+    one launch; CPU: torch copies), broadcast with one collective and scattered back (ghn3_mt_unpack); the rest
+    (num_batches_tracked: int64) is stacked into one tensor per dtype and broadcast the same way.  parameters=False: the
+    buffers alone (the Trainer's sync between epochs).  A 1-rank group returns at once unless `force` is set (tests of the code
+    path)."""
+    if not is_ddp() or (dist.get_world_size() == 1 and not force):
+        return model
+    from .optim import flat_layout, mt_pack, mt_unpack
+    tensors = ([p.data for p in model.parameters()] if parameters else []) + [b for b in model.buffers() if b is not None]
+    with torch.no_grad():
+        f32 = [t for t in tensors if t.dtype == torch.float32 and t.numel() > 0 and t.is_contiguous()]
+        if f32:
+            offs = flat_layout([t.numel() for t in f32])
+            flat = torch.zeros(int(offs[-1]), dtype=torch.float32, device=f32[0].device)
+            if flat.is_cuda:
+                mt_pack(flat, offs, f32)
+            else:
+                for o, t in zip(offs, f32):
+                    flat[int(o):int(o) + t.numel()].copy_(t.reshape(-1))
+            dist.broadcast(flat, src=src)
+            if flat.is_cuda:
+                mt_unpack(flat, offs, f32)
+            else:
+                for o, t in zip(offs, f32):
+                    t.copy_(flat[int(o):int(o) + t.numel()].view(t.shape))
+        done = set(id(t) for t in f32)
+        rest = {}
+        for t in tensors:
+            if id(t) not in done and t.numel() > 0:
+                rest.setdefault((t.dtype, t.device), []).append(t)
+        for group in rest.values():                           # (the same sequence on every rank: module order)
+            cat = torch.cat([t.reshape(-1) for t in group])
+            dist.broadcast(cat, src=src)
+            for t, piece in zip(group, cat.split([t.numel() for t in group])):
+                t.copy_(piece.view(t.shape))
+    return model
+
+
 def all_reduce_flat_grads(flat, chunk_bytes=256 << 20, average=True):
     """
     In-place mean all-reduce of the flat gradient buffer in `chunk_bytes` pieces (async, then waited).

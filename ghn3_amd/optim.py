@@ -467,6 +467,100 @@ _MT_CHUNK_DT = np.dtype([('tensor', '<i4'), ('_pad', '<i4'), ('first', '<i8')])
 assert _MT_TENSOR_DT.itemsize == ctypes.sizeof(_MtTensor) == 24 and _MT_CHUNK_DT.itemsize == ctypes.sizeof(_MtChunk) == 16
 
 
+def flat_layout(sizes):
+    """Offsets (int64, in floats) of tensors of the element counts `sizes` inside one flat fp32 buffer: every segment is padded
+    to 4 floats, so each starts on 16 bytes; the last entry is the buffer's length.  A function of the sizes alone."""
+    offs = np.zeros(len(sizes) + 1, dtype=np.int64)
+    np.cumsum([(int(n) + 3) // 4 * 4 for n in sizes], dtype=np.int64, out=offs[1:])
+    return offs
+
+
+def _mt_tables(base, offs, sizes, device):
+    """Device tables over the segments of a flat buffer at address `base` (layout `offs`) that hold tensors of `sizes` elements:
+    the ghn3_mt_tensor records (p = the segment, m = 0), the chunk list, the number of chunks.  Empty tensors have no chunk."""
+    rec = np.zeros(len(sizes), dtype=_MT_TENSOR_DT)
+    chunks = []
+    for k, n in enumerate(sizes):
+        rec[k] = (base + 4 * int(offs[k]), 0, n)
+        chunks += [(k, 0, first) for first in range(0, n, MT_CHUNK)]
+    ch = np.array(chunks, dtype=_MT_CHUNK_DT)
+    return torch.from_numpy(rec.view(np.uint8)).to(device), torch.from_numpy(ch.view(np.uint8)).to(device), len(ch)
+
+
+def _mt_wire(name, flat, offs, tensors):
+    """ghn3_mt_pack / ghn3_mt_unpack of a list of fp32 CUDA tensors and their segments of `flat`, tables built on the spot (the
+    start-up paths; FusedSGD keeps its tables)."""
+    dev = flat.device
+    for t in tensors:
+        if t.dtype != torch.float32 or t.device != dev or not t.is_contiguous():
+            raise ValueError('%s takes contiguous fp32 tensors on the flat buffer\'s device' % name)
+    sizes = [t.numel() for t in tensors]
+    assert flat.dtype == torch.float32 and flat.is_contiguous() and flat.numel() >= int(offs[len(sizes)])
+    lib = L.load()
+    with torch.cuda.device(dev):
+        rec, chunks, n_chunks = _mt_tables(flat.data_ptr(), offs, sizes, dev)
+        ptrs = torch.from_numpy(np.asarray([t.data_ptr() for t in tensors], dtype=np.int64)).to(dev)
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        L._check(getattr(lib, name)(rec.data_ptr(), ptrs.data_ptr(), chunks.data_ptr(), n_chunks, stream), name)
+
+
+def mt_pack(flat, offs, tensors):
+    """flat[offs[k] : offs[k] + n_k] = tensors[k], bit for bit, in one launch (ghn3_mt_pack); the pad floats are not written."""
+    _mt_wire('ghn3_mt_pack', flat, offs, tensors)
+
+
+def mt_unpack(flat, offs, tensors):
+    """tensors[k] = flat[offs[k] : offs[k] + n_k], bit for bit, in one launch (ghn3_mt_unpack)."""
+    _mt_wire('ghn3_mt_unpack', flat, offs, tensors)
+
+
+class _FlatGrads:
+    """The flat fp32 gradient buffer of an optimizer whose gradients go through a FlatGradReducer: one segment per parameter that
+    had requires_grad when the optimizer was built, in flat_layout.  The layout depends on the parameter list alone -- the
+    collectives of the exchange must have the same sequence and sizes on every rank -- so under a reducer every such parameter
+    needs a gradient in every step (DistributedDataParallel with find_unused_parameters=False asks the same).  Allocated once
+    with zeros: the pad floats are defined and an average of zeros is zero."""
+
+    def __init__(self, params):
+        self.idx = [i for i, p in enumerate(params) if p.requires_grad]
+        self.sizes = [params[i].numel() for i in self.idx]
+        self.offs = flat_layout(self.sizes)
+        self.flat = torch.zeros(int(self.offs[-1]), dtype=torch.float32, device=params[0].device)
+        self.params = params
+
+    def grads(self):
+        """The gradients of the layout's parameters as dense fp32 tensors on the device, or the RuntimeError."""
+        out = []
+        for i in self.idx:
+            p = self.params[i]
+            g = p.grad
+            if g is None:
+                raise RuntimeError('parameter %d (shape %s) has requires_grad but no gradient: under a gradient reducer every '
+                                   'parameter of the layout takes part in every step (the exchange has the same sizes on every '
+                                   'rank); freeze it before the optimizer is built' % (i, tuple(p.shape)))
+            if g.dtype != torch.float32 or g.is_sparse or g.device != p.device or not g.is_contiguous():
+                g = (g.to_dense() if g.is_sparse else g).to(device=p.device, dtype=torch.float32).contiguous()
+            out.append(g)
+        return out
+
+    def view(self, k):
+        o = int(self.offs[k])
+        return self.flat[o:o + self.sizes[k]].view(self.params[self.idx[k]].shape)
+
+    def exchange(self, reducer):
+        reducer.begin()
+        reducer.finish(self.flat)
+
+    def gather_torch(self, reducer, grads):
+        """Pack `grads` (self.grads()), exchange and return views of the averaged gradients, in torch expressions (CPU tensors,
+        StockSGD)."""
+        with torch.no_grad():
+            for k, g in enumerate(grads):
+                self.view(k).copy_(g)
+            self.exchange(reducer)
+        return [self.view(k) for k in range(len(self.idx))]
+
+
 def sgd_reference_(params, grads, bufs, lr, momentum=0.0, weight_decay=0.0, nesterov=False, max_norm=0.0, inv_scale=1.0):
     """torch restatement of one FusedSGD step (ghn3_mt_sumsq + ghn3_mt_sgd), in place on lists of tensors of any float type:
     the gradients' global norm as clip_grad_norm_ takes it (the norm of the per-tensor norms), g / scale times the clip
@@ -500,10 +594,17 @@ class FusedSGD:
     bytes); state_dict() hands out views of it.  The buffers start at zero, which with dampening 0 is torch's first-step
     `buf = clone(d)` bit for bit.  The chunk table and the parameter / momentum pointers go to the device once per set of
     parameters that take part; the gradient pointers -- autograd allocates the gradients anew after zero_grad(set_to_none) --
-    go up once per step through the pinned ring.  CPU parameters take sgd_reference_ (host logic can be tested anywhere)."""
+    go up once per step through the pinned ring.  CPU parameters take sgd_reference_ (host logic can be tested anywhere).
+
+    reducer (a ddp_utils.FlatGradReducer; None: nothing below applies): the data-parallel step.  The gradients are gathered into
+    ONE flat buffer laid out like the momentum buffer (ghn3_mt_pack over the same chunk list and the gradient pointers the
+    step uploads anyway), the reducer averages that buffer over the ranks, and norm + update read the averaged gradients from
+    it through a static pointer table: p.grad stays what autograd wrote.  Every parameter that had requires_grad at construction
+    is in the layout and must have a gradient in every step (_FlatGrads); the others are left out.  The returned norm is that of
+    the averaged gradient, the same bits on every rank: a non-finite value on any rank skips the update on all of them."""
 
     def __init__(self, params, lr, momentum=0, dampening=0, weight_decay=0, nesterov=False, max_grad_norm=0.0,
-                 nan_guard=True):
+                 nan_guard=True, reducer=None):
         if dampening != 0:
             raise ValueError('FusedSGD implements dampening = 0 only (momentum buffers start at zero and no first-step flag '
                              'exists on the device), got %r' % (dampening,))
@@ -525,11 +626,13 @@ class FusedSGD:
         self.params, self.device = params, dev
         self.lr, self.momentum, self.weight_decay, self.nesterov = lr, momentum, weight_decay, bool(nesterov)
         self.max_grad_norm, self.nan_guard = max_grad_norm, nan_guard
-        self._offs = np.concatenate([[0], np.cumsum([(p.numel() + 3) // 4 * 4 for p in params])]).astype(np.int64)
+        self._offs = flat_layout([p.numel() for p in params])
         self.momentum_buffer = torch.zeros(int(self._offs[-1]), dtype=torch.float32, device=dev) if momentum != 0 else None
         self._stepped = set()           # parameters that had a gradient in some step: the ones torch keeps a state entry for
         self._table = None
         self.steps = 0
+        self.reducer = reducer
+        self._gflat = _FlatGrads(params) if reducer is not None else None
 
     def _buf(self, i):
         if self.momentum_buffer is None:
@@ -557,15 +660,28 @@ class FusedSGD:
             chunks += [(k, 0, first) for first in range(0, n, MT_CHUNK)]
         ch = np.array(chunks, dtype=_MT_CHUNK_DT)
         dev = self.device
-        return {'active': active, 'pptr': pptr, 'n_chunks': len(ch),
-                'rec': torch.from_numpy(rec.view(np.uint8)).to(dev), 'chunks': torch.from_numpy(ch.view(np.uint8)).to(dev),
-                'scal': torch.zeros(4 + len(ch), dtype=torch.float32, device=dev)}      # [norm^2, pad | one partial per chunk]
+        tb = {'active': active, 'pptr': pptr, 'n_chunks': len(ch),
+              'rec': torch.from_numpy(rec.view(np.uint8)).to(dev), 'chunks': torch.from_numpy(ch.view(np.uint8)).to(dev),
+              'scal': torch.zeros(4 + len(ch), dtype=torch.float32, device=dev)}        # [norm^2, pad | one partial per chunk]
+        if self._gflat is not None:
+            # (reducer: the segments of the flat gradient buffer, as pack's records and as the step's gradient pointers: static)
+            fl = self._gflat
+            at = {i: k for k, i in enumerate(fl.idx)}
+            seg = np.zeros(len(active), dtype=_MT_TENSOR_DT)
+            for k, i in enumerate(active):
+                seg[k] = (fl.flat.data_ptr() + 4 * int(fl.offs[at[i]]), 0, self.params[i].numel())
+            tb['seg'] = torch.from_numpy(seg.view(np.uint8)).to(dev)
+            tb['fptr'] = torch.from_numpy(seg['p'].astype(np.int64)).to(dev)
+            tb['views'] = [fl.view(at[i]) for i in active]
+        return tb
 
     def step(self, grad_scale=1.0):
         """One update from the parameters' .grad; grad_scale: the loss scale the gradients carry (they are divided by it inside
         the kernel).  Returns the gradient norm (device scalar, like clip_grad_norm_) when clipping or the NaN guard is on, else
         None; when it is not finite no parameter and no momentum buffer changed.  A parameter without a gradient or with
-        requires_grad=False does not take part, as in torch."""
+        requires_grad=False does not take part, as in torch.  With a reducer: see the class."""
+        if self._gflat is not None:
+            return self._step_reduced(grad_scale)
         active, grads = [], []
         for i, p in enumerate(self.params):
             g = p.grad
@@ -604,6 +720,50 @@ class FusedSGD:
                 L._check(lib.ghn3_mt_sumsq(*tables, scal.data_ptr() + 16, scal.data_ptr(), stream), 'ghn3_mt_sumsq')
             args = _MtSgdArgs(self.lr, self.momentum, self.weight_decay, float(self.max_grad_norm or 0.0), inv_scale,
                               int(self.nesterov))
+            L._check(lib.ghn3_mt_sgd(*tables, scal.data_ptr() if guard else None, ctypes.byref(args), stream), 'ghn3_mt_sgd')
+        return scal[0].sqrt() * inv_scale if guard else None
+
+    def _step_reduced(self, grad_scale):
+        """The step under a reducer: pack, exchange, norm + update from the flat buffer."""
+        fl = self._gflat
+        grads = fl.grads()                        # (raises before anything is counted or written)
+        self._stepped.update(fl.idx)
+        self.steps += 1
+        guard = bool(self.max_grad_norm and self.max_grad_norm > 0) or self.nan_guard
+        inv_scale = 1.0 / float(grad_scale)
+        max_norm = float(self.max_grad_norm or 0.0)
+        if self.device.type != 'cuda':
+            avg = fl.gather_torch(self.reducer, grads)
+            with torch.no_grad():
+                norm = sgd_reference_([self.params[i] for i in fl.idx], avg, [self._buf(i) for i in fl.idx], self.lr,
+                                      self.momentum, self.weight_decay, self.nesterov, max_norm if guard else 0.0, inv_scale)
+            return norm if guard else None
+        keep = [k for k, n in enumerate(fl.sizes) if n > 0]          # (an empty tensor has no chunk and no record)
+        active = tuple(fl.idx[k] for k in keep)
+        pptr = [self.params[i].data_ptr() for i in active]
+        tb = self._table
+        if tb is None or tb['active'] != active or tb['pptr'] != pptr:
+            tb = self._table = self._build_table(active, pptr)
+        if not active:
+            return torch.zeros((), device=self.device) if guard else None
+        lib = L.load()
+        with torch.cuda.device(self.device):
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            if os.environ.get('GHN3_MT_PACK', '1') != '0':
+                gptr = pinned_ring(self.device).upload(np.asarray([grads[k].data_ptr() for k in keep], dtype=np.int64),
+                                                       self.device)
+                L._check(lib.ghn3_mt_pack(tb['seg'].data_ptr(), gptr.data_ptr(), tb['chunks'].data_ptr(), tb['n_chunks'], stream),
+                         'ghn3_mt_pack')
+            else:
+                # the A/B switch: the same gather by torch's multi-tensor copy (the shorter one on a ResNet-18's 62 tensors, the
+                # longer one on a ResNet-50's 161: profiles/r18a_plain_ddp_step.txt)
+                torch._foreach_copy_(tb['views'], [grads[k] for k in keep])
+            fl.exchange(self.reducer)
+            scal = tb['scal']
+            tables = (tb['rec'].data_ptr(), tb['fptr'].data_ptr(), tb['chunks'].data_ptr(), tb['n_chunks'])
+            if guard:
+                L._check(lib.ghn3_mt_sumsq(*tables, scal.data_ptr() + 16, scal.data_ptr(), stream), 'ghn3_mt_sumsq')
+            args = _MtSgdArgs(self.lr, self.momentum, self.weight_decay, max_norm, inv_scale, int(self.nesterov))
             L._check(lib.ghn3_mt_sgd(*tables, scal.data_ptr() if guard else None, ctypes.byref(args), stream), 'ghn3_mt_sgd')
         return scal[0].sqrt() * inv_scale if guard else None
 
@@ -651,8 +811,12 @@ class StockSGD:
     GHN3_FUSED_SGD switch.  Unscale, norm, clip and update are separate torch passes, and skipping a step whose norm is not
     finite costs one host read per step."""
 
-    def __init__(self, params, lr, momentum=0, dampening=0, weight_decay=0, nesterov=False, max_grad_norm=0.0):
+    def __init__(self, params, lr, momentum=0, dampening=0, weight_decay=0, nesterov=False, max_grad_norm=0.0, reducer=None):
         self.params = list(params)
+        # reducer: FusedSGD's data-parallel sequence in torch expressions -- the gradients are copied into the flat layout,
+        # averaged by the reducer and copied back into p.grad (where DistributedDataParallel leaves them) for the stock pair
+        self.reducer = reducer
+        self._gflat = _FlatGrads(self.params) if reducer is not None else None
         self.opt = torch.optim.SGD(self.params, lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
                                    nesterov=nesterov)
         self.max_grad_norm = max_grad_norm
@@ -670,6 +834,11 @@ class StockSGD:
         self.opt.zero_grad(set_to_none=set_to_none)
 
     def step(self, grad_scale=1.0):
+        if self._gflat is not None:
+            avg = self._gflat.gather_torch(self.reducer, self._gflat.grads())
+            with torch.no_grad():
+                for i, a in zip(self._gflat.idx, avg):
+                    self.params[i].grad.copy_(a)
         with_grad = [p for p in self.params if p.grad is not None]
         self.steps += 1
         if not with_grad:

@@ -38,8 +38,10 @@ trainer.py:102-133):
 
 `ckpt` names a GHN that predicts the initial parameters on the device (a checkpoint.pt in save_dir wins and resumes instead);
 norm, unscale, clip and the SGD update are one multi-tensor step (FusedSGD; GHN3_FUSED_SGD=0: the stock pair).  Metrics, loss
-scale, skipped steps, checkpoints and schedules are the GHN branch's code.  Refused for plain networks: other optimizers, bce,
-mixup, data-parallel runs.
+scale, skipped steps, checkpoints and schedules are the GHN branch's code.  Under a process group the branch is opt-in:
+data_parallel=True broadcasts rank 0's parameters and buffers (sync_module_states), averages the gradients through one flat
+buffer (FusedSGD(reducer=FlatGradReducer(compress=grad_compress))) and re-broadcasts the buffers in scheduler_step(); without
+it a process group is refused.  Refused for plain networks: other optimizers, bce, mixup.
 """
 
 import math
@@ -47,7 +49,7 @@ import os
 
 import torch
 
-from .ddp_utils import is_ddp, get_ddp_rank, sync_parameters, FlatGradReducer
+from .ddp_utils import is_ddp, get_ddp_rank, sync_parameters, sync_module_states, FlatGradReducer
 from . import target_ops
 from .optim import FusedAdamW, FusedSGD, StockSGD, save_checkpoint
 from .utils import log, Logger
@@ -107,11 +109,12 @@ class Trainer:
     def __init__(self, model, opt, opt_args, scheduler, n_batches, grad_clip=5, auxiliary=False, auxiliary_weight=0.4,
                  device='cuda', log_interval=100, label_smoothing=0, predparam_wd=0, scheduler_args=None, save_dir=None,
                  ckpt=None, epochs=None, verbose=False, amp=False, amp_min_scale=None, amp_growth_interval=2000,
-                 grad_compress=None, amp_init_scale=65536.0, bce=False, mixup=False, compile_mode=None, beta=1e-5, native_layers=False, **unused):
+                 grad_compress=None, amp_init_scale=65536.0, bce=False, mixup=False, compile_mode=None, beta=1e-5, native_layers=False,
+                 data_parallel=False, **unused):
         from .nn import GHN3
         self._plain = not isinstance(model, GHN3)
         if self._plain:
-            self._check_plain(opt, bce, mixup, compile_mode)
+            self._check_plain(opt, bce, mixup, compile_mode, data_parallel)
         elif opt.lower() != 'adamw':
             raise NotImplementedError('the fused optimizer step implements AdamW (the GHN-3 recipe); got %s' % opt)
         assert 'lr' in opt_args, 'learning rate must be specified in opt_args'
@@ -135,6 +138,7 @@ class Trainer:
         # grad_compress: None = fp32 on the wire (what DistributedDataParallel does, trainer.py:136); 'bf16' halves the xGMI
         # bytes at ~3 significant digits per gradient element (torch's bf16_compress_hook trade-off) -- opt-in
         self.ddp = is_ddp()
+        self._grad_compress = grad_compress
         self.rank = get_ddp_rank() if self.ddp else 0
         model.to(device)
         self.start_epoch = self.start_step = 0
@@ -143,13 +147,23 @@ class Trainer:
         if self.checkpoint_path is not None and os.path.exists(self.checkpoint_path):
             ckpt = self.checkpoint_path
             log('Found existing checkpoint %s: resuming.' % ckpt)
+        # data_parallel (plain branch only, opt-in; the GHN branch ignores it): one replica per rank, see _plain_optimizer
+        self._dp = self._plain and self.ddp and bool(data_parallel)
         if self._plain:
+            if self._dp:
+                dist.barrier()                           # (rank 0 may still be writing the checkpoint all ranks resume from)
+                if self.checkpoint_path is not None and os.path.exists(self.checkpoint_path):
+                    ckpt = self.checkpoint_path
             # (trainer.py:102-133: a checkpoint of the run wins; else `ckpt` names a GHN that predicts the initial parameters)
             if ckpt == self.checkpoint_path and ckpt is not None:
                 state = torch.load(ckpt, map_location='cpu')
                 model.load_state_dict(state['state_dict'])
             elif ckpt is not None:
                 self._ghn_init(model, ckpt, float(beta))
+            if self._dp:
+                # what DistributedDataParallel's constructor does: rank 0's parameters and buffers are the run's (every rank
+                # predicted and drew its own noise above; a resumed checkpoint is the same file everywhere already)
+                sync_module_states(model)
         elif ckpt is not None:
             if self.ddp:
                 dist.barrier()
@@ -204,6 +218,11 @@ class Trainer:
     def scheduler_step(self):
         self._epoch += 1
         self._optimizer.lr = self.base_lr * self._lr_mult(self._epoch)
+        if self._dp:
+            # torch's DDP broadcasts rank 0's buffers before every training forward; here once per epoch: BatchNorm
+            # normalises with batch statistics while training and only rank 0 saves, so nothing a run writes depends on it --
+            # what user code reads between epochs (an evaluation) is the same network on every rank
+            sync_module_states(self._model, parameters=False)
 
     # ------------------------------------------------------------------ one training step
     def update(self, images, targets, graphs=None):
@@ -326,11 +345,11 @@ class Trainer:
 
     # ------------------------------------------------------------------ plain networks (train_ddp.py)
     @staticmethod
-    def _check_plain(opt, bce, mixup, compile_mode):
+    def _check_plain(opt, bce, mixup, compile_mode, data_parallel=False):
         """What the plain-network branch does not take (the GHN branch ignores these arguments, as before)."""
-        if is_ddp():
-            raise NotImplementedError('plain networks train on one GPU here: the data-parallel gradient exchange exists for '
-                                      'the GHN branch only')
+        if is_ddp() and not data_parallel:
+            raise NotImplementedError('plain networks train on one GPU unless Trainer(..., data_parallel=True) is given: the '
+                                      'data-parallel plain branch is opt-in (its exchange has not run on real links)')
         if opt.lower() != 'sgd':
             raise NotImplementedError('plain networks train with SGD (the train_ddp.py recipe); got %s' % opt)
         if bce or mixup:
@@ -358,6 +377,10 @@ class Trainer:
         """FusedSGD, or with GHN3_FUSED_SGD=0 the stock pair behind the same interface (the A/B switch)."""
         kw = {k: opt_args[k] for k in ('momentum', 'weight_decay', 'nesterov', 'dampening') if k in opt_args}
         cls = FusedSGD if os.environ.get('GHN3_FUSED_SGD', '1') != '0' else StockSGD
+        if self._dp:
+            # data parallel: the optimizer gathers the gradients into one flat buffer and the reducer averages it over the ranks
+            # before norm + update, which then run on every rank alike (replicas stay bit-identical with the default exchange)
+            kw['reducer'] = FlatGradReducer(compress=self._grad_compress)
         return cls(model.parameters(), lr=self.base_lr, max_grad_norm=float(self.grad_clip or 0.0), **kw)
 
     def _plain_forward_model(self):

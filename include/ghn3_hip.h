@@ -919,6 +919,19 @@ int ghn3_mt_sumsq(const ghn3_mt_tensor* tensors, const float* const* grads, cons
 int ghn3_mt_sgd(const ghn3_mt_tensor* tensors, const float* const* grads, const ghn3_mt_chunk* chunks, int n_chunks,
                 const float* sumsq, const ghn3_mt_sgd_args* args, void* stream);
 
+/* ---- multi-tensor pack / unpack (added without a version step) ------------------------------------------------------------------
+ * Bit copies between the separate tensors of a table and their segments of ONE flat fp32 buffer (the buffer a data-parallel gradient
+ * exchange or a start-up broadcast wants), one launch each, over the work list of the step above.  DEVICE tables:
+ *   segs   [n_tensors]  segs[k].p = where tensor k's segment starts inside the flat buffer, segs[k].n = its length; .m is unused;
+ *   src/dst[n_tensors]  the tensor on the other side (pack reads it, unpack writes it);
+ *   chunks [n_chunks]   as for ghn3_mt_sgd.
+ * ghn3_mt_pack: segs[k].p[i] = src[k][i]; ghn3_mt_unpack: dst[k][i] = segs[k].p[i], for i in [0, segs[k].n) and nothing else: the
+ * pad floats between segments and whatever surrounds a tensor are not written.  A quad moves as one 16-byte access when both
+ * sides are 16-byte aligned and the quad is whole, else as 4-byte ones: the same bytes either way (NaN payloads, -0.0 included).
+ * No atomics, no allocation, no synchronisation.  n_chunks == 0: GHN3_OK without a launch.  GHN3_E_ARG: a NULL or misaligned table. */
+int ghn3_mt_pack(const ghn3_mt_tensor* segs, const float* const* src, const ghn3_mt_chunk* chunks, int n_chunks, void* stream);
+int ghn3_mt_unpack(const ghn3_mt_tensor* segs, float* const* dst, const ghn3_mt_chunk* chunks, int n_chunks, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
