@@ -5,8 +5,8 @@ parameters predicted by a GHN-3 checkpoint (--ckpt) plus a little noise (--beta)
 ``ghn3_amd.Trainer`` -- the same call sequence (``update`` / ``log`` / ``save`` / ``scheduler_step``) -- on seeded random images.
 
     python examples/train_ddp.py --ckpt ghn3xlm16.pt [--lr 0.025] [--wd 3e-5] [--momentum 0.9] [--label_smooth 0.1]
-                                 [--beta 1e-5] [--amp] [--arch resnet|genotype] [--steps 30] [--epochs 2] [--save DIR]
-                                 [--native-layers]
+                                 [--beta 1e-5] [--amp] [--arch resnet|densenet|preact|genotype] [--steps 30] [--epochs 2]
+                                 [--save DIR] [--native-layers] [--native-windows resnet|all]
 
 Without --ckpt the network keeps its own initialisation.  The optimizer step is the fused multi-tensor SGD (ghn3_amd.FusedSGD);
 GHN3_FUSED_SGD=0 runs stock clip_grad_norm_ + torch.optim.SGD instead.
@@ -66,6 +66,92 @@ class SmallResNet(nn.Module):
         return self.fc(torch.flatten(F.adaptive_avg_pool2d(x, 1), 1))
 
 
+class DenseLayer(nn.Module):
+    def __init__(self, cin, growth, bn_size=4):
+        super().__init__()
+        self.norm1 = nn.BatchNorm2d(cin)
+        self.conv1 = nn.Conv2d(cin, bn_size * growth, 1, bias=False)
+        self.norm2 = nn.BatchNorm2d(bn_size * growth)
+        self.conv2 = nn.Conv2d(bn_size * growth, growth, 3, 1, 1, bias=False)
+
+    def forward(self, x):
+        y = self.conv1(F.relu(self.norm1(x)))
+        return torch.cat([x, self.conv2(F.relu(self.norm2(y)))], 1)
+
+
+class Transition(nn.Module):
+    def __init__(self, cin, cout):
+        super().__init__()
+        self.norm = nn.BatchNorm2d(cin)
+        self.conv = nn.Conv2d(cin, cout, 1, bias=False)
+
+    def forward(self, x):
+        return F.avg_pool2d(self.conv(F.relu(self.norm(x))), 2)
+
+
+class SmallDenseNet(nn.Module):
+    """A DenseNet-BC for 32 x 32 images: three dense blocks of four bottleneck layers (growth 16: every channel count a multiple
+    of four, as the native nodes ask), transitions that halve the channels.  Its BatchNorm layers lead their convolutions:
+    --native-windows all puts them on the native nodes."""
+
+    def __init__(self, num_classes=10, growth=16, layers=4):
+        super().__init__()
+        c = 2 * growth
+        self.conv0 = nn.Conv2d(3, c, 3, 1, 1, bias=False)
+        stages = []
+        for i in range(3):
+            for _ in range(layers):
+                stages.append(DenseLayer(c, growth))
+                c += growth
+            if i < 2:
+                stages.append(Transition(c, c // 2))
+                c //= 2
+        self.features = nn.Sequential(*stages)
+        self.norm = nn.BatchNorm2d(c)
+        self.fc = nn.Linear(c, num_classes)
+
+    def forward(self, x):
+        x = F.relu(self.norm(self.features(self.conv0(x))))
+        return self.fc(torch.flatten(F.adaptive_avg_pool2d(x, 1), 1))
+
+
+class PreActBlock(nn.Module):
+    def __init__(self, cin, cout, stride):
+        super().__init__()
+        self.bn1 = nn.BatchNorm2d(cin)
+        self.conv1 = nn.Conv2d(cin, cout, 3, stride, 1, bias=False)
+        self.bn2 = nn.BatchNorm2d(cout)
+        self.conv2 = nn.Conv2d(cout, cout, 3, 1, 1, bias=False)
+        self.shortcut = nn.Conv2d(cin, cout, 1, stride, bias=False) if (stride != 1 or cin != cout) else None
+
+    def forward(self, x):
+        o = F.relu(self.bn1(x))
+        skip = x if self.shortcut is None else self.shortcut(o)
+        return self.conv2(F.relu(self.bn2(self.conv1(o)))) + skip
+
+
+class SmallPreActResNet(nn.Module):
+    """A pre-activation (v2) ResNet-18-shaped network for 32 x 32 images at a quarter of the width."""
+
+    def __init__(self, num_classes=10, width=16):
+        super().__init__()
+        self.conv1 = nn.Conv2d(3, width, 3, 1, 1, bias=False)
+        layers, cin = [], width
+        for i, cout in enumerate((width, 2 * width, 4 * width, 8 * width)):
+            layers += [PreActBlock(cin, cout, 1 if i == 0 else 2), PreActBlock(cout, cout, 1)]
+            cin = cout
+        self.layers = nn.Sequential(*layers)
+        self.bn = nn.BatchNorm2d(cin)
+        self.fc = nn.Linear(cin, num_classes)
+
+    def forward(self, x):
+        x = F.relu(self.bn(self.layers(self.conv1(x))))
+        return self.fc(torch.flatten(F.adaptive_avg_pool2d(x, 1), 1))
+
+
+PLAIN_NETWORKS = {'resnet': SmallResNet, 'densenet': SmallDenseNet, 'preact': SmallPreActResNet}
+
+
 def genotype_network(num_classes):
     """A DARTS-style network of the DeepNets-1M search space on the native layers (ghn3_amd.ops.Network)."""
     from ghn3_amd import ops
@@ -79,7 +165,7 @@ def genotype_network(num_classes):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--ckpt', default=None, help='GHN-3 checkpoint that predicts the initial parameters')
-    ap.add_argument('--arch', choices=('resnet', 'genotype'), default='resnet')
+    ap.add_argument('--arch', choices=('resnet', 'densenet', 'preact', 'genotype'), default='resnet')
     ap.add_argument('--lr', type=float, default=0.025)
     ap.add_argument('--wd', type=float, default=3e-5)
     ap.add_argument('--momentum', type=float, default=0.9)
@@ -93,17 +179,21 @@ def main():
     ap.add_argument('--save', default=None)
     ap.add_argument('--native-layers', action='store_true',
                     help='run the conv-norm-ReLU, pooling and head layers on the native nodes (ghn3_amd.nativize)')
+    ap.add_argument('--native-windows', choices=('resnet', 'all'), default=None,
+                    help="which windows --native-layers takes; 'all' (implies --native-layers) adds the stand-alone BatchNorm, bare "
+                         'convolutions, concatenations and sums of pre-activation and densely connected networks')
     args = ap.parse_args()
+    native = 'all' if args.native_windows == 'all' else bool(args.native_layers or args.native_windows)
 
     from ghn3_amd import Trainer, log, setup_ddp, clean_ddp
     ddp = setup_ddp()                      # (under torchrun: the process group, device = cuda:LOCAL_RANK; else rank 0 of 1)
     torch.manual_seed(args.seed)
     num_classes = 10
-    model = SmallResNet(num_classes) if args.arch == 'resnet' else genotype_network(num_classes)
+    model = PLAIN_NETWORKS[args.arch](num_classes) if args.arch in PLAIN_NETWORKS else genotype_network(num_classes)
     trainer = Trainer(model, opt='sgd', opt_args={'lr': args.lr, 'weight_decay': args.wd, 'momentum': args.momentum},
                       scheduler='cosine', n_batches=args.steps, grad_clip=5, device=ddp.device, log_interval=10,
                       label_smoothing=args.label_smooth, save_dir=args.save, ckpt=args.ckpt, epochs=args.epochs, amp=args.amp,
-                      beta=args.beta, native_layers=args.native_layers, data_parallel=ddp.ddp)
+                      beta=args.beta, native_layers=native, data_parallel=ddp.ddp)
     log('training %s (%d parameters in %d tensors), %d x %d images per step'
         % (type(model).__name__, sum(p.numel() for p in model.parameters()), len(list(model.parameters())), args.batch_size, 32))
     gen = torch.Generator().manual_seed(args.seed + 1 + ddp.rank)

@@ -22,6 +22,20 @@ CPU the nativized module computes what the original computes, bit for bit.  Tens
 node that reads a native node's result gets it NCHW-contiguous (the stock layers of this ROCm build return wrong gradients for
 channels_last inputs: target_ops' module text).
 
+``nativize(model, windows='all')`` -- opt-in; the default 'resnet' is the table above and nothing else -- adds, after the convolution
+pass, the windows of pre-activation (v2) ResNets and DenseNets, whose BatchNorm does not follow a convolution:
+
+    BatchNorm2d whose only user is a ReLU                target_ops.run_bn_act(relu=True)         'bn_relu'
+    any other BatchNorm2d the first pass left            target_ops.run_bn_act(relu=False)        'bn'
+    any other Conv2d the first pass left for which       target_ops._conv_dispatch(_BARE): the    'conv'
+      `conv_refusal` is None; it leaves `stock_convs`      no-norm member, ConvOnly
+    torch.cat([...], 1) of 2 .. 16 nodes                 target_ops.cell_concat                   'concat'
+    an add of two nodes no window above consumed         target_ops.pair_sum                      'add'
+
+Their counts are in ``report()['windows']`` in that mode only.  The convolutions the dense kernels refuse (`conv_refusal`) keep
+their stock layer and their reason in both modes.  Measured against warmed stock layers the stand-alone BatchNorm node is reported in README.md ("Plain networks");
+it is opt-in whatever the figure.
+
 Every intermediate node of a window has exactly one user; the convolution is bias-free, ungrouped, zero-padded with numeric
 padding, at most 7 x 7 and of one dilation.  Anything else stays stock, and ``report()`` says why.
 """
@@ -36,6 +50,7 @@ from . import target_ops as T
 from .utils import log
 
 WINDOW_KINDS = ('conv_bn_relu', 'conv_bn_add_relu', 'conv_bn', 'pool', 'head')
+EXTRA_KINDS = ('bn_relu', 'bn', 'conv', 'concat', 'add')          # the opt-in windows of nativize(windows='all')
 
 
 def _stock_layout(t):
@@ -112,11 +127,59 @@ class NativeHead(_Window):
         return fc(torch.flatten(pool(_stock_layout(x)), 1)) if out is None else out
 
 
+class NativeBnAct(_Window):
+    """BatchNorm2d [-> ReLU] with no convolution in front of it (windows='all')."""
+
+    def __init__(self, bn, relu):
+        super().__init__(bn=bn)
+        self.relu = bool(relu)
+
+    def forward(self, x):
+        bn = self.layers['bn']
+        out = T.run_bn_act(bn, x, self.relu) if torch.is_tensor(x) and x.dim() == 4 else None
+        if out is not None:
+            return out
+        y = bn(_stock_layout(x))
+        return F.relu(y) if self.relu else y
+
+
+class NativeConv(_Window):
+    """A bare Conv2d the dense kernels take (windows='all'): the no-norm member of the dense-convolution family."""
+
+    def forward(self, x):
+        conv = self.layers['conv']
+        if T._native_input(x, 'GHN3_NATIVE_CONV') and T.zero_padded_conv(conv):
+            xin, w = T._image_pad(x, conv.weight)
+            dil = T._pair(conv.dilation)[0]
+            if T.conv_desc_fits(T._conv_desc(xin, w, conv.stride, conv.padding, dil, False, 0.0)):
+                out = T._conv_dispatch(xin, w, T._BARE, conv.stride, conv.padding, dil, False)
+                if out is not None:
+                    return out
+        return conv(_stock_layout(x))
+
+
+class NativeConcat(_Window):
+    """torch.cat([...], 1) (windows='all'): one join node."""
+
+    def forward(self, *xs):
+        out = T.cell_concat(list(xs)) if all(torch.is_tensor(t) and t.dim() == 4 for t in xs) else None
+        return torch.cat([_stock_layout(t) for t in xs], 1) if out is None else out
+
+
+class NativeAdd(_Window):
+    """a + b of two activations (windows='all'): one join node."""
+
+    def forward(self, a, b):
+        ok = torch.is_tensor(a) and torch.is_tensor(b) and a.dim() == 4 and a.shape == b.shape
+        out = T.pair_sum(a, b) if ok else None
+        return _stock_layout(a) + _stock_layout(b) if out is None else out
+
+
 class NativeReport(dict):
     """What nativize did: `windows` (kind -> count), `stock_convs` (module name -> reason), and `traced`."""
 
     def __str__(self):
-        rows = ['%-18s %d' % (k, self['windows'][k]) for k in WINDOW_KINDS]
+        rows = ['%-18s %d' % kv for kv in self['windows'].items()]
         rows += ['stock %s: %s' % kv for kv in self['stock_convs'].items()]
         return '\n'.join(rows)
 
@@ -144,12 +207,13 @@ def conv_refusal(conv):
 
 
 class _Matcher:
-    def __init__(self, gm):
+    def __init__(self, gm, extra=False):
         self.gm, self.graph = gm, gm.graph
         self.mods = dict(gm.named_modules())
         self.native = set()                 # the windows' nodes: they read either layout
         self.nhwc = set()                   # those of them whose result is channels_last
-        self.windows = dict.fromkeys(WINDOW_KINDS, 0)
+        self.extra = extra                  # windows='all': the opt-in passes, and their keys in the report
+        self.windows = dict.fromkeys(WINDOW_KINDS + (EXTRA_KINDS if extra else ()), 0)
         self.stock = {}
         self.n = 0
 
@@ -295,10 +359,62 @@ class _Matcher:
         if ok:
             self.put(NativeHead(fc), (self.input_of(gp),), node, (node, fl, gp), 'head', nhwc=False)
 
+    # ---- the opt-in windows (windows='all') ----
+    def bn_window(self, b):
+        """A BatchNorm2d the conv pass left: with its ReLU when that is its only user, else alone."""
+        bn, x = self.mods[b.target], self.input_of(b)
+        if not isinstance(x, torch.fx.Node):
+            return
+        users = list(b.users)
+        if len(users) == 1 and self.is_relu(users[0]) and self.input_of(users[0]) is b:
+            self.put(NativeBnAct(bn, True), (x,), users[0], (users[0], b), 'bn_relu')
+        else:
+            self.put(NativeBnAct(bn, False), (x,), b, (b,), 'bn')
+
+    def bare_conv_window(self, c):
+        """A Conv2d the dense kernels take that the first pass left -- not followed by a norm layer (the end of a dense layer, of
+        a transition, of a pre-activation block), several users (a stem whose result is also a skip operand), a norm layer with
+        several users --: it leaves the stock list."""
+        x = self.input_of(c)
+        if conv_refusal(self.mods[c.target]) is None and isinstance(x, torch.fx.Node):
+            self.stock.pop(c.target, None)
+            self.put(NativeConv(conv=self.mods[c.target]), (x,), c, (c,), 'conv')
+
+    def concat_window(self, node):
+        if not ((node.op == 'call_function' and node.target in (torch.cat, torch.concat)) and node.args):
+            return
+        parts = node.args[0]
+        dim = node.args[1] if len(node.args) > 1 else node.kwargs.get('dim', 0)
+        if len(node.args) > 2 or set(node.kwargs) - {'dim'} or dim != 1 or not isinstance(parts, (list, tuple)):
+            return
+        if 2 <= len(parts) <= T.JOIN_MAX_SLICES and all(isinstance(p, torch.fx.Node) for p in parts):
+            self.put(NativeConcat(), tuple(parts), node, (node,), 'concat')
+
+    def add_window(self, node):
+        if not self.is_add(node):
+            return
+        in_place = node.target in (operator.iadd, 'add_')
+        if in_place and len(node.args[0].users) != 1:      # (its other readers see the sum: the call stays what it is)
+            return
+        self.put(NativeAdd(), tuple(node.args), node, (node,), 'add')
+
     def run(self):
         for node in list(self.graph.nodes):
             if node.op == 'call_module' and self.mod(node, nn.Conv2d) is not None:
                 self.conv_window(node)
+        if self.extra:
+            for node in list(self.graph.nodes):
+                if node not in self.native and self.mod(node, nn.BatchNorm2d) is not None:
+                    self.bn_window(node)
+            for node in list(self.graph.nodes):
+                if node not in self.native and self.mod(node, nn.Conv2d) is not None:
+                    self.bare_conv_window(node)
+            for node in list(self.graph.nodes):
+                if node not in self.native:
+                    self.concat_window(node)
+            for node in list(self.graph.nodes):
+                if node not in self.native:
+                    self.add_window(node)
         for node in list(self.graph.nodes):
             if node not in self.native:
                 self.pool_window(node)
@@ -318,10 +434,13 @@ class _Matcher:
         return NativeReport(traced=True, windows=self.windows, stock_convs=self.stock)
 
 
-def nativize(model, strict=False):
+def nativize(model, strict=False, windows='resnet'):
     """`model` (a torch.nn.Module) with its conv -> norm [-> add] -> ReLU, pooling and head windows on the native nodes: a
     torch.fx.GraphModule over the SAME submodules, Parameters and buffers, with `report()`.  A model torch.fx cannot trace (data-
-    dependent control flow) is returned unchanged and the reason logged; strict=True raises instead."""
+    dependent control flow) is returned unchanged and the reason logged; strict=True raises instead.  windows='all' adds the
+    opt-in windows of pre-activation and densely connected networks (the module text; EXTRA_KINDS in the report)."""
+    if windows not in ('resnet', 'all'):
+        raise ValueError("windows is 'resnet' or 'all', not %r" % (windows,))
     try:
         gm = torch.fx.symbolic_trace(model)
     except Exception as e:                                  # (torch.fx raises TraceError, TypeError, ... depending on the construct)
@@ -330,6 +449,6 @@ def nativize(model, strict=False):
         log('nativize: %s cannot be traced (%s: %s): it stays on the stock layers'
             % (type(model).__name__, type(e).__name__, str(e).splitlines()[0] if str(e) else ''))
         return model
-    report = _Matcher(gm).run()
+    report = _Matcher(gm, extra=windows == 'all').run()
     gm.report = lambda: report
     return gm

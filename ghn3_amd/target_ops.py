@@ -49,7 +49,10 @@ Plain ``torch.nn`` networks (ResNet-shaped: ``conv -> BatchNorm -> ReLU``, and `
 block -- the ReLU BEHIND the norm layer, which no member above has) run on the "act" members of the dense-convolution family,
 ``ConvBnAct`` / ``conv_bn_act`` (batch statistics) and ``ConvBnActEval`` / ``conv_bn_act_eval`` (running statistics), through the
 runner ``run_conv_bn_act(conv, bn, x, residual=None)``; ``ghn3_amd.nativize`` (native_net.py) finds these windows in a traced
-module.  GHN3_NATIVE_ACT=0 keeps them stock.
+module.  GHN3_NATIVE_ACT=0 keeps them stock.  A BatchNorm2d [-> ReLU] that follows NO convolution (a DenseNet's dense layer, a
+pre-activation residual block) has a node of its own, ``BnAct`` / ``bn_act`` and ``BnActEval`` / ``bn_act_eval`` (ghn3_bn_act_*,
+csrc/tnet_bnact.hip), through ``run_bn_act(bn, x, relu)``; only ``nativize(windows='all')`` asks for it, and GHN3_NATIVE_BNACT=0
+keeps it stock there too.
 
 ``DwPwBn.applicable`` states what the kernels take (fp32 CUDA tensors, batch statistics, C <= 512, ks <= 7); a layer
 outside of it goes to the two-node form above or keeps the stock path.  There is no CPU implementation: on a CPU tensor the
@@ -769,6 +772,152 @@ def conv_act_reference(x, w, gamma, beta, residual=None, stride=1, padding=0, di
     return F.relu(y if residual is None else y + residual)
 
 
+# ---- a BatchNorm [-> ReLU] that stands alone: ghn3_bn_act_* (csrc/tnet_bnact.hip) -------------------------------------------------
+# The leading layers of a DenseNet's dense layer and of a pre-activation residual block: no convolution in front of the norm layer.
+# Opt-in through ghn3_amd.nativize(windows='all'); GHN3_NATIVE_BNACT=0 keeps the layers stock even there.
+BNACT_MAX_C = 16384
+_BNACT_SCRATCH = 'ghn3_bn_act_scratch_floats'         # (desc, mode): mode = backward | 2 frozen
+
+
+class _BnActDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ('P', 'C', 'relu')] + [('eps', ctypes.c_float)]
+
+
+def bnact_enabled():
+    """GHN3_NATIVE_BNACT=0 keeps every stand-alone BatchNorm [-> ReLU] on the stock layers."""
+    return os.environ.get('GHN3_NATIVE_BNACT', '1') != '0'
+
+
+def bn_act_refusal(x, gamma, beta, frozen=False, running_mean=None, running_var=None):
+    """Why ghn3_bn_act_* do not take the layer, or None when they do.  The rules in the order they are asked -- those of the
+    shape first, so they can be asked of CPU and meta tensors, and they mirror every limit of the C side, so a network never
+    meets the C refusal:
+      'type'     x a 4-d fp32 tensor with at least one element;
+      'channels' C % 4 == 0;
+      'width'    C <= BNACT_MAX_C;
+      'size'     fewer than 2^31 elements;
+      'rows'     batch statistics: P = N H W >= 2 (torch raises for one value per channel: the stock layer has to);
+      'params'   gamma, beta (and the running statistics of a frozen layer) fp32 tensors of C elements on x's device;
+      'device'   CUDA tensors;
+      'switch'   GHN3_NATIVE_BNACT / GHN3_NATIVE_OPS / GHN3_NATIVE_AMP under autocast."""
+    if not (torch.is_tensor(x) and x.dim() == 4 and x.dtype == torch.float32 and x.numel() > 0):
+        return 'type'
+    C = x.shape[1]
+    if C % 4:
+        return 'channels'
+    if C > BNACT_MAX_C:
+        return 'width'
+    if x.numel() >= 2 ** 31:
+        return 'size'
+    if not frozen and x.numel() // C < 2:
+        return 'rows'
+    for t in (gamma, beta) + ((running_mean, running_var) if frozen else ()):
+        if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.numel() == C and t.device == x.device):
+            return 'params'
+    if not x.is_cuda:
+        return 'device'
+    if not (enabled() and bnact_enabled()) or _autocast_excludes():
+        return 'switch'
+    return None
+
+
+def _bn_act_forward(ctx, frozen, x, norm, relu, eps, keep):
+    """The forward of BnAct (norm = (gamma, beta)) and BnActEval (norm = (gamma, beta, running_mean, running_var)): x in either
+    dense layout, the result channels_last.  Returns (out, stats -- None when frozen).  With `keep`, x, the parameters and the
+    statistics are saved; the ReLU mask is recomputed from x in the backward, so `out` is not."""
+    lib = L.load()
+    xc = _aligned(x.contiguous(memory_format=torch.channels_last))
+    norm = [t.contiguous() for t in norm]
+    N, C, H, W = xc.shape
+    d = _BnActDesc(N * H * W, C, int(bool(relu)), float(eps))
+    out = torch.empty((N, C, H, W), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    if frozen:
+        stats = None
+        L._check(lib.ghn3_bn_act_frozen_fwd(ctypes.byref(d), *_ptrs(xc, *norm, out), _stream()), 'ghn3_bn_act_frozen_fwd')
+    else:
+        stats = torch.empty(3 * C, dtype=torch.float32, device=x.device)
+        scratch = torch.empty(_scratch_floats(_BNACT_SCRATCH, d, 0), dtype=torch.float32, device=x.device)
+        L._check(lib.ghn3_bn_act_fwd(ctypes.byref(d), *_ptrs(xc, *norm, out, stats, scratch), _stream()), 'ghn3_bn_act_fwd')
+    if keep:
+        ctx.save_for_backward(xc, *norm, *(() if frozen else (stats,)))
+        ctx.desc = d
+    return out, stats
+
+
+def _bn_act_backward(ctx, frozen, dout):
+    """(dx, dgamma, dbeta) of both members; the parameter gradients are tensors of their own (leaves' .grad)."""
+    lib = L.load()
+    d = ctx.desc
+    xc, g, b, *st = ctx.saved_tensors
+    do = _aligned(dout.contiguous(memory_format=torch.channels_last))
+    dx = torch.empty_like(xc)
+    dg, db = torch.empty_like(g), torch.empty_like(g)
+    scratch = torch.empty(_scratch_floats(_BNACT_SCRATCH, d, 3 if frozen else 1), dtype=torch.float32, device=xc.device)
+    if frozen:
+        rm, rv = st
+        L._check(lib.ghn3_bn_act_frozen_bwd(ctypes.byref(d), *_ptrs(do, xc, g, b, rm, rv, dx, dg, db, scratch), _stream()),
+                 'ghn3_bn_act_frozen_bwd')
+    else:
+        stats, = st
+        L._check(lib.ghn3_bn_act_bwd(ctypes.byref(d), *_ptrs(do, xc, stats, g, b, dx, dg, db, scratch), _stream()), 'ghn3_bn_act_bwd')
+    return dx, dg, db
+
+
+class BnAct(torch.autograd.Function):
+    """BatchNorm (batch statistics) [-> ReLU] on its own as ONE autograd node on ghn3_bn_act_fwd / _bwd (2 launches each); returns
+    (out, stats), stats [3 C] = mean, rstd, biased variance as ConvBn's, not differentiable."""
+
+    @staticmethod
+    def applicable(x, gamma, beta, training_stats=True):
+        return bool(training_stats) and bn_act_refusal(x, gamma, beta) is None
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, relu, eps, keep):
+        out, stats = _bn_act_forward(ctx, False, x, (gamma, beta), relu, eps, keep)
+        ctx.mark_non_differentiable(stats)
+        return out, stats
+
+    @staticmethod
+    def backward(ctx, dout, _dstats):
+        return _bn_act_backward(ctx, False, dout) + (None,) * 3
+
+
+class BnActEval(torch.autograd.Function):
+    """The same with RUNNING statistics (eval mode), read only: ghn3_bn_act_frozen_fwd / _bwd, the per-channel affine map [+ ReLU]."""
+
+    @staticmethod
+    def applicable(x, gamma, beta, running_mean, running_var):
+        return bn_act_refusal(x, gamma, beta, True, running_mean, running_var) is None
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, running_mean, running_var, relu, eps, keep):
+        return _bn_act_forward(ctx, True, x, (gamma, beta, running_mean, running_var), relu, eps, keep)[0]
+
+    @staticmethod
+    def backward(ctx, dout):
+        return _bn_act_backward(ctx, True, dout) + (None,) * 5
+
+
+def bn_act(x, gamma, beta, relu=True, eps=1e-5):
+    """out = relu(batch_norm(x)) (relu=False: batch_norm(x)) with batch statistics; returns (out, stats).  x: (N, C, H, W) fp32
+    CUDA tensor in either dense layout; out is channels_last.  Under torch.no_grad(), or when no input requires a gradient,
+    nothing is saved."""
+    _needs_gpu('bn_act', x)
+    return BnAct.apply(x, gamma, beta, bool(relu), float(eps), _wants_grad(x, gamma, beta))
+
+
+def bn_act_eval(x, gamma, beta, running_mean, running_var, relu=True, eps=1e-5):
+    """The same with the given running statistics (a BatchNorm in eval mode); returns out."""
+    _needs_gpu('bn_act_eval', x)
+    return BnActEval.apply(x, gamma, beta, running_mean, running_var, bool(relu), float(eps), _wants_grad(x, gamma, beta))
+
+
+def bn_act_reference(x, gamma, beta, relu=True, eps=1e-5, running_mean=None, running_var=None):
+    """The stock layers the two nodes replace, functional form -- the parity reference of the tests."""
+    y = F.batch_norm(x, running_mean, running_var, gamma, beta, running_mean is None, 0.1, eps)
+    return F.relu(y) if relu else y
+
+
 class _PatchDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ('N', 'H', 'W', 'C_in', 'C_out', 'kh', 'kw', 'stride_h', 'stride_w', 'Ho', 'Wo', 'nhwc')]
 
@@ -1168,6 +1317,27 @@ def run_conv_bn_act(conv, bn, x, residual=None):
         out, stats = conv_bn_act(xin, w, g, b, *args, False, slot.eps)
         _update_running_stats(slot, stats, out)
         return out
+    return None
+
+
+def run_bn_act(bn, x, relu):
+    """BatchNorm2d [-> ReLU] of a torch.nn network, with no convolution in front of it, on the stand-alone member that fits the
+    norm slot (`_norm_slot`: BnAct with batch statistics, whose running statistics follow as torch's would; BnActEval in eval
+    mode); the NHWC result, or None where the node does not apply -- CPU tensors, another dtype, GHN3_NATIVE_OPS=0,
+    GHN3_NATIVE_BNACT=0, autocast with GHN3_NATIVE_AMP=0, a limit of the kernels, a slot of kind 'none' / 'stock' -- and the
+    caller keeps its stock layers."""
+    if not (bnact_enabled() and _native_input(x) and _is_kind(bn, 'BatchNorm2d')):
+        return None
+    slot = _norm_slot(bn)
+    g, b = slot.gamma, slot.beta
+    if slot.kind == 'batch':
+        if BnAct.applicable(x, g, b):
+            out, stats = bn_act(x, g, b, relu, slot.eps)
+            _update_running_stats(slot, stats, out)
+            return out
+    elif slot.kind == 'frozen':
+        if BnActEval.applicable(x, g, b, slot.mean, slot.var):
+            return bn_act_eval(x, g, b, slot.mean, slot.var, relu, slot.eps)
     return None
 
 

@@ -177,8 +177,12 @@ class Trainer:
         self._model = model
         # native_layers (plain branch only; the GHN branch ignores it): the forward runs ghn3_amd.nativize(model), a view of the
         # SAME modules and Parameters on the native conv-norm-ReLU, pooling and head nodes.  self._model stays the original, so
-        # checkpoints, the GHN initialisation and the optimizer do not see the difference.
-        self._native_layers = bool(native_layers) and self._plain
+        # checkpoints, the GHN initialisation and the optimizer do not see the difference.  native_layers='all' also asks for the
+        # opt-in windows (nativize(windows='all'): stand-alone BatchNorm, bare convolutions, concatenations and sums); the value
+        # itself is kept, not its truth.
+        if native_layers not in (False, True, None, 'all'):
+            raise ValueError("native_layers is False, True or 'all', not %r" % (native_layers,))
+        self._native_layers = (native_layers or False) if self._plain else False
         self._forward_model = None
         self.base_lr = float(opt_args['lr'])
         if self._plain:
@@ -390,7 +394,7 @@ class Trainer:
             return self._model
         if self._forward_model is None:
             from .native_net import nativize
-            self._forward_model = nativize(self._model)
+            self._forward_model = nativize(self._model, windows='all' if self._native_layers == 'all' else 'resnet')
         return self._forward_model
 
     def _update_plain(self, images, targets):

@@ -890,6 +890,39 @@ int ghn3_join_fwd(const ghn3_join_desc* desc, float* out, void* stream);
 int ghn3_join_bwd(const ghn3_join_desc* desc, const float* dout, void* stream);
 int ghn3_posenc_bwd(int N, int C, int H, int W, int layout, const float* dy, float* dw, void* stream);
 
+/* ---- stand-alone BatchNorm [+ ReLU] (ABI v21, added without a version step: symbols only) --------------------------------------
+ * A BatchNorm2d that does not follow a convolution -- the leading layers of a DenseNet's dense layer and of a pre-activation
+ * residual block -- on the family's storage: x, out, dout, dx are [P = N H W][C] fp32 (NHWC), gamma / beta [C],
+ *   out = act(gamma xhat + beta),  xhat = (x - mean) rstd,  rstd = 1 / sqrt(var + desc->eps),  act = ReLU when desc->relu, else none.
+ * Batch statistics (the entry points without "frozen"): mean and the biased variance of x over the P rows; stats [3 C] = mean,
+ * rstd, variance is written by the forward -- the layout the convolution members write -- and read by the backward.  Frozen
+ * (running) statistics: mean / var [C] are read only, and the op is the per-channel affine map + act.
+ * Statistics are per row-chunk (mean, M2) per channel, Chan-combined in a fixed order, never sum / sum of squares: a channel whose
+ * mean lies 100 standard deviations from zero keeps its variance.  No atomics: the same bits on every run.
+ * Launches: batch forward 2 (partial statistics; the apply pass, in which every workgroup combines the partials of its own channel
+ * block in the same order and the workgroups of the first row block write stats), batch backward 2 (partial sum g and sum g xhat;
+ * the dx pass, which finalises the same way and writes dgamma = sum g xhat and dbeta = sum g), frozen forward 1, frozen backward
+ * 2 (dx = g gamma rstd beside the partial sums; a pass of parameter size for dgamma / dbeta).  16 bytes per lane on x, out,
+ * dout and dx; more than 1024 channels loop over channel blocks inside a workgroup.
+ * The backward's ReLU mask, g = dout 1[y > 0], is RECOMPUTED from x where dout is first read (the pre-activation y with the
+ * forward's own instruction sequence, so its bits are the forward's): neither out nor anything else of activation size is
+ * saved besides x, and the backward does not read out.
+ * Limits (GHN3_E_LIMIT: the caller keeps its stock layer): C % 4 == 0, C <= 16384, P C < 2^31, and P >= 2 with batch statistics
+ * (torch raises for one value per channel).  x, out, dout, dx must start on 16 bytes (GHN3_E_ARG); gamma, beta, mean, var, stats,
+ * dgamma, dbeta may start anywhere.
+ * `scratch` = the floats the size function answers for (desc, mode), mode = backward | 2 frozen (a negative GHN3_E_* code for a
+ * descriptor the op does not take; 0 for mode 2, whose entry point takes no scratch).  No allocation, no synchronisation inside. */
+typedef struct ghn3_bnact_desc { int32_t P, C, relu; float eps; } ghn3_bnact_desc;
+int64_t ghn3_bn_act_scratch_floats(const ghn3_bnact_desc* desc, int mode);      /* < 0: bad descriptor (ghn3_last_error) */
+int ghn3_bn_act_fwd(const ghn3_bnact_desc* desc, const float* x, const float* gamma, const float* beta, float* out, float* stats,
+                    float* scratch, void* stream);
+int ghn3_bn_act_bwd(const ghn3_bnact_desc* desc, const float* dout, const float* x, const float* stats, const float* gamma,
+                    const float* beta, float* dx, float* dgamma, float* dbeta, float* scratch, void* stream);
+int ghn3_bn_act_frozen_fwd(const ghn3_bnact_desc* desc, const float* x, const float* gamma, const float* beta, const float* mean,
+                           const float* var, float* out, void* stream);
+int ghn3_bn_act_frozen_bwd(const ghn3_bnact_desc* desc, const float* dout, const float* x, const float* gamma, const float* beta,
+                           const float* mean, const float* var, float* dx, float* dgamma, float* dbeta, float* scratch, void* stream);
+
 /* ---- multi-tensor SGD step for plain networks (ABI v21, added without a version step) ------------------------------------------
  * nn.utils.clip_grad_norm_ + torch.optim.SGD over a table of separate fp32 tensors (a network's parameters, their gradients and
  * the optimizer's momentum buffers) in two launches, whatever the number of tensors.  Every table lives in DEVICE memory:
