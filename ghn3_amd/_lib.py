@@ -85,7 +85,8 @@ EXPORTS = ['ghn3_abi_version', 'ghn3_last_error', 'ghn3_ctx_create', 'ghn3_ctx_d
            'ghn3_mt_sumsq', 'ghn3_mt_sgd', 'ghn3_mt_pack', 'ghn3_mt_unpack',
            'ghn3_conv_act_scratch_floats', 'ghn3_conv_bn_act_fwd', 'ghn3_conv_bn_act_bwd', 'ghn3_conv_frozen_act_fwd',
            'ghn3_conv_frozen_act_bwd',
-           'ghn3_bn_act_scratch_floats', 'ghn3_bn_act_fwd', 'ghn3_bn_act_bwd', 'ghn3_bn_act_frozen_fwd', 'ghn3_bn_act_frozen_bwd']
+           'ghn3_bn_act_scratch_floats', 'ghn3_bn_act_fwd', 'ghn3_bn_act_bwd', 'ghn3_bn_act_frozen_fwd', 'ghn3_bn_act_frozen_bwd',
+           'ghn3_conv_bias_act_scratch_floats', 'ghn3_conv_bias_act_fwd', 'ghn3_conv_bias_act_bwd']
 OPFLAG_TIMED = 0x100
 OPFLAG_SIDE = 0x200
 
@@ -162,6 +163,10 @@ def load():
         lib.ghn3_conv_bn_act_bwd.argtypes = [ctypes.c_void_p] * 15
         lib.ghn3_conv_frozen_act_fwd.argtypes = [ctypes.c_void_p] * 12
         lib.ghn3_conv_frozen_act_bwd.argtypes = [ctypes.c_void_p] * 16
+        lib.ghn3_conv_bias_act_scratch_floats.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        lib.ghn3_conv_bias_act_scratch_floats.restype = ctypes.c_int64
+        lib.ghn3_conv_bias_act_fwd.argtypes = [ctypes.c_void_p] * 8
+        lib.ghn3_conv_bias_act_bwd.argtypes = [ctypes.c_void_p] * 11
         lib.ghn3_bn_act_scratch_floats.argtypes = [ctypes.c_void_p, ctypes.c_int]
         lib.ghn3_bn_act_scratch_floats.restype = ctypes.c_int64
         lib.ghn3_bn_act_fwd.argtypes = [ctypes.c_void_p] * 8

@@ -1284,8 +1284,12 @@ namespace {
 //    barrier per chunk), the A pieces are stored as 16-byte vectors;
 //  * the backward reads dz from a buffer written once (tnet_dz_kernel).
 // BWD = false: dst = z[P_dst = output pixels][R = C_out] from src = x;  BWD = true: dst = dx[input pixels][R = C_in] from src = dz.
-// FROZEN (forward only): the norm layer behind the convolution has frozen statistics: its affine map is applied to the
-// accumulators and stored to fz.out, dst = z is stored as well when it is non-null, and the kernel ends there (no statistics).
+// EPI, what the forward does with its accumulators (the backward has EPI_STATS and stores dx alone):
+//  * EPI_STATS: dst = z and the per-tile (mean, M2) of every channel to `part`;
+//  * EPI_FROZEN: the norm layer behind the convolution has frozen statistics: its affine map is applied to the accumulators and
+//    stored to ep.fz.out, dst = z is stored as well when it is non-null, and the kernel ends there (no statistics);
+//  * EPI_BIAS (the "bias" member): ep.fz.out = act(acc + ep.bias[c] [+ ep.res]), act = ReLU when ep.act else the identity; dst and
+//    `part` are not touched, nothing else is stored.
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void tnet_conv_w_pack_kernel(const float* __restrict__ w, unsigned short* __restrict__ wp, int C_out,
                                                                int C_in, int taps, int transposed) {
@@ -1366,12 +1370,22 @@ __global__ __launch_bounds__(256) void tnet_dz_act_kernel(const float* __restric
     }
 }
 
-template <int NT, bool BWD, bool FROZEN = false>
+constexpr int EPI_STATS = 0, EPI_FROZEN = 1, EPI_BIAS = 2;
+
+// The epilogue's operands: the frozen norm layer's constants and the result's address (EPI_FROZEN; EPI_BIAS uses fz.out alone),
+// the bias [C_out], the skip tensor [P][C_out] or null, and whether the result is clamped at zero (EPI_BIAS).
+struct ConvEpi {
+    Frozen fz;
+    const float *bias, *res;
+    int act;
+};
+
+template <int NT, bool BWD, int EPI = EPI_STATS>
 __global__ __launch_bounds__(256) void tnet_conv2_kernel(const float* __restrict__ src, const unsigned short* __restrict__ wp,
                                                          float* __restrict__ dst, float* __restrict__ part,
                                                          const float* __restrict__ xmask, const CDesc d, const int P_dst, const int P_src,
-                                                         const Frozen fz) {
-    static_assert(!(BWD && FROZEN), "the frozen norm layer is an epilogue of the forward");
+                                                         const ConvEpi ep) {
+    static_assert(!(BWD && EPI != EPI_STATS), "the epilogues are the forward's");
     constexpr int S = 3;
     constexpr int A_BUF = S * TP * LDK, B_BUF = S * 16 * NT * LDK;             // 16-bit elements per stage
     constexpr int NB = (S * 16 * NT * 4 + 255) / 256;                          // 16-byte units of the B tile per thread
@@ -1495,13 +1509,29 @@ __global__ __launch_bounds__(256) void tnet_conv2_kernel(const float* __restrict
     }
     const int prow = p0 + 16 * w + r16;
     const bool valid = prow < P_dst;
-    if constexpr (FROZEN) {
+    if constexpr (EPI == EPI_FROZEN) {
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
             const int col = col0 + 16 * j + 4 * kc;
             if (valid && col < R) {
                 if (dst) *reinterpret_cast<f32x4*>(dst + (int64_t)prow * R + col) = acc[j];
-                *reinterpret_cast<f32x4*>(fz.out + (int64_t)prow * R + col) = frozen_affine4(acc[j], fz, col, d.eps);
+                *reinterpret_cast<f32x4*>(ep.fz.out + (int64_t)prow * R + col) = frozen_affine4(acc[j], ep.fz, col, d.eps);
+            }
+        }
+        return;
+    }
+    if constexpr (EPI == EPI_BIAS) {
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            const int col = col0 + 16 * j + 4 * kc;
+            if (valid && col < R) {
+                f32x4 v = acc[j] + *reinterpret_cast<const f32x4*>(ep.bias + col);
+                if (ep.res) v += *reinterpret_cast<const f32x4*>(ep.res + (int64_t)prow * R + col);
+                if (ep.act) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+                }
+                *reinterpret_cast<f32x4*>(ep.fz.out + (int64_t)prow * R + col) = v;
             }
         }
         return;
@@ -1662,7 +1692,7 @@ int conv_bwd_products(const CDesc& d, const CPlan& pl, const CScratch& sc, const
     const dim3 grid(pl.n_tiles_in, (d.C_in + 16 * NT - 1) / (16 * NT));
     const size_t lds = conv2_lds(NT);
 #define C2B_CASE(n) case n: rc = tnet_raise_lds(tnet_conv2_kernel<n, true>, lds); if (rc) return rc; \
-    hipLaunchKernelGGL((tnet_conv2_kernel<n, true>), grid, dim3(256), lds, s, dz, wp, dx, (float*)nullptr, x, d, pl.P_in, pl.P, Frozen{}); break;
+    hipLaunchKernelGGL((tnet_conv2_kernel<n, true>), grid, dim3(256), lds, s, dz, wp, dx, (float*)nullptr, x, d, pl.P_in, pl.P, ConvEpi{}); break;
     switch (NT) { C2B_CASE(2) C2B_CASE(4) C2B_CASE(8) }
 #undef C2B_CASE
     TNET_LAUNCH_CHECK("conv bwd data")
@@ -1674,13 +1704,13 @@ int conv_bwd_products(const CDesc& d, const CPlan& pl, const CScratch& sc, const
     return reduce_rows(part_w, pl.w_chunks, wr, dw, d.C_out * d.C_in, pl.taps, s, "conv wgrad reduce");
 }
 
-// The forward convolution of both members: weight pack, then the implicit GEMM.  Not FROZEN: z = the convolution's result, the
-// per-tile statistics to the scratch's `part`.  FROZEN: the affine map of `fz` in the epilogue (fz.out the result, z beside it when
-// non-null), no statistics.
-template <bool FROZEN>
-int conv_fwd_launch(const CDesc& d, const CPlan& pl, const CScratch& sc, const float* x, const float* w, float* z, const Frozen& fz,
+// The forward convolution of every member: weight pack, then the implicit GEMM.  EPI_STATS: z = the convolution's result, the
+// per-tile statistics to the scratch's `part`.  EPI_FROZEN: the affine map of `ep.fz` in the epilogue (ep.fz.out the result, z
+// beside it when non-null), no statistics.  EPI_BIAS: ep.fz.out = act(result + bias [+ res]), z not touched, no statistics.
+template <int EPI>
+int conv_fwd_launch(const CDesc& d, const CPlan& pl, const CScratch& sc, const float* x, const float* w, float* z, const ConvEpi& ep,
                     float* scratch, hipStream_t s, const char* what) {
-    float* const part = FROZEN ? nullptr : scratch + sc.part;
+    float* const part = EPI != EPI_STATS ? nullptr : scratch + sc.part;
     unsigned short* wp = reinterpret_cast<unsigned short*>(scratch + sc.wp);
     const int64_t plane = (int64_t)pl.taps * d.C_out * ((d.C_in + KC - 1) / KC * KC);
     hipLaunchKernelGGL(tnet_conv_w_pack_kernel, grid1d(plane, 2048), dim3(256), 0, s, w, wp, d.C_out, d.C_in, pl.taps, 0);
@@ -1689,8 +1719,8 @@ int conv_fwd_launch(const CDesc& d, const CPlan& pl, const CScratch& sc, const f
     const dim3 grid(pl.n_tiles, (d.C_out + 16 * NT - 1) / (16 * NT));
     const size_t lds = conv2_lds(NT);
     int rc;
-#define C2F_CASE(n) case n: rc = tnet_raise_lds(tnet_conv2_kernel<n, false, FROZEN>, lds); if (rc) return rc; \
-    hipLaunchKernelGGL((tnet_conv2_kernel<n, false, FROZEN>), grid, dim3(256), lds, s, x, wp, z, part, (const float*)nullptr, d, pl.P, pl.P_in, fz); break;
+#define C2F_CASE(n) case n: rc = tnet_raise_lds(tnet_conv2_kernel<n, false, EPI>, lds); if (rc) return rc; \
+    hipLaunchKernelGGL((tnet_conv2_kernel<n, false, EPI>), grid, dim3(256), lds, s, x, wp, z, part, (const float*)nullptr, d, pl.P, pl.P_in, ep); break;
     switch (NT) { C2F_CASE(2) C2F_CASE(4) C2F_CASE(8) }
 #undef C2F_CASE
     return launched(what);
@@ -1752,7 +1782,7 @@ extern "C" int ghn3_conv_bn_fwd(const ghn3_conv_desc* g, const float* x, const f
     hipStream_t s = (hipStream_t)stream_;
     const CPlan pl = make_cplan(d);
     const CScratch sc = conv_scratch(d, pl, false, false);
-    rc = conv_fwd_launch<false>(d, pl, sc, x, w, z, Frozen{}, scratch, s, "conv fwd");
+    rc = conv_fwd_launch<EPI_STATS>(d, pl, sc, x, w, z, ConvEpi{}, scratch, s, "conv fwd");
     if (rc || no_norm) return rc;
     return bn_apply_launch(scratch + sc.part, pl.n_tiles, pl.P, d.C_out, d.eps, z, gamma, beta, stats, out, s);
 }
@@ -1779,8 +1809,9 @@ extern "C" int ghn3_conv_frozen_fwd(const ghn3_conv_desc* g, const float* x, con
     if (g->relu & GHN3_CONV_NO_NORM) { ghn3_set_error("conv frozen: GHN3_CONV_NO_NORM has no meaning here"); return GHN3_E_ARG; }
     if (!x || !w || !gamma || !beta || !mean || !var || !out || !scratch) { ghn3_set_error("conv frozen fwd: null pointer"); return GHN3_E_ARG; }
     const CPlan pl = make_cplan(d);
-    return conv_fwd_launch<true>(d, pl, conv_scratch(d, pl, true, false), x, w, z, Frozen{gamma, beta, mean, var, out}, scratch,
-                                 (hipStream_t)stream_, "conv frozen fwd");
+    return conv_fwd_launch<EPI_FROZEN>(d, pl, conv_scratch(d, pl, true, false), x, w, z,
+                                       ConvEpi{Frozen{gamma, beta, mean, var, out}, nullptr, nullptr, 0}, scratch, (hipStream_t)stream_,
+                                       "conv frozen fwd");
 }
 
 extern "C" int ghn3_conv_frozen_bwd(const ghn3_conv_desc* g, const float* dout, const float* x, const float* z, const float* w,
@@ -1882,7 +1913,7 @@ extern "C" int ghn3_conv_bn_act_fwd(const ghn3_conv_desc* g, const float* x, con
     hipStream_t s = (hipStream_t)stream_;
     const CPlan pl = make_cplan(d);
     const CScratch sc = conv_act_scratch(d, pl, false, false).sc;
-    rc = conv_fwd_launch<false>(d, pl, sc, x, w, z, Frozen{}, scratch, s, "conv act fwd");
+    rc = conv_fwd_launch<EPI_STATS>(d, pl, sc, x, w, z, ConvEpi{}, scratch, s, "conv act fwd");
     if (rc) return rc;
     hipLaunchKernelGGL(tnet_bn_finalize_kernel, dim3((d.C_out + 15) / 16), dim3(256), 0, s, scratch + sc.part, pl.n_tiles, pl.P, d.C_out, d.eps,
                        stats);
@@ -1910,7 +1941,7 @@ extern "C" int ghn3_conv_frozen_act_fwd(const ghn3_conv_desc* g, const float* x,
     hipStream_t s = (hipStream_t)stream_;
     const CPlan pl = make_cplan(d);
     const CScratch sc = conv_act_scratch(d, pl, true, false).sc;
-    rc = conv_fwd_launch<false>(d, pl, sc, x, w, z, Frozen{}, scratch, s, "conv frozen act fwd");
+    rc = conv_fwd_launch<EPI_STATS>(d, pl, sc, x, w, z, ConvEpi{}, scratch, s, "conv frozen act fwd");
     if (rc) return rc;
     rc = frozen_stats(mean, var, d.eps, d.C_out, scratch + sc.stats, s);
     if (rc) return rc;
@@ -1923,6 +1954,110 @@ extern "C" int ghn3_conv_frozen_act_bwd(const ghn3_conv_desc* g, const float* do
     return conv_act_bwd_core(g, true, "conv frozen act bwd",
                              dout && out && x && z && w && gamma && mean && var && dx && dw && dgamma && dbeta && scratch, dout, out, x, z,
                              nullptr, w, gamma, mean, var, dx, dw, dgamma, dbeta, dres, scratch, stream_);
+}
+
+// ---- the "bias" member: [ReLU ->] convolution + bias [+ skip] [-> ReLU], the layers of networks WITHOUT norm layers ------------
+//   out = act(conv(relu(x) if desc->relu & 1 else x, w) + bias[c] [+ res]),  act = ReLU with GHN3_CONV_ACT_OUT in desc->relu
+// Forward: weight pack + the convolution kernel with the EPI_BIAS epilogue (2 launches); nothing but `out` is stored -- with the
+// ReLU it carries the mask 1[out > 0], torch's rule -- and no statistics pass runs.  Backward: ONE pass over dout per 64-pixel
+// tile (tnet_bias_bwd_partial_kernel) forms g = dout 1[out > 0] (g = dout without the ReLU), writes it to the scratch's dz (with
+// the ReLU) and to dres (when wanted) and leaves the tile's column sums; reduce_rows adds them to dbias in a fixed order; then
+// conv_bwd_products on dz -- or on dout itself without the ReLU, which is then never copied: ConvOnly's launches + 2.
+// Scratch: forward = the frozen member's forward layout (the weight pack alone); backward = the batch member's backward layout
+// (`part` holds the [tiles][C_out] column sums in the first half of its area, s12 is not used).
+namespace {
+
+// part[tile][c] = sum over the tile's pixels of g, g = dout 1[out > 0] (out == null: g = dout); dz / dres [P][C] = g where
+// non-null.  Geometry, LDS and summation order of tnet_bn_bwd_partial_kernel, in both of its arms, with one sum per channel.
+__global__ __launch_bounds__(256) void tnet_bias_bwd_partial_kernel(const float* __restrict__ dout, const float* __restrict__ out,
+                                                                    float* __restrict__ dz, float* __restrict__ dres,
+                                                                    float* __restrict__ part, int P, int C) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    float* red = reinterpret_cast<float*>(smem);                               // [ng][C]
+    const int nq = C / 4, ng = max(1, 256 / nq);
+    const int g = threadIdx.x / nq, q = threadIdx.x % nq, c = 4 * q;
+    const int p0 = blockIdx.x * TP, p1 = min(P, p0 + TP);
+    auto masked = [&](int64_t at) {
+        f32x4 gd = *reinterpret_cast<const f32x4*>(dout + at);
+        if (out) gd = act_masked(gd, *reinterpret_cast<const f32x4*>(out + at));
+        if (dz) *reinterpret_cast<f32x4*>(dz + at) = gd;
+        if (dres) *reinterpret_cast<f32x4*>(dres + at) = gd;
+        return gd;
+    };
+    if (nq > 256) {
+        for (int cw = 4 * threadIdx.x; cw < C; cw += 1024) {
+            f32x4 s1 = {0.f, 0.f, 0.f, 0.f};
+            for (int p = p0; p < p1; ++p) s1 += masked((int64_t)p * C + cw);
+            *reinterpret_cast<f32x4*>(part + (int64_t)blockIdx.x * C + cw) = s1;
+        }
+        return;
+    }
+    if (g < ng) {
+        f32x4 s1 = {0.f, 0.f, 0.f, 0.f};
+        for (int p = p0 + g; p < p1; p += ng) s1 += masked((int64_t)p * C + c);
+        *reinterpret_cast<f32x4*>(red + g * C + c) = s1;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < C; i += 256) {
+        float s = 0.f;
+        for (int k = 0; k < ng; ++k) s += red[k * C + i];
+        part[(int64_t)blockIdx.x * C + i] = s;
+    }
+}
+
+// bit 1 of desc->relu is the ReLU on x (CDesc.relu, which the kernels test for truth), GHN3_CONV_ACT_OUT the one on the result
+int check_bias_desc(const ghn3_conv_desc* g, CDesc& d, const char* who) {
+    const int rc = check_cdesc(g, d);
+    if (rc) return rc;
+    if (g->relu & GHN3_CONV_NO_NORM) { ghn3_set_error("%s: GHN3_CONV_NO_NORM has no meaning here", who); return GHN3_E_ARG; }
+    return GHN3_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t ghn3_conv_bias_act_scratch_floats(const ghn3_conv_desc* g, int backward) {
+    CDesc d;
+    const int rc = check_bias_desc(g, d, "conv bias act");
+    if (rc) return rc;                                            // GHN3_E_ARG / GHN3_E_LIMIT
+    return conv_scratch(d, make_cplan(d), backward == 0, backward != 0).total;
+}
+
+extern "C" int ghn3_conv_bias_act_fwd(const ghn3_conv_desc* g, const float* x, const float* w, const float* bias, const float* res,
+                                      float* out, float* scratch, void* stream_) {
+    CDesc d;
+    const int rc = check_bias_desc(g, d, "conv bias act fwd");
+    if (rc) return rc;
+    if (!x || !w || !bias || !out || !scratch) { ghn3_set_error("conv bias act fwd: null pointer"); return GHN3_E_ARG; }
+    const CPlan pl = make_cplan(d);
+    const ConvEpi ep = {Frozen{nullptr, nullptr, nullptr, nullptr, out}, bias, res, (g->relu & GHN3_CONV_ACT_OUT) != 0};
+    return conv_fwd_launch<EPI_BIAS>(d, pl, conv_scratch(d, pl, true, false), x, w, nullptr, ep, scratch, (hipStream_t)stream_,
+                                     "conv bias act fwd");
+}
+
+extern "C" int ghn3_conv_bias_act_bwd(const ghn3_conv_desc* g, const float* dout, const float* out, const float* x, const float* w,
+                                      float* dx, float* dw, float* dbias, float* dres, float* scratch, void* stream_) {
+    CDesc d;
+    int rc = check_bias_desc(g, d, "conv bias act bwd");
+    if (rc) return rc;
+    const bool act = (g->relu & GHN3_CONV_ACT_OUT) != 0;
+    if (!dout || (act && !out) || !x || !w || !dx || !dw || !dbias || !scratch) {
+        ghn3_set_error("conv bias act bwd: null pointer");
+        return GHN3_E_ARG;
+    }
+    hipStream_t s = (hipStream_t)stream_;
+    const CPlan pl = make_cplan(d);
+    const CScratch sc = conv_scratch(d, pl, false, true);
+    // 1. g = dout 1[out > 0] -> dz (only with the ReLU: without it dout IS dz), dres; the tiles' column sums -> dbias
+    float* const dz = act ? scratch + sc.dz : nullptr;
+    float* const part = scratch + sc.part;
+    const int nq = d.C_out / 4, ng = std::max(1, 256 / nq);
+    hipLaunchKernelGGL(tnet_bias_bwd_partial_kernel, dim3(pl.n_tiles), dim3(256), nq > 256 ? 0 : (size_t)ng * d.C_out * 4, s, dout,
+                       act ? out : nullptr, dz, dres, part, pl.P, d.C_out);
+    TNET_LAUNCH_CHECK("conv bias bwd partial")
+    rc = reduce_rows(part, pl.n_tiles, d.C_out, dbias, 0, 0, s, "conv bias bwd reduce");
+    if (rc) return rc;
+    // 2. weight pack, dx, dW and its reduction, as for every member
+    return conv_bwd_products(d, pl, sc, act ? dz : dout, x, w, dx, dw, scratch, s);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

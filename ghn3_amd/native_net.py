@@ -36,8 +36,27 @@ Their counts are in ``report()['windows']`` in that mode only.  The convolutions
 their stock layer and their reason in both modes.  Measured against warmed stock layers the stand-alone BatchNorm node is reported in README.md ("Plain networks");
 it is opt-in whatever the figure.
 
-Every intermediate node of a window has exactly one user; the convolution is bias-free, ungrouped, zero-padded with numeric
-padding, at most 7 x 7 and of one dilation.  Anything else stays stock, and ``report()`` says why.
+``nativize(model, biased=True)`` -- a third opt-in, with either `windows` value -- takes the convolutions WITH a bias (``nn.Conv2d``'s
+default; VGG, AlexNet, SqueezeNet and other networks without norm layers), which `conv_refusal` otherwise answers first, and the
+classifier such networks end in:
+
+    Conv2d(bias) -> ReLU                                 target_ops.run_conv_bias_act(relu=True)  'conv_bias_relu'
+    Conv2d(bias) -> add(., r) -> ReLU                    ... (relu=True, residual=r)              'conv_bias_add_relu'
+    any other Conv2d(bias) for which `conv_refusal(conv, ... (relu=False); it leaves              'conv_bias'
+      biased=True)` is None                                `stock_convs`
+    flatten(1) -> Linear (-> ReLU -> Dropout -> Linear)  target_ops.run_classifier_head(None, .)  'mlp_head'
+      x 1 .. 3: 2 .. 4 linears                             on a Sequential over the SAME modules
+    AdaptiveAvgPool2d(size) / F.adaptive_avg_pool2d      the input itself where its map already   'same_size_pool'
+      with a constant size other than 1                    has that size (the mean of ONE element:
+                                                           exact), else the stock layer
+
+Their counts are in ``report()['windows']`` in that mode only (BIAS_KINDS).  A bias is never folded into a BatchNorm behind the
+convolution: that BatchNorm is taken by the 'bn_relu' / 'bn' windows under windows='all' and stays stock under 'resnet'.  The
+one-linear 'head' window is tried first and is unchanged.  Measured against warmed stock layers the node is reported in README.md
+("Plain networks"); it is opt-in whatever the figure.
+
+Every intermediate node of a window has exactly one user; the convolution is ungrouped, zero-padded with numeric padding, at most
+7 x 7 and of one dilation -- and bias-free unless biased=True.  Anything else stays stock, and ``report()`` says why.
 """
 
 import operator
@@ -51,6 +70,7 @@ from .utils import log
 
 WINDOW_KINDS = ('conv_bn_relu', 'conv_bn_add_relu', 'conv_bn', 'pool', 'head')
 EXTRA_KINDS = ('bn_relu', 'bn', 'conv', 'concat', 'add')          # the opt-in windows of nativize(windows='all')
+BIAS_KINDS = ('conv_bias_relu', 'conv_bias_add_relu', 'conv_bias', 'mlp_head', 'same_size_pool')     # those of nativize(biased=True)
 
 
 def _stock_layout(t):
@@ -158,6 +178,51 @@ class NativeConv(_Window):
         return conv(_stock_layout(x))
 
 
+class NativeConvBias(_Window):
+    """Conv2d with a bias [-> + residual] [-> ReLU] (biased=True): the "bias" member of the dense-convolution family."""
+
+    def __init__(self, conv, relu):
+        super().__init__(conv=conv)
+        self.relu = bool(relu)
+
+    def forward(self, x, residual=None):
+        conv = self.layers['conv']
+        out = T.run_conv_bias_act(conv, x, self.relu, residual) if torch.is_tensor(x) and x.dim() == 4 else None
+        if out is not None:
+            return out
+        y = conv(_stock_layout(x))
+        if residual is not None:
+            y = y + _stock_layout(residual)
+        return F.relu(y) if self.relu else y
+
+
+class NativeMlpHead(_Window):
+    """flatten(1) -> Linear (-> ReLU -> Dropout -> Linear)*, 2 .. 4 linears (biased=True): the classifier head without its pool."""
+
+    def __init__(self, modules):
+        super().__init__(**{'m%d' % k: m for k, m in enumerate(modules)})
+        self.__dict__['seq'] = nn.Sequential(*modules)             # (over the SAME modules; outside the registry)
+
+    def forward(self, x):
+        seq = self.__dict__['seq']
+        out = T.run_classifier_head(None, seq, x) if torch.is_tensor(x) and x.dim() == 4 else None
+        return seq(torch.flatten(_stock_layout(x), 1)) if out is None else out
+
+
+class NativeSameSizePool(_Window):
+    """An adaptive average pool to a constant size (biased=True): the input itself where its map has that size already."""
+
+    def __init__(self, stock, size):
+        super().__init__(pool=stock if isinstance(stock, nn.Module) else None)
+        self.__dict__['stock'] = stock
+        self.size = size
+
+    def forward(self, x):
+        if torch.is_tensor(x) and x.dim() == 4 and tuple(x.shape[-2:]) == self.size:
+            return x
+        return self.__dict__['stock'](_stock_layout(x))
+
+
 class NativeConcat(_Window):
     """torch.cat([...], 1) (windows='all'): one join node."""
 
@@ -189,9 +254,10 @@ _RELU_FUNCTIONS = (F.relu, torch.relu, torch.relu_, F.relu_)
 _ADD_FUNCTIONS = (operator.add, operator.iadd, torch.add)
 
 
-def conv_refusal(conv):
-    """Why the dense kernels do not take this Conv2d, or None.  Asked of the layer itself, padding_mode included."""
-    if conv.bias is not None:
+def conv_refusal(conv, biased=False):
+    """Why the dense kernels do not take this Conv2d, or None.  Asked of the layer itself, padding_mode included.  biased=True:
+    the answer of nativize(biased=True), where a bias is no reason."""
+    if conv.bias is not None and not biased:
         return 'biased convolution'
     if conv.groups != 1:
         return 'grouped convolution (groups=%d)' % conv.groups
@@ -207,13 +273,14 @@ def conv_refusal(conv):
 
 
 class _Matcher:
-    def __init__(self, gm, extra=False):
+    def __init__(self, gm, extra=False, biased=False):
         self.gm, self.graph = gm, gm.graph
         self.mods = dict(gm.named_modules())
         self.native = set()                 # the windows' nodes: they read either layout
         self.nhwc = set()                   # those of them whose result is channels_last
         self.extra = extra                  # windows='all': the opt-in passes, and their keys in the report
-        self.windows = dict.fromkeys(WINDOW_KINDS + (EXTRA_KINDS if extra else ()), 0)
+        self.biased = biased                # biased=True: the windows of biased convolutions, and their keys in the report
+        self.windows = dict.fromkeys(WINDOW_KINDS + (EXTRA_KINDS if extra else ()) + (BIAS_KINDS if biased else ()), 0)
         self.stock = {}
         self.n = 0
 
@@ -274,6 +341,8 @@ class _Matcher:
 
     def conv_window(self, c):
         conv = self.mod(c, nn.Conv2d)
+        if self.biased and conv.bias is not None:
+            return self.bias_window(c, conv)
         why = conv_refusal(conv)
         users = list(c.users)
         if why is None and len(users) != 1:
@@ -359,6 +428,86 @@ class _Matcher:
         if ok:
             self.put(NativeHead(fc), (self.input_of(gp),), node, (node, fl, gp), 'head', nhwc=False)
 
+    # ---- the opt-in windows of biased convolutions (biased=True) ----
+    def biased_result(self, node):
+        """node is the result of a Conv2d with a bias the kernels take, read by one node only."""
+        conv = self.mod(node, nn.Conv2d) if isinstance(node, torch.fx.Node) else None
+        return conv is not None and conv.bias is not None and conv_refusal(conv, biased=True) is None and len(node.users) == 1
+
+    def bias_window(self, c, conv):
+        """A Conv2d with a bias: with its ReLU, with a skip add and the ReLU behind it (the operand rules of conv_window), or alone."""
+        why = conv_refusal(conv, biased=True)
+        x = self.input_of(c)
+        if why is None and not isinstance(x, torch.fx.Node):
+            why = 'its input is not a node of the graph'
+        if why is not None:
+            self.stock[c.target] = why
+            return
+        nxt = next(iter(c.users)) if len(c.users) == 1 else None
+        if nxt is not None and self.is_relu(nxt) and self.input_of(nxt) is c:
+            self.put(NativeConvBias(conv, True), (x,), nxt, (nxt, c), 'conv_bias_relu')
+            return
+        if nxt is not None and self.is_add(nxt):
+            other = nxt.args[1] if nxt.args[0] is c else nxt.args[0]
+            relu = next(iter(nxt.users)) if len(nxt.users) == 1 else None
+            fuse = relu is not None and self.is_relu(relu) and self.input_of(relu) is nxt and other is not c
+            # both operands are biased convolutions: the first one takes the add and the ReLU
+            if fuse and nxt.args[1] is c and self.biased_result(nxt.args[0]):
+                fuse = False
+            if fuse:
+                self.put(NativeConvBias(conv, True), (x, other), relu, (relu, nxt, c), 'conv_bias_add_relu')
+                return
+        self.put(NativeConvBias(conv, False), (x,), c, (c,), 'conv_bias')
+
+    def mlp_head_window(self, node):
+        """node: a Linear whose input is flatten(x, 1); behind it (ReLU, Dropout, Linear) one to three times, one user each."""
+        first = self.mod(node, nn.Linear)
+        fl = self.input_of(node)
+        if first is None or not isinstance(fl, torch.fx.Node) or len(fl.users) != 1:
+            return
+        if fl.op == 'call_module':
+            m = self.mods.get(fl.target)
+            ok = type(m) is nn.Flatten and m.start_dim == 1 and m.end_dim == -1
+        else:
+            ok = ((fl.op == 'call_function' and fl.target is torch.flatten) or (fl.op == 'call_method' and fl.target == 'flatten')) and \
+                tuple(fl.args[1:]) + tuple(fl.kwargs.values()) == (1,)
+        x = self.input_of(fl) if ok else None
+        if not isinstance(x, torch.fx.Node):
+            return
+        modules, nodes, last = [first], [node, fl], node
+        while len(modules) < 3 * T.HEAD_MAX_LINEAR - 2:
+            trio, at = [], last
+            for cls in (nn.ReLU, nn.Dropout, nn.Linear):
+                nxt = next(iter(at.users)) if len(at.users) == 1 else None
+                if nxt is None or self.mod(nxt, cls) is None or self.input_of(nxt) is not at:
+                    break
+                trio.append(nxt)
+                at = nxt
+            if len(trio) != 3:
+                break
+            modules += [self.mods[n.target] for n in trio]
+            nodes = trio[::-1] + nodes
+            last = trio[-1]
+        if len(modules) >= 4:
+            self.put(NativeMlpHead(modules), (x,), last, tuple(nodes), 'mlp_head', nhwc=False)
+
+    def same_size_pool_window(self, node):
+        x, size = self.input_of(node), None
+        if node.op == 'call_module' and type(self.mods.get(node.target)) is nn.AdaptiveAvgPool2d:
+            stock = self.mods[node.target]
+            size = stock.output_size
+        elif node.op == 'call_function' and node.target is F.adaptive_avg_pool2d:
+            size = node.args[1] if len(node.args) > 1 else node.kwargs.get('output_size')
+            fn, const = node.target, size
+            stock = lambda t: fn(t, const)                                      # noqa: E731
+        if isinstance(size, int):
+            size = (size, size)
+        if not (isinstance(x, torch.fx.Node) and isinstance(size, (tuple, list)) and len(size) == 2 and
+                all(isinstance(v, int) for v in size)) or tuple(size) == (1, 1):
+            return
+        # (the result may be the input itself, channels_last from a native node: a stock reader gets it converted)
+        self.put(NativeSameSizePool(stock, tuple(size)), (x,), node, (node,), 'same_size_pool')
+
     # ---- the opt-in windows (windows='all') ----
     def bn_window(self, b):
         """A BatchNorm2d the conv pass left: with its ReLU when that is its only user, else alone."""
@@ -421,6 +570,13 @@ class _Matcher:
         for node in list(self.graph.nodes):
             if node.op == 'call_module' and node not in self.native:
                 self.head_window(node)
+        if self.biased:
+            for node in list(self.graph.nodes):
+                if node.op == 'call_module' and node not in self.native:
+                    self.mlp_head_window(node)
+            for node in list(self.graph.nodes):
+                if node not in self.native:
+                    self.same_size_pool_window(node)
         # a stock node (the output included) reads a native node's result NCHW-contiguous; the head reads either layout
         for node in list(self.nhwc):
             readers = [u for u in node.users if u not in self.native]
@@ -434,11 +590,12 @@ class _Matcher:
         return NativeReport(traced=True, windows=self.windows, stock_convs=self.stock)
 
 
-def nativize(model, strict=False, windows='resnet'):
+def nativize(model, strict=False, windows='resnet', biased=False):
     """`model` (a torch.nn.Module) with its conv -> norm [-> add] -> ReLU, pooling and head windows on the native nodes: a
     torch.fx.GraphModule over the SAME submodules, Parameters and buffers, with `report()`.  A model torch.fx cannot trace (data-
     dependent control flow) is returned unchanged and the reason logged; strict=True raises instead.  windows='all' adds the
-    opt-in windows of pre-activation and densely connected networks (the module text; EXTRA_KINDS in the report)."""
+    opt-in windows of pre-activation and densely connected networks (the module text; EXTRA_KINDS in the report); biased=True
+    those of convolutions with a bias and of the flatten -> MLP classifier (BIAS_KINDS)."""
     if windows not in ('resnet', 'all'):
         raise ValueError("windows is 'resnet' or 'all', not %r" % (windows,))
     try:
@@ -449,6 +606,6 @@ def nativize(model, strict=False, windows='resnet'):
         log('nativize: %s cannot be traced (%s: %s): it stays on the stock layers'
             % (type(model).__name__, type(e).__name__, str(e).splitlines()[0] if str(e) else ''))
         return model
-    report = _Matcher(gm, extra=windows == 'all').run()
+    report = _Matcher(gm, extra=windows == 'all', biased=bool(biased)).run()
     gm.report = lambda: report
     return gm

@@ -52,7 +52,10 @@ runner ``run_conv_bn_act(conv, bn, x, residual=None)``; ``ghn3_amd.nativize`` (n
 module.  GHN3_NATIVE_ACT=0 keeps them stock.  A BatchNorm2d [-> ReLU] that follows NO convolution (a DenseNet's dense layer, a
 pre-activation residual block) has a node of its own, ``BnAct`` / ``bn_act`` and ``BnActEval`` / ``bn_act_eval`` (ghn3_bn_act_*,
 csrc/tnet_bnact.hip), through ``run_bn_act(bn, x, relu)``; only ``nativize(windows='all')`` asks for it, and GHN3_NATIVE_BNACT=0
-keeps it stock there too.
+keeps it stock there too.  A convolution WITH a bias (``nn.Conv2d``'s default: VGG, AlexNet, SqueezeNet, networks without norm
+layers) runs on the "bias" member, ``ConvBiasAct`` / ``conv_bias_act`` (ghn3_conv_bias_act_*: convolution + bias [+ skip]
+[-> ReLU], nothing saved but x, w and the result), through ``run_conv_bias_act(conv, x, relu, residual=None)``; only
+``nativize(biased=True)`` asks for it, and GHN3_NATIVE_BIAS=0 keeps it stock there too.
 
 ``DwPwBn.applicable`` states what the kernels take (fp32 CUDA tensors, batch statistics, C <= 512, ks <= 7); a layer
 outside of it goes to the two-node form above or keeps the stock path.  There is no CPU implementation: on a CPU tensor the
@@ -772,6 +775,96 @@ def conv_act_reference(x, w, gamma, beta, residual=None, stride=1, padding=0, di
     return F.relu(y if residual is None else y + residual)
 
 
+# ---- the "bias" member of the dense-convolution family: [ReLU ->] convolution + bias [+ skip] [-> ReLU] ------------------------
+# The layers of torch.nn networks WITHOUT norm layers (VGG, AlexNet, SqueezeNet: nn.Conv2d with its default bias=True, then a
+# ReLU), and any other biased convolution.  Opt-in through ghn3_amd.nativize(biased=True); ghn3_conv_bias_act_*.
+CONV_ACT_OUT = 4                  # include/ghn3_hip.h GHN3_CONV_ACT_OUT
+_BIAS_SCRATCH = 'ghn3_conv_bias_act_scratch_floats'   # (desc, backward)
+
+
+def bias_enabled():
+    """GHN3_NATIVE_BIAS=0 keeps every biased-convolution window on the stock layers."""
+    return os.environ.get('GHN3_NATIVE_BIAS', '1') != '0'
+
+
+def _bias_desc(x, w, stride, pad, dil, relu_in, relu):
+    d = _conv_desc(x, w, stride, pad, dil, relu_in, 0.0)
+    if relu:
+        d.relu |= CONV_ACT_OUT
+    return d
+
+
+class ConvBiasAct(torch.autograd.Function):
+    """[ReLU ->] dense kh x kw convolution + bias [+ residual] [-> ReLU] as ONE autograd node on ghn3_conv_bias_act_fwd / _bwd.
+    Conventions of ConvBn.  Saved between the directions: x, w, and -- with the ReLU -- out, which carries its mask."""
+
+    @staticmethod
+    def applicable(x, w, bias, residual=None, stride=1, padding=0, dilation=1):
+        """Every limit of the C side (check_cdesc, the two 2^31 rules included), and what the op asks of the bias and the skip
+        tensor: fp32 CUDA tensors of C_out elements / of the output's shape."""
+        if not (bias_enabled() and _conv_applicable(x, w) and _f32_cuda(bias) and bias.numel() == w.shape[0]):
+            return False
+        (sh, sw), (ph, pw) = _pair(stride), _pair(padding)
+        if min(sh, sw) <= 0 or min(ph, pw) < 0 or int(dilation) <= 0:
+            return False
+        d = _conv_desc(x, w, stride, padding, dilation, False, 0.0)
+        if not conv_desc_fits(d):
+            return False
+        return residual is None or (_f32_cuda(residual) and tuple(residual.shape) == (d.N, d.C_out, d.Ho, d.Wo))
+
+    @staticmethod
+    def forward(ctx, x, w, bias, residual, stride, pad, dil, relu, relu_in, keep):
+        lib = L.load()
+        xc = x.contiguous(memory_format=torch.channels_last)
+        wc, bc = w.contiguous(), bias.contiguous()
+        rc = None if residual is None else residual.contiguous(memory_format=torch.channels_last)
+        d = _bias_desc(xc, wc, stride, pad, dil, relu_in, relu)
+        out = torch.empty((d.N, d.C_out, d.Ho, d.Wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+        scratch = torch.empty(_scratch_floats(_BIAS_SCRATCH, d, 0), dtype=torch.float32, device=x.device)
+        L._check(lib.ghn3_conv_bias_act_fwd(ctypes.byref(d), *_ptrs(xc, wc, bc, rc, out, scratch), _stream()), 'ghn3_conv_bias_act_fwd')
+        if keep:
+            ctx.save_for_backward(xc, wc, *((out,) if relu else ()))
+            ctx.cfg = (stride, pad, dil, relu, relu_in)
+            ctx.has_res = residual is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        """(dx, dw, dbias, dres): tensors of their own, not views of one buffer with the scratch area (`_carve`) -- the
+        parameters of a plain network are leaves, whose .grad would pin it."""
+        lib = L.load()
+        xc, wc, *saved = ctx.saved_tensors
+        stride, pad, dil, relu, relu_in = ctx.cfg
+        out = saved[0] if relu else None
+        d = _bias_desc(xc, wc, stride, pad, dil, relu_in, relu)
+        do = dout.contiguous(memory_format=torch.channels_last)
+        dx, dw = torch.empty_like(xc), torch.empty_like(wc)
+        db = torch.empty(d.C_out, dtype=torch.float32, device=xc.device)
+        dres = torch.empty_like(do) if (ctx.has_res and ctx.needs_input_grad[3]) else None
+        scratch = torch.empty(_scratch_floats(_BIAS_SCRATCH, d, 1), dtype=torch.float32, device=xc.device)
+        L._check(lib.ghn3_conv_bias_act_bwd(ctypes.byref(d), *_ptrs(do, out, xc, wc, dx, dw, db, dres, scratch), _stream()),
+                 'ghn3_conv_bias_act_bwd')
+        return (dx, dw, db, dres) + (None,) * 6
+
+
+def conv_bias_act(x, w, bias, residual=None, stride=1, padding=0, dilation=1, relu=True, relu_in=False):
+    """out = act(conv2d(relu(x) if relu_in else x, w, bias) [+ residual]), act = ReLU when `relu` else the identity.  x: (N, C, H, W)
+    fp32 CUDA tensor (channels_last preferred), w (C_out, C, kh, kw), bias (C_out), residual: a tensor of the output's shape (any
+    layout; channels_last is read as it is) or None.  Under torch.no_grad(), or when no input requires a gradient, nothing is
+    saved."""
+    _needs_gpu('conv_bias_act', x)
+    return ConvBiasAct.apply(x, w, bias, residual, _pair(stride), _pair(padding), int(dilation), bool(relu), bool(relu_in),
+                             _wants_grad(x, w, bias, residual))
+
+
+def conv_bias_act_reference(x, w, bias, residual=None, stride=1, padding=0, dilation=1, relu=True, relu_in=False):
+    """The stock layers ConvBiasAct replaces, functional form -- the parity reference of the tests."""
+    y = F.conv2d(F.relu(x) if relu_in else x, w, bias, stride, padding, dilation)
+    if residual is not None:
+        y = y + residual
+    return F.relu(y) if relu else y
+
+
 # ---- a BatchNorm [-> ReLU] that stands alone: ghn3_bn_act_* (csrc/tnet_bnact.hip) -------------------------------------------------
 # The leading layers of a DenseNet's dense layer and of a pre-activation residual block: no convolution in front of the norm layer.
 # Opt-in through ghn3_amd.nativize(windows='all'); GHN3_NATIVE_BNACT=0 keeps the layers stock even there.
@@ -1317,6 +1410,23 @@ def run_conv_bn_act(conv, bn, x, residual=None):
         out, stats = conv_bn_act(xin, w, g, b, *args, False, slot.eps)
         _update_running_stats(slot, stats, out)
         return out
+    return None
+
+
+def run_conv_bias_act(conv, x, relu, residual=None):
+    """Conv2d WITH a bias [-> + residual] [-> ReLU] of a torch.nn network on ConvBiasAct, 3-channel images as `_image_pad` says;
+    the NHWC result, or None where the node does not apply -- CPU tensors, another dtype, GHN3_NATIVE_OPS=0, GHN3_NATIVE_CONV=0,
+    GHN3_NATIVE_BIAS=0, autocast with GHN3_NATIVE_AMP=0, a grouped, oddly padded or unbiased convolution, a limit of the kernels --
+    and the caller keeps its stock layers."""
+    if not (bias_enabled() and _native_input(x, 'GHN3_NATIVE_CONV') and torch.is_tensor(getattr(conv, 'bias', None)) and
+            hasattr(conv, 'kernel_size') and not isinstance(conv.padding, str) and getattr(conv, 'groups', 1) == 1 and
+            getattr(conv, 'padding_mode', 'zeros') == 'zeros' and torch.is_tensor(getattr(conv, 'weight', None)) and
+            len(set(_pair(getattr(conv, 'dilation', 1)))) == 1):
+        return None
+    xin, w = _image_pad(x, conv.weight)
+    args = (residual, conv.stride, conv.padding, _pair(conv.dilation)[0])
+    if ConvBiasAct.applicable(xin, w, conv.bias, *args):
+        return conv_bias_act(xin, w, conv.bias, *args, relu, False)
     return None
 
 

@@ -110,7 +110,7 @@ class Trainer:
                  device='cuda', log_interval=100, label_smoothing=0, predparam_wd=0, scheduler_args=None, save_dir=None,
                  ckpt=None, epochs=None, verbose=False, amp=False, amp_min_scale=None, amp_growth_interval=2000,
                  grad_compress=None, amp_init_scale=65536.0, bce=False, mixup=False, compile_mode=None, beta=1e-5, native_layers=False,
-                 data_parallel=False, **unused):
+                 data_parallel=False, native_biased=False, **unused):
         from .nn import GHN3
         self._plain = not isinstance(model, GHN3)
         if self._plain:
@@ -183,6 +183,11 @@ class Trainer:
         if native_layers not in (False, True, None, 'all'):
             raise ValueError("native_layers is False, True or 'all', not %r" % (native_layers,))
         self._native_layers = (native_layers or False) if self._plain else False
+        # native_biased (with native_layers only): nativize(biased=True) -- the windows of convolutions WITH a bias and of the
+        # flatten -> MLP classifier (VGG-, AlexNet-, SqueezeNet-shaped networks), a third opt-in
+        if native_biased and not native_layers:
+            raise ValueError('native_biased asks for native_layers (True or \'all\')')
+        self._native_biased = bool(native_biased)
         self._forward_model = None
         self.base_lr = float(opt_args['lr'])
         if self._plain:
@@ -394,7 +399,8 @@ class Trainer:
             return self._model
         if self._forward_model is None:
             from .native_net import nativize
-            self._forward_model = nativize(self._model, windows='all' if self._native_layers == 'all' else 'resnet')
+            self._forward_model = nativize(self._model, windows='all' if self._native_layers == 'all' else 'resnet',
+                                           biased=self._native_biased)
         return self._forward_model
 
     def _update_plain(self, images, targets):

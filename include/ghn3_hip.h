@@ -687,6 +687,35 @@ int ghn3_conv_frozen_act_bwd(const ghn3_conv_desc* desc, const float* dout, cons
                              const float* w, const float* gamma, const float* mean, const float* var, float* dx, float* dw,
                              float* dgamma, float* dbeta, float* dres, float* scratch, void* stream);
 
+/* The "bias" member of the family: the layers of plain networks WITHOUT norm layers (VGG, AlexNet, SqueezeNet: nn.Conv2d with its
+ * default bias=True, then a ReLU),
+ *   out = act(conv(relu(x) if desc->relu & 1 else x, w) + bias[c] [+ res]),  act = ReLU with GHN3_CONV_ACT_OUT in desc->relu,
+ *                                                                            the identity without it.
+ * Same descriptor, limits, error codes, NHWC fp32 conventions and in-place weight views as ghn3_conv_bn_fwd / _bwd (the two 2^31
+ * rules included); GHN3_CONV_NO_NORM in desc->relu is GHN3_E_ARG.  Added without an ABI version step: symbols plus the flag
+ * GHN3_CONV_ACT_OUT, a bit of desc->relu every other entry point ignores (they read bit 1 and GHN3_CONV_NO_NORM, as before).
+ * bias [C_out]; res [N Ho Wo][C_out] is the skip tensor, NULL for none.  No pre-activation tensor is stored: with the ReLU, out
+ * (alive anyway as the next layer's input) carries the mask 1[out > 0] -- torch's rule -- and the backward reads it; without the
+ * ReLU `out` may be NULL in the backward.  dres [N Ho Wo][C_out] = the masked gradient, NULL: not wanted; it must be NULL when
+ * the forward had no res.
+ * Forward: 2 launches (weight pack + the convolution with bias, skip and clamp in its epilogue); only `out` is written, no
+ * statistics pass runs.
+ * Backward: 6 launches, two more than the convolution alone (GHN3_CONV_NO_NORM: 4) -- one pass per 64-pixel tile forms
+ * g = dout 1[out > 0] (g = dout without the ReLU), writes it to scratch and to dres where wanted and leaves the tile's column
+ * sums; a fixed-order reduction of those gives dbias; then weight pack, dx, dW and its reduction unchanged.  Without the ReLU
+ * dout itself is the operand of dx and dW and is not copied (only the column sums run, and the write of dres when wanted).
+ * `scratch` = ghn3_conv_bias_act_scratch_floats(desc, backward) floats, in the terms of ghn3_conv_scratch_floats:
+ *   forward   pack(C_out, C_in) + 64
+ *   backward  what ghn3_conv_scratch_floats(desc, 1) answers (the column sums take tiles C_out of its first area)
+ * (a negative GHN3_E_* code for a descriptor the op does not take).  No float atomics, no allocation, no synchronisation
+ * inside.  Deterministic (fixed-order partial sums): reruns are bit-identical. */
+#define GHN3_CONV_ACT_OUT 4
+int64_t ghn3_conv_bias_act_scratch_floats(const ghn3_conv_desc* desc, int backward);  /* < 0: bad descriptor (ghn3_last_error) */
+int ghn3_conv_bias_act_fwd(const ghn3_conv_desc* desc, const float* x, const float* w, const float* bias, const float* res,
+                           float* out, float* scratch, void* stream);
+int ghn3_conv_bias_act_bwd(const ghn3_conv_desc* desc, const float* dout, const float* out, const float* x, const float* w,
+                           float* dx, float* dw, float* dbias, float* dres, float* scratch, void* stream);
+
 /* The patch embedding of the ImageNet-sized ViT-style networks (`conv_stride`: Conv2d(3, C, 16, stride = 16) on 224 x 224
  * images) -- a bias-free, ungrouped convolution without padding or dilation whose windows do not overlap, which is a plain GEMM
  * over a permutation of the image (ghn3_amd/csrc/tnet_patch.hip):
