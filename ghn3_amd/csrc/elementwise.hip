@@ -1591,6 +1591,53 @@ int ghn3_add(float* dst, const float* src, int64_t n, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// Ranged zero-fill: what ghn3_run issues for a run of consecutive GHN3_OP_MEMSET0 ops -- one launch instead of one
+// hipMemsetAsync (a ~5 us dependent launch) each.  A work block is one kFillChunk-byte piece of a range, cut on the 16-byte
+// grid of the address space; the block finds its range by binary search over the ascending first-block numbers and every
+// lane writes 16 bytes per step.  Only the first and the last 16-byte slot of a range can be partial: dword stores where a
+// whole dword lies inside [p, p + bytes), byte stores for the rest.  Nothing outside the range is written.
+// ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void fill_ranges_kernel(const FillRangeDev* __restrict__ R, int n) {
+    const unsigned b = blockIdx.x;
+    int lo = 0, hi = n - 1;                              // the last range with block0 <= b
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (R[mid].block0 <= b) lo = mid; else hi = mid - 1;
+    }
+    const uintptr_t beg = reinterpret_cast<uintptr_t>(R[lo].p), end = beg + R[lo].bytes;
+    const uintptr_t c0 = (beg & ~(uintptr_t)15) + (uintptr_t)(b - R[lo].block0) * kFillChunk;
+    const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+    if (c0 >= beg && c0 + kFillChunk <= end) {           // a block inside the range: no checks
+#pragma unroll
+        for (int it = 0; it < kFillChunk / 4096; ++it)
+            *reinterpret_cast<uint4*>(c0 + ((uintptr_t)it * 256 + threadIdx.x) * 16) = z;
+        return;
+    }
+    for (int it = 0; it < kFillChunk / 4096; ++it) {
+        const uintptr_t a = c0 + ((uintptr_t)it * 256 + threadIdx.x) * 16;
+        if (a >= end) break;
+        if (a >= beg && a + 16 <= end) {
+            *reinterpret_cast<uint4*>(a) = z;
+            continue;
+        }
+        for (int d = 0; d < 4; ++d) {                    // the range's first or last slot
+            const uintptr_t w = a + 4 * d;
+            if (w >= beg && w + 4 <= end) {
+                *reinterpret_cast<unsigned*>(w) = 0u;
+            } else {
+                for (int e = 0; e < 4; ++e)
+                    if (w + e >= beg && w + e < end) *reinterpret_cast<unsigned char*>(w + e) = 0;
+            }
+        }
+    }
+}
+int ghn3_fill_ranges(const FillRangeDev* d_ranges, int n_ranges, unsigned total_blocks, hipStream_t s) {
+    if (n_ranges <= 0 || total_blocks == 0) return GHN3_OK;
+    hipLaunchKernelGGL(fill_ranges_kernel, dim3(total_blocks), dim3(256), 0, s, d_ranges, n_ranges);
+    return launch_ok("fill_ranges");
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // GHN3_OP_WIRE_PACK / GHN3_OP_RANK_REDUCE: the local passes of the mesh gradient exchange (ddp_utils.mesh_all_reduce_avg).
 // HBM streaming kernels: 16-byte accesses, grid-stride, bf16 round-to-nearest-even.
 // ---------------------------------------------------------------------------------------------------------------

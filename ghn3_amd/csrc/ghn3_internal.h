@@ -115,6 +115,11 @@ int ghn3_colsum(float* out, const float* X, int M, int N, int ld, int q, int sdi
 int ghn3_rowseg_sum(float* out, const float* X, const int* seg_ptr, const int* idx, int rows, int C, int ldx,
                     int ldo, int accum, hipStream_t s);
 int ghn3_add(float* dst, const float* src, int64_t n, hipStream_t s);
+// Ranged zero-fill (a run of GHN3_OP_MEMSET0 ops in one launch).  Table entry: bytes [p, p + bytes); the range owns the work
+// blocks [block0, block0 of the next entry), one per kFillChunk bytes of its span on the 16-byte grid.  d_ranges is device memory.
+struct FillRangeDev { char* p; uint64_t bytes; uint32_t block0; uint32_t pad_; };
+static const int kFillChunk = 65536;
+int ghn3_fill_ranges(const FillRangeDev* d_ranges, int n_ranges, unsigned total_blocks, hipStream_t s);
 int ghn3_transpose32(float* dst, const float* src, int rows, int cols, int ld_src, int ld_dst, int batch, int64_t sb, int64_t db,
                      hipStream_t s);
 int ghn3_wire_pack(void* dst, const void* src, int64_t n, int64_t n_pad, int reverse, hipStream_t s);

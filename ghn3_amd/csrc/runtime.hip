@@ -35,6 +35,12 @@ static const int kStageSlots = 16;
 
 struct Launch { int a_mode, b_mode, tile, first, count, tiles, with_ln, max_slice; };
 
+// A run of consecutive GHN3_OP_MEMSET0 ops bound for the same stream (ops [op0, op1)), resolved: nothing to do, one range
+// (hipMemsetAsync, as for an isolated op) or ranged-fill launches over entries [first, first + count) of the slot's range table.
+static const int kFillCap = 128;                         // ranges per launch (a longer run is split, never truncated)
+struct FillLaunch { int first, count; unsigned blocks; };
+struct FillRun { int op0, op1; void* p; size_t bytes; std::vector<FillLaunch> launches; };
+
 // What a staging slot's table was resolved from (copies of the caller's arrays) and the launch groups that came out: a run with
 // the same ops, problems and buffer pointers -- every step of a training loop once the allocator has settled -- reuses the
 // table already on the device: no host resolve (hundreds of problems, ~0.3 ms at ghn3xlm16) and no 100 KB upload in front
@@ -47,6 +53,7 @@ struct SlotCache {
     std::vector<ghn3_gemm_problem> problems;
     std::vector<void*> bufs;
     std::vector<std::vector<Launch>> launches;
+    std::vector<FillRun> fills;        // ascending op0
     hipStream_t up_stream = nullptr;   // the stream the table was uploaded on
 };
 
@@ -277,6 +284,22 @@ extern "C" int ghn3_run(ghn3_ctx* c, const ghn3_op* ops, int n_ops, const ghn3_g
     size_t need = 0;
     for (int k = 0; k < n_ops; ++k)
         if (ops[k].kind == GHN3_OP_GEMM) need += (size_t)ops[k].i[1];
+    // Runs of two or more consecutive MEMSET0 ops with the same main / side flag become ranged-fill launches; their range
+    // table lies behind the problem table of the same staging slot (so a replayed run finds it on the device as well).
+    std::vector<FillRun> fresh_fills;
+    const std::vector<FillRun>* fills = &fresh_fills;
+    const size_t need_probs = need;
+    size_t fill_ops = 0;
+    for (int k = 0; k < n_ops;) {
+        int e = k + 1;
+        if (ops[k].kind == GHN3_OP_MEMSET0) {
+            while (e < n_ops && ops[e].kind == GHN3_OP_MEMSET0 &&
+                   ((ops[e].flags ^ ops[k].flags) & GHN3_OPFLAG_SIDE) == 0) ++e;
+            if (e - k >= 2) { fresh_fills.push_back(FillRun{k, e, nullptr, 0, {}}); fill_ops += (size_t)(e - k); }
+        }
+        k = e;
+    }
+    need += (fill_ops * sizeof(FillRangeDev) + sizeof(GemmProbDev) - 1) / sizeof(GemmProbDev);
     GemmProbDev* hs = nullptr; GemmProbDev* ds = nullptr;
     static const bool use_cache = !(getenv("GHN3_RUN_CACHE") && atoi(getenv("GHN3_RUN_CACHE")) == 0);
     int hit = -1;
@@ -287,9 +310,9 @@ extern "C" int ghn3_run(ghn3_ctx* c, const ghn3_op* ops, int n_ops, const ghn3_g
         for (int i = 0; use_cache && i < kStageSlots && hit < 0; ++i) {
             const SlotCache& e = c->cache[i];
             if (e.valid && e.n_ops == n_ops && e.n_problems == n_problems && e.n_bufs == n_bufs &&
-                memcmp(e.bufs.data(), bufs, (size_t)n_bufs * sizeof(void*)) == 0 &&
+                (n_bufs == 0 || memcmp(e.bufs.data(), bufs, (size_t)n_bufs * sizeof(void*)) == 0) &&
                 memcmp(e.ops.data(), ops, (size_t)n_ops * sizeof(ghn3_op)) == 0 &&
-                memcmp(e.problems.data(), problems, (size_t)n_problems * sizeof(ghn3_gemm_problem)) == 0)
+                (n_problems == 0 || memcmp(e.problems.data(), problems, (size_t)n_problems * sizeof(ghn3_gemm_problem)) == 0))
                 hit = i;
         }
     }
@@ -300,6 +323,7 @@ extern "C" int ghn3_run(ghn3_ctx* c, const ghn3_op* ops, int n_ops, const ghn3_g
         c->cache_hits++;
         hs = c->h_stage[hit]; ds = c->d_stage[hit];
         launches = &e.launches;
+        fills = &e.fills;
         if (e.up_stream != stream && c->ev_used[hit]) HIPCHK(hipStreamWaitEvent(stream, c->ev[hit], 0));
     } else if (need > 0) {
         int slot = 0;                                    // the least recently used slot (never used ones first)
@@ -553,9 +577,41 @@ extern "C" int ghn3_run(ghn3_ctx* c, const ghn3_op* ops, int n_ops, const ghn3_g
                     }
         }
         if (R.bad) { ghn3_set_error("ghn3_run: a GEMM problem references an absent buffer"); return GHN3_E_ARG; }
+        // the fill runs: resolve, drop absent / empty ops, merge ranges that touch or overlap, cut into launches
+        FillRangeDev* const hf = reinterpret_cast<FillRangeDev*>(hs + need_probs);
+        size_t fpos = 0;
+        for (FillRun& run : fresh_fills) {
+            std::vector<std::pair<uintptr_t, uintptr_t>> rg;     // [begin, end)
+            for (int k = run.op0; k < run.op1; ++k) {
+                char* p = R.get<char>(ops[k].r[0]);
+                if (R.bad) { ghn3_set_error("op %d (kind %d): reference to an absent buffer", k, ops[k].kind); return GHN3_E_ARG; }
+                if (p && ops[k].i[0] > 0)
+                    rg.push_back({reinterpret_cast<uintptr_t>(p), reinterpret_cast<uintptr_t>(p) + (uintptr_t)ops[k].i[0]});
+            }
+            std::sort(rg.begin(), rg.end());
+            size_t n = 0;
+            for (size_t j = 0; j < rg.size(); ++j) {
+                if (n && rg[j].first <= rg[n - 1].second) rg[n - 1].second = std::max(rg[n - 1].second, rg[j].second);
+                else rg[n++] = rg[j];
+            }
+            rg.resize(n);
+            if (n == 1) { run.p = reinterpret_cast<void*>(rg[0].first); run.bytes = (size_t)(rg[0].second - rg[0].first); }
+            for (size_t j = 0; n >= 2 && j < n; ++j) {
+                const uint64_t nb = (uint64_t)((rg[j].second - (rg[j].first & ~(uintptr_t)15) + kFillChunk - 1) / kFillChunk);
+                if (nb >= ((uint64_t)1 << 31)) { ghn3_set_error("MEMSET0 run at op %d: a range of 2^47 bytes or more", run.op0); return GHN3_E_LIMIT; }
+                if (run.launches.empty() || run.launches.back().count == kFillCap ||
+                    (uint64_t)run.launches.back().blocks + nb >= ((uint64_t)1 << 31))
+                    run.launches.push_back(FillLaunch{(int)fpos, 0, 0u});
+                FillLaunch& fl = run.launches.back();
+                hf[fpos++] = FillRangeDev{reinterpret_cast<char*>(rg[j].first), (uint64_t)(rg[j].second - rg[j].first), fl.blocks, 0u};
+                fl.blocks += (unsigned)nb;
+                fl.count++;
+            }
+        }
         // Upload in `stream` itself: the host runs far enough ahead that the copy is never waited for, and a run that repeats
         // finds its table on the device (SlotCache), so a separate copy stream gains nothing (docs/EXPERIMENTS.md, round 6).
-        HIPCHK(hipMemcpyAsync(ds, hs, pos * sizeof(GemmProbDev), hipMemcpyHostToDevice, stream));
+        const size_t up_bytes = fpos ? need_probs * sizeof(GemmProbDev) + fpos * sizeof(FillRangeDev) : pos * sizeof(GemmProbDev);
+        if (up_bytes) HIPCHK(hipMemcpyAsync(ds, hs, up_bytes, hipMemcpyHostToDevice, stream));
         HIPCHK(hipEventRecord(c->ev[slot], stream));
         c->ev_used[slot] = true;
         if (use_cache) {
@@ -566,6 +622,8 @@ extern "C" int ghn3_run(ghn3_ctx* c, const ghn3_op* ops, int n_ops, const ghn3_g
             e.bufs.assign(bufs, bufs + n_bufs);
             e.launches.swap(fresh_launches);
             launches = &e.launches;
+            e.fills.swap(fresh_fills);
+            fills = &e.fills;
             e.up_stream = stream;
             e.stamp = ++c->clock;
             e.valid = true;
@@ -599,9 +657,11 @@ extern "C" int ghn3_run(ghn3_ctx* c, const ghn3_op* ops, int n_ops, const ghn3_g
         for (int i = 0; i < 4; ++i) mark_set[i] = false;    // everything marked so far has been waited for
         return GHN3_OK;
     };
+    size_t next_fill = 0;                                // the first fill run that starts at or behind op k
     for (int k = 0; k < n_ops; ++k) {
         const ghn3_op& o = ops[k];
         int rc = GHN3_OK;
+        int n_merged = 1;                                // ops this iteration stands for (a fill run: all of its ops)
         R.bad = false;
         const bool on_side = (o.flags & GHN3_OPFLAG_SIDE) && c->side_enabled && c->profile != 1 && c->profile != 3;
         // A grid cap of a side-stream GEMM only exists to leave CUs to the chain it runs beside: serialised (no side stream,
@@ -806,6 +866,19 @@ extern "C" int ghn3_run(ghn3_ctx* c, const ghn3_op* ops, int n_ops, const ghn3_g
                                  (int)o.i[4], stream);
             break;
         case GHN3_OP_MEMSET0: {
+            while (next_fill < fills->size() && (*fills)[next_fill].op1 <= k) ++next_fill;
+            if (next_fill < fills->size() && (*fills)[next_fill].op0 == k) {
+                // a run of fills, resolved with the run's tables: one launch (per kFillCap ranges) for all of its ops
+                const FillRun& run = (*fills)[next_fill];
+                const FillRangeDev* const df = reinterpret_cast<const FillRangeDev*>(ds + need_probs);
+                if (run.bytes) HIPCHK(hipMemsetAsync(run.p, 0, run.bytes, stream));
+                for (const FillLaunch& fl : run.launches) {
+                    rc = ghn3_fill_ranges(df + fl.first, fl.count, fl.blocks, stream);
+                    if (rc) break;
+                }
+                n_merged = run.op1 - run.op0;
+                break;
+            }
             void* p = R.get<void>(o.r[0]);
             if (p && o.i[0] > 0) HIPCHK(hipMemsetAsync(p, 0, (size_t)o.i[0], stream));
             break;
@@ -895,8 +968,9 @@ extern "C" int ghn3_run(ghn3_ctx* c, const ghn3_op* ops, int n_ops, const ghn3_g
             float ms = 0.f;
             HIPCHK(hipEventElapsedTime(&ms, c->pe0, c->pe1));
             c->ms[o.kind] += ms;
-            c->launches[o.kind] += 1;
+            c->launches[o.kind] += n_merged;
         }
+        k += n_merged - 1;
     }
     if (detach && side_dirty) {                          // joined by the next run / ghn3_ctx_side_wait
         c->side_pending = true;

@@ -487,7 +487,16 @@ class GHN3(nn.Module):
                     index_mode=self.index_mode, layernorm=self.layernorm, weight_norm=self.weight_norm,
                     decoder_ctype=L.COMPUTE_TYPES[self.compute],
                     decoder_bwd_ctype=L.COMPUTE_TYPES[self.compute_bwd] if self.compute_bwd else None,
-                    direct16=self.direct16, side_stream=self.side_stream, graphormer_x3=self.graphormer_x3)
+                    direct16=self.direct16, side_stream=self.side_stream, graphormer_x3=self.graphormer_x3,
+                    grad_layout=self._grad_layout())
+
+    def _grad_layout(self):
+        """Program(grad_layout=...): the flat gradient buffer's layout -- with it the backward overwrites single-writer weight
+        gradients, fills only the rest and does so in one launch (GHN3_GRAD_OVERWRITE=0: the program without)."""
+        if os.environ.get('GHN3_GRAD_OVERWRITE', '1') == '0':
+            return None
+        return (tuple(int(v) for v in self._offs) + (int(self._flat_numel),),
+                tuple(int(self._split_sizes[2 * k]) for k in range(len(self._offs))))
 
     def _fill_bufs(self, plan, out=None, dout=None, gflat=None):
         prog = plan.program
@@ -545,7 +554,7 @@ class GHN3(nn.Module):
             raise L.Ghn3Error('this plan was compiled without a backward program (training=False)')
         if dout is None and norm_g is None:
             raise L.Ghn3Error('backward without an upstream gradient')
-        gflat = torch.empty(self._flat_numel, dtype=torch.float32, device=self.device)
+        gflat = self._new_grad_buffer()
         # (the direct 16-bit tile route -- the fused norm term alone, and compiled in: not with GHN3_TILE_D16=0 / bf16 backward
         # operands -- never reads the fp32 tile gradient; every other route does)
         direct = dout is None and norm_g is not None and bool(prog.tile_bwd_h16)
@@ -602,12 +611,23 @@ class GHN3(nn.Module):
         pieces = gflat.split_with_sizes(self._split_sizes)
         return [pieces[2 * k].view(p.shape) for k, p in enumerate(self._slot_params())]
 
+    def _new_grad_buffer(self):
+        """The flat gradient buffer of one backward, uninitialised: the backward program zeroes or overwrites every byte."""
+        return torch.empty(self._flat_numel, dtype=torch.float32, device=self.device)
+
     def _patch_grad_memsets(self, prog):
         """Zero the flat gradient buffer except tensors the backward program fully overwrites."""
         k = prog.memset_grad_op
         total = 4 * self._flat_numel
         ops = prog.bwd_ops
-        if prog.grad_no_memset:
+        if getattr(prog, 'grad_fill_patch', None) is not None:
+            # (compiled against the buffer's layout: the two patched fills are the spans on either side of W2 up to the
+            # neighbouring overwritten tensors, the program's own fills cover the rest)
+            if prog.grad_layout[0][-1] != self._flat_numel or len(prog.grad_layout[1]) != len(self._offs):
+                raise L.Ghn3Error('the program was compiled for another gradient-buffer layout')
+            for j, (off, n) in enumerate(prog.grad_fill_patch):
+                ops[k + j]['r'][0]['off'], ops[k + j]['i'][0] = off, n
+        elif prog.grad_no_memset:
             name = prog.grad_no_memset[0]
             slot = prog.slot[name]
             beg = 4 * int(self._offs[slot])

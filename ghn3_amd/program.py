@@ -56,6 +56,7 @@ class _Backward:
     """What one stage of Program._build_backward hands to a later one (and, at the end, to the scheduling): one object per
     build, never kept on the program.  A stage that reads a field no earlier stage has set fails with an AttributeError."""
     __slots__ = ('sw',                                   # the switches (Program._backward_switches)
+                 'head_fills',                           # grad_layout: (ref, bytes) of the zero-fills deferred to the head
                  'd_rows',                               # gradient of the gathered node rows [M + n1][C]
                  'scaled', 'amax_t', 'amax_u',           # f16 gradient copies: scaled?  running-max refs of d_tiles / d_u
                  't', 'u', 'd_t', 'd_u',                 # decoder activations of the forward and their gradients
@@ -72,6 +73,7 @@ class _Backward:
     def __init__(self, sw):
         self.sw = sw
         self.g16, self.bands, self.d16_on, self.d16_off, self.late_ops = [], [], [], [], []
+        self.head_fills = []
         self.i_dgrad = self.i_late0 = self.i_late1 = self.d_up = None
 
 
@@ -142,8 +144,18 @@ class Program:
 
     def __init__(self, cfg, node_infos, n_nodes, node_types, max_edge, nets, index_mode='reference',
                  training=True, predict_class_layers=True, reduce_graph=False, layernorm=True, weight_norm=True,
-                 decoder_ctype=None, decoder_bwd_ctype=None, direct16=True, side_stream=True, graphormer_x3=None):
+                 decoder_ctype=None, decoder_bwd_ctype=None, direct16=True, side_stream=True, graphormer_x3=None,
+                 grad_layout=None):
         self.cfg = cfg
+        # grad_layout = (offsets, element counts) of every parameter slot in the GHN's flat gradient buffer (floats; offsets
+        # carry the buffer's length as a last entry): GHN3.program_config() passes it unless GHN3_GRAD_OVERWRITE=0.  With it a
+        # training program (1) lets a weight gradient that ONE GEMM problem writes completely overwrite instead of accumulate
+        # and leaves that tensor out of the zero-fill, and (2) issues every zero-fill of the backward at its head, where the
+        # runtime turns the run of MEMSET0 ops into one launch.  None: every problem accumulates, the fill covers everything
+        # except W2 and the workspace fills stand where their regions are allocated.
+        self.grad_layout = None
+        if grad_layout is not None:
+            self.grad_layout = (tuple(int(v) for v in grad_layout[0]), tuple(int(v) for v in grad_layout[1]))
         # side_stream: weight-gradient GEMMs, LayerNorm parameter gradients and operand copies (everything off the
         # dependent chain of the program) carry GHN3_OPFLAG_SIDE and overlap with the chain on a second stream;
         # the temporaries they read are then per-layer buffers instead of reused ones.
@@ -241,6 +253,7 @@ class Program:
         self.dgrad_sub = None
         self.grad_sumsq = None                  # set when the W2 weight gradient leaves its own sum of squares
         self.grad_no_memset = []                # parameters whose gradient the backward fully overwrites
+        self.grad_fill_patch = None             # grad_layout: ((offset, bytes), (offset, bytes)) of the two patched gradient fills
         self.decoder_slots = None               # (training programs only: `is not None` = "this is a training program")
         self.bwd_ops_a = self.bwd_ops_b = None
         self.bwd_parts, self.ddp_index, self.ddp_wgrad_first = (), {}, False
@@ -1840,7 +1853,99 @@ class Program:
         g_xl = self._bwd_final_layernorm(bb, g_xe)
         g_x0 = self._bwd_graphormer(bb, g_xl)
         self._bwd_embed_and_edge_bias(bb, g_x0)
+        if self.grad_layout is not None:
+            self._bwd_head_fills(bb)
         return bb
+
+    def _zero_fill(self, bb, ref, nbytes):
+        """Zero-fill of a workspace region that this stage has just allocated and that nothing in front of this program point
+        writes (the regions are bump-allocated and not reused): where it stands, or -- grad_layout -- at the head of the backward
+        with every other fill (_bwd_head_fills)."""
+        if self.grad_layout is not None:
+            bb.head_fills.append((ref, int(nbytes)))
+        else:
+            self.op(L.OP_MEMSET0, refs=(ref,), ints=(nbytes,))
+
+    def _grad_overwrites(self):
+        """Weight gradients with exactly ONE writer that covers them: a GEMM problem without row gather or row map of C whose
+        M x N is the whole tensor, and no other problem or op that refers to the gradient slot.  The problem loses
+        GHN3_GEMM_ACCUM (it no longer reads the zeros back as its C operand) and the tensor joins grad_no_memset.  A rule over
+        what the build emitted, not a list of names: a weight with one problem per graph, per position or per column half
+        (class-layer predictor at B > 1, decoder.fc, proj_e.0) keeps accumulating into the fill."""
+        P = self.P
+        offs, numels = self.grad_layout
+        nr = len(self._PROBLEM_REFS)
+        col = {n: nr + k for k, n in enumerate(self._PROBLEM_INTS)}
+        i_ksplit = nr + len(self._PROBLEM_INTS) + 1
+        i_c, i_cg = self._PROBLEM_REFS.index('C'), self._PROBLEM_REFS.index('c_gather')
+        writers, other = {}, set()
+        for q in range(self.n_fwd_problems, len(self._probs)):
+            pr = self._probs[q]
+            for j in range(nr):
+                if P <= pr[j][0] < 2 * P:
+                    if j == i_c:
+                        writers.setdefault(pr[j][0] - P, []).append(q)
+                    else:
+                        other.add(pr[j][0] - P)
+        for (_, _, _, _, refs) in self._ops:
+            other.update(b_ - P for b_, _ in refs if P <= b_ < 2 * P)
+        for slot in sorted(writers):
+            name = self.names[slot]
+            if slot in other or len(writers[slot]) != 1 or name in self.grad_no_memset:
+                continue
+            q = writers[slot][0]
+            pr = self._probs[q]
+            M, N = pr[col['M']], pr[col['N']]
+            plain = pr[i_cg][0] < 0 and pr[i_c][1] == 0 and pr[col['ldc']] == N and pr[i_ksplit] <= 1 and \
+                (pr[col['c_q']] == 0 or pr[col['c_q']] == pr[col['c_s']])
+            if plain and M * N == numels[slot] and pr[col['flags']] & L.GEMM_ACCUM:
+                self._probs[q] = pr[:col['flags']] + (pr[col['flags']] & ~L.GEMM_ACCUM,) + pr[col['flags'] + 1:]
+                self.grad_no_memset.append(name)
+
+    def _bwd_head_fills(self, bb):
+        """grad_layout: the compile-time zero-fills of the backward, inserted right behind the two patched gradient fills: the
+        flat gradient buffer except the tensors of grad_no_memset, then the deferred workspace fills.  The fills cover the
+        complement of the overwritten tensors exactly -- alignment gaps included, FusedAdamW and the gradient norm walk them --
+        and no byte of an overwritten tensor.  The two patched fills keep the spans on either side of W2 (grad_fill_patch, what
+        GHN3._patch_grad_memsets writes into them); the rest are MEMSET0 ops from the end of an overwritten tensor (or the
+        start of the buffer) to the start of the next one."""
+        self._grad_overwrites()
+        offs, numels = self.grad_layout
+        assert len(offs) == self.P + 1 and len(numels) == self.P
+        skip = sorted(self.slot[n] for n in self.grad_no_memset)
+        spans, at, at_ref = [], 0, (self.xbuf(self.X_GRADFLAT), 0)        # (begin, end) in floats, ref of begin
+        for s_ in skip:
+            spans.append((at, offs[s_], at_ref))
+            at, at_ref = offs[s_] + numels[s_], self.gref(self.names[s_], numels[s_])
+        spans.append((at, offs[-1], at_ref))
+        w2 = self.slot['decoder.conv.2.weight']
+        patch = [(0, 0), (0, 0)]
+        fills = []
+        for lo, hi, ref in spans:
+            if hi <= lo:
+                continue
+            if w2 in skip and hi == offs[w2]:
+                patch[0] = (4 * lo, 4 * (hi - lo))
+            elif w2 in skip and lo == offs[w2] + numels[w2]:
+                patch[1] = (4 * lo, 4 * (hi - lo))
+            elif w2 not in skip and patch[0] == (0, 0):
+                patch[0] = (4 * lo, 4 * (hi - lo))
+            else:
+                fills.append((ref, 4 * (hi - lo)))
+        self.grad_fill_patch = tuple(patch)
+        fills += bb.head_fills
+        k = self.memset_grad_op + 2
+        self._ops[k:k] = [(L.OP_MEMSET0, 0, (n,), (), (ref,)) for ref, n in fills]
+        n = len(fills)
+        # (every op index recorded during the build lies behind the insertion point)
+        self.tile_bwd_op = None if self.tile_bwd_op is None else self.tile_bwd_op + n
+        for name in ('i_dgrad', 'i_late0', 'i_late1'):
+            if getattr(bb, name) is not None:
+                setattr(bb, name, getattr(bb, name) + n)
+        if self.wgrad_op_range is not None:
+            self.wgrad_op_range = (self.wgrad_op_range[0] + n, self.wgrad_op_range[1] + n)
+        self.bwd_cut_w2 = max(self.bwd_cut_w2, k) + n            # (data-parallel parts: the fills live in part 1)
+        self.bwd_split += n
 
     def _bwd_memsets_and_tile(self, bb):
         """Gradient memsets, the workspace zero-fills of this program point and the tile backward."""
@@ -1888,7 +1993,7 @@ class Program:
                 run[2] = off + n - run[1]                   # (the gap: slack / padding of the previous region)
                 continue
             if run is not None:
-                self.op(L.OP_MEMSET0, refs=((run[0], run[1]),), ints=(run[2],))
+                self._zero_fill(bb, (run[0], run[1]), run[2])
             run = [buf, off, n]
         if self.n_desc:
             grads = self._tile_sources(True)
@@ -1961,7 +2066,9 @@ class Program:
             if g['kind'] != 'cls':
                 continue
             # the head dgrad writes columns i' < i only; the pad columns (i <= i' < i_ld) must read as zero
-            self.op(L.OP_MEMSET0, refs=(self.wref('d_tiles', g['tile_off']),), ints=(4 * g['rows'] * g['ld'],))
+            # (nothing else writes these rows -- the tile backward has no descriptor in a classifier family, the resized kernels
+            # are convolutions -- so at the head of the backward the fill does the same)
+            self._zero_fill(bb, self.wref('d_tiles', g['tile_off']), 4 * g['rows'] * g['ld'])
             p0 = len(self._probs)
             for n_idx in range(len(g['inds'])):
                 tile_n = self.wref('tiles', g['tile_off'] + n_idx * g['ld'])
@@ -2295,7 +2402,7 @@ class Program:
                         tm, tn = ((o_hi - o_lo) * b_['bw'] + 255) // 256, (8 * C + wg_tn - 1) // wg_tn
                         sq_ids += tm * tn + 8 * (tm + tn + 1)
                 sq_ref = self.wsf('dw2_sq', 8 * sq_ids)
-                self.op(L.OP_MEMSET0, refs=(sq_ref,), ints=(4 * 8 * sq_ids,))
+                self._zero_fill(bb, sq_ref, 4 * 8 * sq_ids)
                 self.grad_sumsq = dict(name=W2, ws_off=sq_ref[1], count=8 * sq_ids)
             for b_ in bands:
                 mem = b_['members']
@@ -2449,7 +2556,7 @@ class Program:
         bb.dBias = self.wsf('dBias', nb_ // 4 + 2 * V * V * H + 16)
         bb.hist = (bb.dBias[0], bb.dBias[1] + nb_)
         bb.hist_amax = (bb.dBias[0], bb.dBias[1] + nb_ + 8 * V * V * H)
-        self.op(L.OP_MEMSET0, refs=(bb.dBias,), ints=(nb_ + 8 * V * V * H + 16,))
+        self._zero_fill(bb, bb.dBias, nb_ + 8 * V * V * H + 16)
         if not self.layernorm:
             return d_xe
         xL = self.wref('x%d' % self.Lyr)
@@ -2596,7 +2703,7 @@ class Program:
         dhid = self.wsf('dhid', V * V * C)
         dPfw, dPbw = self.wsf('dPfw', V * C), self.wsf('dPbw', V * C)
         hid = self.wref('hid')
-        self.op(L.OP_MEMSET0, refs=(dT,), ints=(4 * V * V * ldT,))
+        self._zero_fill(bb, dT, 4 * V * V * ldT)
         self.op(L.OP_BIAS_HIST, refs=(dT, bb.dBias, pair, bb.hist), ints=(B, N, H, V, 1))
         p0 = self.gemm(dT, hid, self.gref(W2e), H, C, V * V, ldT, C, C, a_mode=L.MODE_COL, b_mode=L.MODE_COL,
                        accum=True, dbias=self.gref(b2e))
