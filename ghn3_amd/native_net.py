@@ -7,16 +7,17 @@ The native ops of ``ghn3_amd.target_ops`` are called from the block classes of `
 with ``torch.fx`` and replaces these windows of the graph by calls of the runners:
 
     window                                               runner                                   report key
-    Conv2d -> BatchNorm2d -> ReLU                        target_ops.run_conv_bn_act               'conv_bn_relu'
-    Conv2d -> BatchNorm2d -> add(., r) -> ReLU           target_ops.run_conv_bn_act(residual=r)   'conv_bn_add_relu'
-    Conv2d -> BatchNorm2d -> add (the other operand;     target_ops._conv_dispatch(relu=False)    'conv_bn'
+    Conv2d -> BatchNorm2d -> ReLU                        target_ops.run_conv_window(relu=True)    'conv_bn_relu'
+    Conv2d -> BatchNorm2d -> add(., r) -> ReLU           ... (relu=True, residual=r)              'conv_bn_add_relu'
+    Conv2d -> BatchNorm2d -> add (the other operand;     ... (relu=False)                         'conv_bn'
       a block's downsample branch)
     MaxPool2d / AvgPool2d / F.max_pool2d / F.avg_pool2d  target_ops.run_pool                      'pool'
     global average pool -> flatten -> Linear             target_ops.run_classifier_head           'head'
 
 The result is a ``torch.fx.GraphModule`` that SHARES the original's submodules, Parameters and buffers (same ``state_dict`` keys; the
 original is not modified, and ``train()`` / ``eval()`` / ``to()`` on either reach the same layers).  Every replaced window keeps the
-very modules it replaced and runs them whenever its runner does not apply -- CPU tensors, a switch that is off
+very modules it replaced -- every convolution window is one class, NativeConvWindow, whose runner's table (run_conv_window) names
+the member -- and runs them whenever its runner does not apply -- CPU tensors, a switch that is off
 (GHN3_NATIVE_OPS / _CONV / _ACT / _POOL / _HEAD / _EVALBN = 0), a limit of the kernels, autocast with GHN3_NATIVE_AMP=0 --, so on the
 CPU the nativized module computes what the original computes, bit for bit.  Tensors stay channels_last between native nodes; a stock
 node that reads a native node's result gets it NCHW-contiguous (the stock layers of this ROCm build return wrong gradients for
@@ -27,7 +28,7 @@ pass, the windows of pre-activation (v2) ResNets and DenseNets, whose BatchNorm 
 
     BatchNorm2d whose only user is a ReLU                target_ops.run_bn_act(relu=True)         'bn_relu'
     any other BatchNorm2d the first pass left            target_ops.run_bn_act(relu=False)        'bn'
-    any other Conv2d the first pass left for which       target_ops._conv_dispatch(_BARE): the    'conv'
+    any other Conv2d the first pass left for which       target_ops.run_conv_window(bn=None): the 'conv'
       `conv_refusal` is None; it leaves `stock_convs`      no-norm member, ConvOnly
     torch.cat([...], 1) of 2 .. 16 nodes                 target_ops.cell_concat                   'concat'
     an add of two nodes no window above consumed         target_ops.pair_sum                      'add'
@@ -40,7 +41,8 @@ it is opt-in whatever the figure.
 default; VGG, AlexNet, SqueezeNet and other networks without norm layers), which `conv_refusal` otherwise answers first, and the
 classifier such networks end in:
 
-    Conv2d(bias) -> ReLU                                 target_ops.run_conv_bias_act(relu=True)  'conv_bias_relu'
+    Conv2d(bias) -> ReLU                                 target_ops.run_conv_window(bn=None,      'conv_bias_relu'
+                                                           relu=True)
     Conv2d(bias) -> add(., r) -> ReLU                    ... (relu=True, residual=r)              'conv_bias_add_relu'
     any other Conv2d(bias) for which `conv_refusal(conv, ... (relu=False); it leaves              'conv_bias'
       biased=True)` is None                                `stock_convs`
@@ -92,33 +94,30 @@ class _Window(nn.Module):
         return ', '.join('%s=%s' % (k, type(v).__name__) for k, v in self.layers.items() if v is not None)
 
 
-class NativeConvBnAct(_Window):
-    """Conv2d -> BatchNorm2d [-> + residual] -> ReLU."""
+class NativeConvWindow(_Window):
+    """Conv2d [-> BatchNorm2d] [-> + residual] [-> ReLU]: the member of the dense-convolution family `target_ops.run_conv_window`
+    names for it, else the replaced layers in that order."""
+
+    def __init__(self, conv, bn=None, relu=False):
+        super().__init__(conv=conv, bn=bn)
+        self.relu = bool(relu)
+
+    @property
+    def conv_bn_relu(self):
+        """The window is a conv -> norm [-> + skip] -> ReLU one (what a downsample branch asks of the node that reads it)."""
+        return self.layers['bn'] is not None and self.relu
 
     def forward(self, x, residual=None):
         conv, bn = self.layers['conv'], self.layers['bn']
-        out = T.run_conv_bn_act(conv, bn, x, residual)
+        out = T.run_conv_window(conv, bn, x, self.relu, residual)
         if out is not None:
             return out
-        y = bn(conv(_stock_layout(x)))
+        y = conv(_stock_layout(x))
+        if bn is not None:
+            y = bn(y)
         if residual is not None:
             y = y + _stock_layout(residual)
-        return F.relu(y)
-
-
-class NativeConvBn(_Window):
-    """Conv2d -> BatchNorm2d without a ReLU (a downsample branch): the existing members of the dense-convolution family."""
-
-    def forward(self, x):
-        conv, bn = self.layers['conv'], self.layers['bn']
-        if T._native_input(x, 'GHN3_NATIVE_CONV') and T.zero_padded_conv(conv) and T._is_kind(bn, 'BatchNorm2d'):
-            xin, w = T._image_pad(x, conv.weight)
-            dil = T._pair(conv.dilation)[0]
-            if T.conv_desc_fits(T._conv_desc(xin, w, conv.stride, conv.padding, dil, False, 0.0)):
-                out = T._conv_dispatch(xin, w, T._norm_slot(bn), conv.stride, conv.padding, dil, False)
-                if out is not None:
-                    return out
-        return bn(conv(_stock_layout(x)))
+        return F.relu(y) if self.relu else y
 
 
 class NativePool(_Window):
@@ -160,39 +159,6 @@ class NativeBnAct(_Window):
         if out is not None:
             return out
         y = bn(_stock_layout(x))
-        return F.relu(y) if self.relu else y
-
-
-class NativeConv(_Window):
-    """A bare Conv2d the dense kernels take (windows='all'): the no-norm member of the dense-convolution family."""
-
-    def forward(self, x):
-        conv = self.layers['conv']
-        if T._native_input(x, 'GHN3_NATIVE_CONV') and T.zero_padded_conv(conv):
-            xin, w = T._image_pad(x, conv.weight)
-            dil = T._pair(conv.dilation)[0]
-            if T.conv_desc_fits(T._conv_desc(xin, w, conv.stride, conv.padding, dil, False, 0.0)):
-                out = T._conv_dispatch(xin, w, T._BARE, conv.stride, conv.padding, dil, False)
-                if out is not None:
-                    return out
-        return conv(_stock_layout(x))
-
-
-class NativeConvBias(_Window):
-    """Conv2d with a bias [-> + residual] [-> ReLU] (biased=True): the "bias" member of the dense-convolution family."""
-
-    def __init__(self, conv, relu):
-        super().__init__(conv=conv)
-        self.relu = bool(relu)
-
-    def forward(self, x, residual=None):
-        conv = self.layers['conv']
-        out = T.run_conv_bias_act(conv, x, self.relu, residual) if torch.is_tensor(x) and x.dim() == 4 else None
-        if out is not None:
-            return out
-        y = conv(_stock_layout(x))
-        if residual is not None:
-            y = y + _stock_layout(residual)
         return F.relu(y) if self.relu else y
 
 
@@ -310,6 +276,42 @@ class _Matcher:
     def input_of(node):
         return node.args[0] if node.args else node.kwargs.get('input')
 
+    def skip_add(self, r, add, same_kind):
+        """(the other operand, the ReLU node) when the window whose result is `r` takes `add`, the one node that reads r, and
+        the ReLU behind it: the add's only user is a ReLU, and r is not added to itself.  When both operands are results of the
+        same kind (`same_kind(node)`), the first one takes them.  Else None."""
+        other = add.args[1] if add.args[0] is r else add.args[0]
+        relu = next(iter(add.users)) if len(add.users) == 1 else None
+        if relu is None or not self.is_relu(relu) or self.input_of(relu) is not add or other is r:
+            return None
+        if add.args[1] is r and same_kind(add.args[0]):
+            return None
+        return other, relu
+
+    def flattened(self, fl):
+        """x when `fl`, a node with one user, is flatten(x, 1) -- nn.Flatten() or the function / method form --, else None."""
+        if not isinstance(fl, torch.fx.Node) or len(fl.users) != 1:
+            return None
+        if fl.op == 'call_module':
+            m = self.mods.get(fl.target)
+            ok = type(m) is nn.Flatten and m.start_dim == 1 and m.end_dim == -1
+        else:
+            ok = ((fl.op == 'call_function' and fl.target is torch.flatten) or (fl.op == 'call_method' and fl.target == 'flatten')) and \
+                tuple(fl.args[1:]) + tuple(fl.kwargs.values()) == (1,)
+        x = self.input_of(fl) if ok else None
+        return x if isinstance(x, torch.fx.Node) else None
+
+    def adaptive_pool(self, node):
+        """(size, stock) of an adaptive average pool node -- the nn.AdaptiveAvgPool2d itself, or a call of F.adaptive_avg_pool2d
+        with that size --, else (None, None)."""
+        m = self.mod(node, nn.AdaptiveAvgPool2d)
+        if m is not None:
+            return m.output_size, m
+        if node.op == 'call_function' and node.target is F.adaptive_avg_pool2d:
+            size = node.args[1] if len(node.args) > 1 else node.kwargs.get('output_size')
+            return size, lambda t: F.adaptive_avg_pool2d(t, size)
+        return None, None
+
     def chain(self, bn_node):
         """(conv node, conv, bn) when bn_node is the BatchNorm2d of a fusable Conv2d -> BatchNorm2d pair with one user each."""
         if not isinstance(bn_node, torch.fx.Node) or self.mod(bn_node, nn.BatchNorm2d) is None or len(bn_node.users) != 1:
@@ -341,6 +343,8 @@ class _Matcher:
 
     def conv_window(self, c):
         conv = self.mod(c, nn.Conv2d)
+        if conv is None:
+            return
         if self.biased and conv.bias is not None:
             return self.bias_window(c, conv)
         why = conv_refusal(conv)
@@ -358,23 +362,19 @@ class _Matcher:
         bn, x = self.mods[b.target], self.input_of(c)
         nxt = next(iter(b.users))
         if self.is_relu(nxt) and self.input_of(nxt) is b:
-            self.put(NativeConvBnAct(conv=conv, bn=bn), (x,), nxt, (nxt, b, c), 'conv_bn_relu')
+            self.put(NativeConvWindow(conv, bn, True), (x,), nxt, (nxt, b, c), 'conv_bn_relu')
             return
-        if nxt in self.native and type(self.mods[nxt.target]) is NativeConvBnAct and nxt.args[0] is not b:
+        if nxt in self.native and getattr(self.mods[nxt.target], 'conv_bn_relu', False) and nxt.args[0] is not b:
             # (the skip operand of a window that is in place already: the other branch of the block)
-            self.put(NativeConvBn(conv=conv, bn=bn), (x,), b, (b, c), 'conv_bn')
+            self.put(NativeConvWindow(conv, bn), (x,), b, (b, c), 'conv_bn')
             return
         if self.is_add(nxt):
-            other = nxt.args[1] if nxt.args[0] is b else nxt.args[0]
-            relu = next(iter(nxt.users)) if len(nxt.users) == 1 else None
-            fuse = relu is not None and self.is_relu(relu) and self.input_of(relu) is nxt and other is not b
-            # both operands are conv -> norm results (a block with a downsample branch): the first one takes the add and the ReLU
-            if fuse and nxt.args[1] is b and self.chain(nxt.args[0]) is not None:
-                fuse = False
-            if fuse:
-                self.put(NativeConvBnAct(conv=conv, bn=bn), (x, other), relu, (relu, nxt, b, c), 'conv_bn_add_relu')
+            # (a block with a downsample branch: both operands are conv -> norm results)
+            skip = self.skip_add(b, nxt, lambda node: self.chain(node) is not None)
+            if skip:
+                self.put(NativeConvWindow(conv, bn, True), (x, skip[0]), skip[1], (skip[1], nxt, b, c), 'conv_bn_add_relu')
             else:
-                self.put(NativeConvBn(conv=conv, bn=bn), (x,), b, (b, c), 'conv_bn')
+                self.put(NativeConvWindow(conv, bn), (x,), b, (b, c), 'conv_bn')
             return
         what = type(self.mods[nxt.target]).__name__ if nxt.op == 'call_module' else getattr(nxt.target, '__name__', str(nxt.target))
         self.stock[c.target] = 'the norm layer is followed by %s, neither a ReLU nor an add' % what
@@ -409,23 +409,11 @@ class _Matcher:
         """node: a Linear; its input flatten(global average pool(x), 1)."""
         fc = self.mod(node, nn.Linear)
         fl = self.input_of(node)
-        if fc is None or not isinstance(fl, torch.fx.Node) or len(fl.users) != 1:
+        gp = self.flattened(fl) if fc is not None else None
+        if gp is None or len(gp.users) != 1:
             return
-        if fl.op == 'call_module':
-            m = self.mods.get(fl.target)
-            ok = type(m) is nn.Flatten and m.start_dim == 1 and m.end_dim == -1
-        else:
-            ok = ((fl.op == 'call_function' and fl.target is torch.flatten) or (fl.op == 'call_method' and fl.target == 'flatten')) and \
-                tuple(fl.args[1:]) + tuple(fl.kwargs.values()) == (1,)
-        gp = self.input_of(fl) if ok else None
-        if not isinstance(gp, torch.fx.Node) or len(gp.users) != 1:
-            return
-        if gp.op == 'call_module':
-            ok = T._is_global_pool(self.mods.get(gp.target)) and type(self.mods.get(gp.target)) is nn.AdaptiveAvgPool2d
-        else:
-            size = gp.args[1] if len(gp.args) > 1 else gp.kwargs.get('output_size')
-            ok = gp.op == 'call_function' and gp.target is F.adaptive_avg_pool2d and size in (1, (1, 1), [1, 1])
-        if ok:
+        size, stock = self.adaptive_pool(gp)
+        if T._is_global_pool(stock) if isinstance(stock, nn.Module) else size in (1, (1, 1), [1, 1]):
             self.put(NativeHead(fc), (self.input_of(gp),), node, (node, fl, gp), 'head', nhwc=False)
 
     # ---- the opt-in windows of biased convolutions (biased=True) ----
@@ -445,34 +433,20 @@ class _Matcher:
             return
         nxt = next(iter(c.users)) if len(c.users) == 1 else None
         if nxt is not None and self.is_relu(nxt) and self.input_of(nxt) is c:
-            self.put(NativeConvBias(conv, True), (x,), nxt, (nxt, c), 'conv_bias_relu')
+            self.put(NativeConvWindow(conv, relu=True), (x,), nxt, (nxt, c), 'conv_bias_relu')
             return
-        if nxt is not None and self.is_add(nxt):
-            other = nxt.args[1] if nxt.args[0] is c else nxt.args[0]
-            relu = next(iter(nxt.users)) if len(nxt.users) == 1 else None
-            fuse = relu is not None and self.is_relu(relu) and self.input_of(relu) is nxt and other is not c
-            # both operands are biased convolutions: the first one takes the add and the ReLU
-            if fuse and nxt.args[1] is c and self.biased_result(nxt.args[0]):
-                fuse = False
-            if fuse:
-                self.put(NativeConvBias(conv, True), (x, other), relu, (relu, nxt, c), 'conv_bias_add_relu')
-                return
-        self.put(NativeConvBias(conv, False), (x,), c, (c,), 'conv_bias')
+        skip = self.skip_add(c, nxt, self.biased_result) if nxt is not None and self.is_add(nxt) else None
+        if skip:
+            self.put(NativeConvWindow(conv, relu=True), (x, skip[0]), skip[1], (skip[1], nxt, c), 'conv_bias_add_relu')
+        else:
+            self.put(NativeConvWindow(conv), (x,), c, (c,), 'conv_bias')
 
     def mlp_head_window(self, node):
         """node: a Linear whose input is flatten(x, 1); behind it (ReLU, Dropout, Linear) one to three times, one user each."""
         first = self.mod(node, nn.Linear)
         fl = self.input_of(node)
-        if first is None or not isinstance(fl, torch.fx.Node) or len(fl.users) != 1:
-            return
-        if fl.op == 'call_module':
-            m = self.mods.get(fl.target)
-            ok = type(m) is nn.Flatten and m.start_dim == 1 and m.end_dim == -1
-        else:
-            ok = ((fl.op == 'call_function' and fl.target is torch.flatten) or (fl.op == 'call_method' and fl.target == 'flatten')) and \
-                tuple(fl.args[1:]) + tuple(fl.kwargs.values()) == (1,)
-        x = self.input_of(fl) if ok else None
-        if not isinstance(x, torch.fx.Node):
+        x = self.flattened(fl) if first is not None else None
+        if x is None:
             return
         modules, nodes, last = [first], [node, fl], node
         while len(modules) < 3 * T.HEAD_MAX_LINEAR - 2:
@@ -492,14 +466,7 @@ class _Matcher:
             self.put(NativeMlpHead(modules), (x,), last, tuple(nodes), 'mlp_head', nhwc=False)
 
     def same_size_pool_window(self, node):
-        x, size = self.input_of(node), None
-        if node.op == 'call_module' and type(self.mods.get(node.target)) is nn.AdaptiveAvgPool2d:
-            stock = self.mods[node.target]
-            size = stock.output_size
-        elif node.op == 'call_function' and node.target is F.adaptive_avg_pool2d:
-            size = node.args[1] if len(node.args) > 1 else node.kwargs.get('output_size')
-            fn, const = node.target, size
-            stock = lambda t: fn(t, const)                                      # noqa: E731
+        x, (size, stock) = self.input_of(node), self.adaptive_pool(node)
         if isinstance(size, int):
             size = (size, size)
         if not (isinstance(x, torch.fx.Node) and isinstance(size, (tuple, list)) and len(size) == 2 and
@@ -511,8 +478,8 @@ class _Matcher:
     # ---- the opt-in windows (windows='all') ----
     def bn_window(self, b):
         """A BatchNorm2d the conv pass left: with its ReLU when that is its only user, else alone."""
-        bn, x = self.mods[b.target], self.input_of(b)
-        if not isinstance(x, torch.fx.Node):
+        bn, x = self.mod(b, nn.BatchNorm2d), self.input_of(b)
+        if bn is None or not isinstance(x, torch.fx.Node):
             return
         users = list(b.users)
         if len(users) == 1 and self.is_relu(users[0]) and self.input_of(users[0]) is b:
@@ -524,10 +491,10 @@ class _Matcher:
         """A Conv2d the dense kernels take that the first pass left -- not followed by a norm layer (the end of a dense layer, of
         a transition, of a pre-activation block), several users (a stem whose result is also a skip operand), a norm layer with
         several users --: it leaves the stock list."""
-        x = self.input_of(c)
-        if conv_refusal(self.mods[c.target]) is None and isinstance(x, torch.fx.Node):
+        conv, x = self.mod(c, nn.Conv2d), self.input_of(c)
+        if conv is not None and conv_refusal(conv) is None and isinstance(x, torch.fx.Node):
             self.stock.pop(c.target, None)
-            self.put(NativeConv(conv=self.mods[c.target]), (x,), c, (c,), 'conv')
+            self.put(NativeConvWindow(conv), (x,), c, (c,), 'conv')
 
     def concat_window(self, node):
         if not ((node.op == 'call_function' and node.target in (torch.cat, torch.concat)) and node.args):
@@ -548,35 +515,16 @@ class _Matcher:
         self.put(NativeAdd(), tuple(node.args), node, (node,), 'add')
 
     def run(self):
-        for node in list(self.graph.nodes):
-            if node.op == 'call_module' and self.mod(node, nn.Conv2d) is not None:
-                self.conv_window(node)
-        if self.extra:
-            for node in list(self.graph.nodes):
-                if node not in self.native and self.mod(node, nn.BatchNorm2d) is not None:
-                    self.bn_window(node)
-            for node in list(self.graph.nodes):
-                if node not in self.native and self.mod(node, nn.Conv2d) is not None:
-                    self.bare_conv_window(node)
-            for node in list(self.graph.nodes):
+        # (every window method looks at any node and returns where it is not the one the window starts from)
+        passes = ((True, self.conv_window),
+                  (self.extra, self.bn_window), (self.extra, self.bare_conv_window), (self.extra, self.concat_window),
+                  (self.extra, self.add_window),
+                  (True, self.pool_window), (True, self.head_window),
+                  (self.biased, self.mlp_head_window), (self.biased, self.same_size_pool_window))
+        for on, window in passes:
+            for node in list(self.graph.nodes) if on else ():
                 if node not in self.native:
-                    self.concat_window(node)
-            for node in list(self.graph.nodes):
-                if node not in self.native:
-                    self.add_window(node)
-        for node in list(self.graph.nodes):
-            if node not in self.native:
-                self.pool_window(node)
-        for node in list(self.graph.nodes):
-            if node.op == 'call_module' and node not in self.native:
-                self.head_window(node)
-        if self.biased:
-            for node in list(self.graph.nodes):
-                if node.op == 'call_module' and node not in self.native:
-                    self.mlp_head_window(node)
-            for node in list(self.graph.nodes):
-                if node not in self.native:
-                    self.same_size_pool_window(node)
+                    window(node)
         # a stock node (the output included) reads a native node's result NCHW-contiguous; the head reads either layout
         for node in list(self.nhwc):
             readers = [u for u in node.users if u not in self.native]

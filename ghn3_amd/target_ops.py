@@ -498,6 +498,19 @@ def conv_desc_fits(d):
     return d.Ho > 0 and d.Wo > 0 and d.N * d.H * d.W * widest < 2 ** 31 and d.N * d.Ho * d.Wo * widest < 2 ** 31
 
 
+def _conv_geometry_fits(x, w, residual, stride, padding, dilation):
+    """What the members that take a torch.nn network's convolution ask of its geometry: positive strides and dilation, padding
+    that is not negative, the two 2^31 rules (`conv_desc_fits`), and a skip tensor that is an fp32 CUDA tensor of the output's
+    shape (or None)."""
+    (sh, sw), (ph, pw) = _pair(stride), _pair(padding)
+    if min(sh, sw) <= 0 or min(ph, pw) < 0 or int(dilation) <= 0:
+        return False
+    d = _conv_desc(x, w, stride, padding, dilation, False, 0.0)
+    if not conv_desc_fits(d):
+        return False
+    return residual is None or (_f32_cuda(residual) and tuple(residual.shape) == (d.N, d.C_out, d.Ho, d.Wo))
+
+
 def _conv_forward(ctx, mode, x, w, norm, stride, pad, dil, relu, eps, keep=True):
     """The forward of ConvBn ('batch': norm = (gamma, beta)), ConvOnly ('none': ()) and ConvBnEval ('frozen': (gamma, beta,
     running_mean, running_var)).  Returns (out, stats -- None but for 'batch').  z and `keep` as for _dwpw_forward; the no-norm
@@ -646,15 +659,8 @@ def act_enabled():
 def _conv_act_applicable(x, w, gamma, beta, residual, stride, padding, dilation):
     """Every limit of the C side (check_cdesc, the two 2^31 rules included) for the two members, and what they ask of the skip
     tensor: an fp32 CUDA tensor of the output's shape."""
-    if not (act_enabled() and ConvBn.applicable(x, w, gamma, beta) and beta.numel() == w.shape[0]):
-        return False
-    (sh, sw), (ph, pw) = _pair(stride), _pair(padding)
-    if min(sh, sw) <= 0 or min(ph, pw) < 0 or int(dilation) <= 0:
-        return False
-    d = _conv_desc(x, w, stride, padding, dilation, False, 0.0)
-    if not conv_desc_fits(d):
-        return False
-    return residual is None or (_f32_cuda(residual) and tuple(residual.shape) == (d.N, d.C_out, d.Ho, d.Wo))
+    return act_enabled() and ConvBn.applicable(x, w, gamma, beta) and beta.numel() == w.shape[0] and \
+        _conv_geometry_fits(x, w, residual, stride, padding, dilation)
 
 
 def _conv_act_forward(ctx, frozen, x, w, norm, res, stride, pad, dil, relu, eps, keep=True):
@@ -802,15 +808,8 @@ class ConvBiasAct(torch.autograd.Function):
     def applicable(x, w, bias, residual=None, stride=1, padding=0, dilation=1):
         """Every limit of the C side (check_cdesc, the two 2^31 rules included), and what the op asks of the bias and the skip
         tensor: fp32 CUDA tensors of C_out elements / of the output's shape."""
-        if not (bias_enabled() and _conv_applicable(x, w) and _f32_cuda(bias) and bias.numel() == w.shape[0]):
-            return False
-        (sh, sw), (ph, pw) = _pair(stride), _pair(padding)
-        if min(sh, sw) <= 0 or min(ph, pw) < 0 or int(dilation) <= 0:
-            return False
-        d = _conv_desc(x, w, stride, padding, dilation, False, 0.0)
-        if not conv_desc_fits(d):
-            return False
-        return residual is None or (_f32_cuda(residual) and tuple(residual.shape) == (d.N, d.C_out, d.Ho, d.Wo))
+        return bias_enabled() and _conv_applicable(x, w) and _f32_cuda(bias) and bias.numel() == w.shape[0] and \
+            _conv_geometry_fits(x, w, residual, stride, padding, dilation)
 
     @staticmethod
     def forward(ctx, x, w, bias, residual, stride, pad, dil, relu, relu_in, keep):
@@ -1295,11 +1294,13 @@ def _stock(layers, x):
     return x
 
 
-def _plain_conv(conv):
-    """A bias-free, ungrouped convolution with numeric padding and one dilation for both axes (what the dense kernels take)."""
-    return hasattr(conv, 'kernel_size') and getattr(conv, 'bias', None) is None and not isinstance(conv.padding, str) and \
-        getattr(conv, 'groups', 1) == 1 and torch.is_tensor(getattr(conv, 'weight', None)) and \
-        len(set(_pair(getattr(conv, 'dilation', 1)))) == 1
+def _plain_conv(conv, biased=False):
+    """An ungrouped convolution with numeric padding and one dilation for both axes (what the dense kernels take): bias-free, or
+    -- biased=True -- with a bias tensor."""
+    bias = getattr(conv, 'bias', None)
+    return hasattr(conv, 'kernel_size') and (torch.is_tensor(bias) if biased else bias is None) and \
+        not isinstance(conv.padding, str) and getattr(conv, 'groups', 1) == 1 and \
+        torch.is_tensor(getattr(conv, 'weight', None)) and len(set(_pair(getattr(conv, 'dilation', 1)))) == 1
 
 
 def _image_pad(x, w):
@@ -1384,50 +1385,67 @@ def run_layer_seq(seq, x):
     return x
 
 
-def zero_padded_conv(conv):
+def zero_padded_conv(conv, biased=False):
     """`_plain_conv` and zero padding: what a convolution of a torch.nn network has to be for the dense kernels (the layers of
     ghn3_amd.ops never pad otherwise; an arbitrary nn.Conv2d may reflect, replicate or wrap)."""
-    return _plain_conv(conv) and getattr(conv, 'padding_mode', 'zeros') == 'zeros'
+    return _plain_conv(conv, biased) and getattr(conv, 'padding_mode', 'zeros') == 'zeros'
+
+
+def run_conv_window(conv, bn, x, relu, residual=None):
+    """Conv2d [-> BatchNorm2d] [-> + residual] [-> ReLU] of a torch.nn network (`bn` None: no norm layer) on the member of the
+    dense-convolution family the window names; the NHWC result, or None where no member applies and the caller keeps its stock
+    layers:
+
+        bn           conv.bias  relu    member
+        BatchNorm2d  none       yes     ConvBnAct / ConvBnActEval, chosen by `_norm_slot`; residual allowed; GHN3_NATIVE_ACT=0: None
+        BatchNorm2d  none       no      ConvBn / ConvBnEval through `_conv_dispatch`; no residual; GHN3_NATIVE_ACT is not asked
+        None         tensor     either  ConvBiasAct; residual allowed; GHN3_NATIVE_BIAS=0: None
+        None         none       no      ConvOnly through `_conv_dispatch(_BARE)`; no residual
+        anything else                   None: a bias together with a norm layer, a bare convolution with a ReLU or a residual,
+                                        a norm layer without a ReLU but with a residual, a norm layer that is no BatchNorm2d
+
+    Every row: None for CPU tensors, another dtype, GHN3_NATIVE_OPS=0, GHN3_NATIVE_CONV=0, autocast with GHN3_NATIVE_AMP=0, a
+    grouped or oddly padded convolution (`zero_padded_conv`) and a limit of the kernels (the member's `applicable`; the two rows
+    of `_conv_dispatch`, whose members leave the 2^31 rules to the C side, ask `_conv_geometry_fits` first); 3-channel images as
+    `_image_pad` says; the running statistics of a batch-statistics member follow as torch's would (`_update_running_stats`)."""
+    biased = getattr(conv, 'bias', None) is not None
+    if not (_native_input(x, 'GHN3_NATIVE_CONV') and zero_padded_conv(conv, biased)):
+        return None
+    if bn is None:
+        if not (bias_enabled() if biased else not relu and residual is None):
+            return None
+        slot = _BARE
+    else:
+        if biased or not _is_kind(bn, 'BatchNorm2d') or not (act_enabled() if relu else residual is None):
+            return None
+        slot = _norm_slot(bn)
+    xin, w = _image_pad(x, conv.weight)
+    args = (residual, conv.stride, conv.padding, _pair(conv.dilation)[0])
+    if biased:
+        if ConvBiasAct.applicable(xin, w, conv.bias, *args):
+            return conv_bias_act(xin, w, conv.bias, *args, relu, False)
+    elif not relu:
+        if _conv_geometry_fits(xin, w, *args):
+            return _conv_dispatch(xin, w, slot, *args[1:], False)
+    elif slot.kind == 'frozen':
+        if ConvBnActEval.applicable(xin, w, slot.gamma, slot.beta, slot.mean, slot.var, *args):
+            return conv_bn_act_eval(xin, w, slot.gamma, slot.beta, slot.mean, slot.var, *args, False, slot.eps)
+    elif slot.kind == 'batch':
+        if ConvBnAct.applicable(xin, w, slot.gamma, slot.beta, *args):
+            out, stats = conv_bn_act(xin, w, slot.gamma, slot.beta, *args, False, slot.eps)
+            _update_running_stats(slot, stats, out)
+            return out
+    return None
 
 
 def run_conv_bn_act(conv, bn, x, residual=None):
-    """Conv2d -> BatchNorm2d [-> + residual] -> ReLU of a torch.nn network on the "act" member that fits the norm slot
-    (`_norm_slot`: ConvBnAct with batch statistics, whose running statistics follow as torch's would; ConvBnActEval in eval mode),
-    3-channel images as `_image_pad` says; the NHWC result, or None where the node does not apply (the caller keeps its stock
-    layers)."""
-    if not (act_enabled() and _native_input(x, 'GHN3_NATIVE_CONV') and zero_padded_conv(conv) and _is_kind(bn, 'BatchNorm2d')):
-        return None
-    slot = _norm_slot(bn)
-    if slot.kind not in ('batch', 'frozen'):
-        return None
-    xin, w = _image_pad(x, conv.weight)
-    args = (residual, conv.stride, conv.padding, _pair(conv.dilation)[0])
-    g, b = slot.gamma, slot.beta
-    if slot.kind == 'frozen':
-        if ConvBnActEval.applicable(xin, w, g, b, slot.mean, slot.var, *args):
-            return conv_bn_act_eval(xin, w, g, b, slot.mean, slot.var, *args, False, slot.eps)
-    elif ConvBnAct.applicable(xin, w, g, b, *args):
-        out, stats = conv_bn_act(xin, w, g, b, *args, False, slot.eps)
-        _update_running_stats(slot, stats, out)
-        return out
-    return None
+    """Conv2d -> BatchNorm2d [-> + residual] -> ReLU: the first row of `run_conv_window`."""
+    return None if bn is None else run_conv_window(conv, bn, x, True, residual)
 
 
 def run_conv_bias_act(conv, x, relu, residual=None):
-    """Conv2d WITH a bias [-> + residual] [-> ReLU] of a torch.nn network on ConvBiasAct, 3-channel images as `_image_pad` says;
-    the NHWC result, or None where the node does not apply -- CPU tensors, another dtype, GHN3_NATIVE_OPS=0, GHN3_NATIVE_CONV=0,
-    GHN3_NATIVE_BIAS=0, autocast with GHN3_NATIVE_AMP=0, a grouped, oddly padded or unbiased convolution, a limit of the kernels --
-    and the caller keeps its stock layers."""
-    if not (bias_enabled() and _native_input(x, 'GHN3_NATIVE_CONV') and torch.is_tensor(getattr(conv, 'bias', None)) and
-            hasattr(conv, 'kernel_size') and not isinstance(conv.padding, str) and getattr(conv, 'groups', 1) == 1 and
-            getattr(conv, 'padding_mode', 'zeros') == 'zeros' and torch.is_tensor(getattr(conv, 'weight', None)) and
-            len(set(_pair(getattr(conv, 'dilation', 1)))) == 1):
-        return None
-    xin, w = _image_pad(x, conv.weight)
-    args = (residual, conv.stride, conv.padding, _pair(conv.dilation)[0])
-    if ConvBiasAct.applicable(xin, w, conv.bias, *args):
-        return conv_bias_act(xin, w, conv.bias, *args, relu, False)
-    return None
+    """Conv2d WITH a bias [-> + residual] [-> ReLU]: the third row of `run_conv_window`; None for an unbiased convolution."""
+    return None if getattr(conv, 'bias', None) is None else run_conv_window(conv, None, x, relu, residual)
 
 
 def run_bn_act(bn, x, relu):
